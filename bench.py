@@ -2,7 +2,7 @@
 """Headline benchmark: 3-D patch-tokens/sec, forward + backward, 2-modality 128^3 p16 cross-attention
 ViT (BASELINE.json configs[1]: d=768, 12 heads, mlp 3072, 2x2 blocks, N=513) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = zero-grad, per-step bf16 re-cast of the fp32 master weights (what an optimizer step
@@ -259,10 +259,38 @@ def emit(obj):
         os.write(_JSON_FD, line)
 
 
+DUMP_GRAD_SAMPLE = 1 << 23     # gradient elements kept in grad_sample.npy (32 MB of float32)
+
+
+def dump_outputs(out_dir, logits, loss, named_params):
+    """--dump-outputs: what the timed step hands its caller, from its last timed step, as float32 / float64 .npy files.
+      logits.npy       (B, num_classes) float32
+      loss.npy         () float32
+      grad_norms.npy   (n_params,) float64: L2 norm of every parameter's gradient, in model.named_parameters() order
+      grad_sample.npy  (n,) float32: the gradients of all parameters flattened and concatenated in that order; all of them if they fit in
+                       DUMP_GRAD_SAMPLE elements, otherwise those at DUMP_GRAD_SAMPLE sorted positions drawn with a fixed seed (the same
+                       positions in every run: they depend only on the parameter count)
+    Inputs and weights are seeded, so two builds run with the same arguments can be compared file for file.  Logits and loss repeat
+    bit for bit; the gradients only up to the order of the fp32 atomic sums of the default backward (XVIT_DETERMINISTIC=1 fixes it)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for _, p in named_params]
+    np.save(os.path.join(out_dir, "grad_norms.npy"), np.array([float(g.detach().double().norm()) for g in grads], dtype=np.float64))
+    flat = torch.cat([g.detach().reshape(-1).float() for g in grads])
+    if flat.numel() > DUMP_GRAD_SAMPLE:
+        gen = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, flat.numel(), (DUMP_GRAD_SAMPLE,), generator=gen).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, "grad_sample.npy"), flat.cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=126, help="per-GPU batch of volume pairs.  Throughput rises with batch until ~126 (42: 2.79 M, 84: 2.99 M, 126: 3.03 M, "
                     "252: 3.06 M tokens/s; 18.7 GB of the 288 GB HBM at 126); 126*513 rows = 253 row tiles of 256 -> 759 / 1518 / 2277 / 3036 tiles per GEMM "
@@ -278,7 +306,11 @@ def main():
                     "pays off when the step is host-bound, i.e. at small per-GPU batch")
     ap.add_argument("--single-stream", action="store_true", help="run the modality branches on one stream (used for the rocprof "
                     "summary under profiles/, so per-kernel durations are not stretched by a concurrently running kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's logits, loss and (a fixed sample of the) gradients "
+                    "to DIR/*.npy, e.g. DIR = bench_outputs (git-ignored); rank 0; see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.single_stream:
         os.environ["XVIT_STREAMS"] = "0"
@@ -324,7 +356,7 @@ def main():
         for p in params:
             p.grad = None
         xvit.invalidate_shadows()          # weights "changed": pay the fp32 -> bf16 operand cast every step
-        _, loss = model(img, labels)
+        logits, loss = model(img, labels)
         loss.backward()
         if reducer is not None:
             if timing[0]:
@@ -335,7 +367,7 @@ def main():
                 exposed.append((e0, e1))
             else:
                 reducer.finish()
-        return loss
+        return logits, loss
 
     timing = [False]
     if reducer is not None:
@@ -348,7 +380,7 @@ def main():
         eager_step = step
 
         def step():                                   # noqa: F811
-            return graphed()[1]
+            return graphed()
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -367,7 +399,7 @@ def main():
     timing[0] = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        logits, loss = step()
     fence()
     dt = time.perf_counter() - t0
     timing[0] = False
@@ -379,7 +411,9 @@ def main():
     log(f"timed region: {ms:.2f} ms/step")
     tokens_per_s = world * B * M * P * args.steps / dt
     loss_val = float(loss.detach())
-    del loss          # frees the last step's autograd graph (a live graph pins its AccumulateGrad nodes to the streams they were created
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logits, loss, list(model.named_parameters()))
+    del logits, loss  # frees the last step's autograd graph (a live graph pins its AccumulateGrad nodes to the streams they were created
                       # on, which a later HIP-graph capture of the step cannot synchronise with: see xvit/graph.py)
 
     out = {
