@@ -42,3 +42,58 @@ def note(name, value):
         with open(path, "a") as f:
             f.write(f"{name} {value:.4e}\n")
     return value
+
+
+# ---- exact-arithmetic operands: a bit-exact oracle for the GEMM at any size ------------------------------------------
+# Operands in {-3..3} 2^-s are exact in bf16, every product is an integer multiple of 2^-(sa+sb) of magnitude <= 9 units, and
+# every partial sum of K <= 2^24 / 9 (~1.8M) of them stays below 2^24 units: the fp32 sum is exact in ANY order (per K-split, in
+# the split-K slab sum, with accumulate=True).  A plain fp32 matmul on the CPU is then the exact product, and the kernel's fp32
+# output must equal it bit for bit (bf16 outputs: its round-to-nearest-even, ref.to(torch.bfloat16)).
+
+def exact_operands(shape, seed, s):
+    """fp32 CPU tensor of values in {-3..3} * 2^-s (exactly representable in bf16)."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-3, 4, tuple(shape), generator=g, dtype=torch.int8).float() * 2.0 ** -s
+
+
+def exact_grid(shape, seed, unit, span):
+    """fp32 CPU tensor of integers in [-span, span] times `unit` (bias / residual / accumulate prefill on the product's grid)."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-span, span + 1, tuple(shape), generator=g, dtype=torch.int32).float() * unit
+
+
+def bf16_ulp(x):
+    """Spacing of bf16 numbers at |x| (0 at x = 0): 2^(e - 8) for |x| in [2^(e-1), 2^e)."""
+    x = x.double()
+    _, e = torch.frexp(x)
+    return torch.where(x == 0, torch.zeros_like(x), torch.ldexp(torch.ones_like(x), e - 8))
+
+
+def gemm_coords(shape, flat):
+    """Where element `flat` of a GEMM output of `shape` ([..., M, N], or [N]) sits in the 256x256 kernel: batch, (row, col), its
+    256x256 tile, the 128x64 sub-tile of the wave (2 x 4 waves) and the 16x16 MFMA fragment inside that sub-tile."""
+    if len(shape) == 1:   # a row vector (column sums)
+        return f"(col {flat}): 256x256 tile column {flat // 256}, wave sub-tile column {(flat % 256) // 64}, 16x16 fragment column {(flat % 64) // 16}"
+    M, N = shape[-2], shape[-1]
+    b, rc = divmod(flat, M * N)
+    r, c = divmod(rc, N)
+    return (f"{'batch %d, ' % b if len(shape) > 2 else ''}(row {r}, col {c}): 256x256 tile ({r // 256}, {c // 256}), "
+            f"wave sub-tile ({(r % 256) // 128}, {(c % 256) // 64}), 16x16 fragment ({(r % 128) // 16}, {(c % 64) // 16})")
+
+
+def assert_exact(out, ref, what="", tol=None):
+    """out (any device, fp32 / bf16) against the CPU reference: bit-equal to ref rounded to out's dtype, or (tol given: a
+    tensor or scalar) |out - ref| <= tol element-wise.  NaN anywhere in out fails, so prefill outputs with NaN: an element
+    that is never written fails too.  The message names the number of wrong elements and where the first one sits."""
+    o = out.detach().cpu()
+    assert o.shape == ref.shape, f"{what}: shape {tuple(o.shape)} != {tuple(ref.shape)}"
+    if tol is None:
+        bad = o != ref.to(o.dtype)
+    else:
+        bad = ~((o.double() - ref.double()).abs() <= tol)
+    n = int(bad.sum())
+    if n:
+        flat = int(bad.reshape(-1).nonzero()[0])
+        got, want = float(o.reshape(-1)[flat]), float(ref.reshape(-1)[flat])
+        raise AssertionError(f"{what}: {n} of {o.numel()} elements wrong; first at {gemm_coords(tuple(o.shape), flat)}: "
+                             f"{got!r} != {want!r} ({o.dtype})")

@@ -14,10 +14,11 @@ def _ops():
     return ops
 
 
-@pytest.fixture(autouse=True, params=[(0, 0), (1, 0), (0, 1)], ids=["auto", "tile128", "narrow-epilogue"])
+@pytest.fixture(autouse=True, params=[(0, 0), (1, 0), (0, 1), (2, 0)], ids=["auto", "tile128", "narrow-epilogue", "tile256"])
 def gemm_variant(request):
-    """Every case runs under the automatic choices, with the 128x128 kernel forced, and with the 8-byte-per-lane epilogue
-    forced (bf16 outputs of the 256x256 kernel normally take the 16-byte-per-lane epilogue) — xvit_set_option."""
+    """Every case runs under the automatic choices, with the 128x128 kernel forced, with the 8-byte-per-lane epilogue
+    forced (bf16 outputs of the 256x256 kernel normally take the 16-byte-per-lane epilogue), and with the 256x256 kernel
+    forced wherever M, N >= 256 (small grids included, e.g. the TN split-K slab path) — xvit_set_option."""
     tile, epi = request.param
     _ops().set_option("gemm_tile", tile)
     _ops().set_option("gemm_epilogue", epi)
