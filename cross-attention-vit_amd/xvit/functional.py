@@ -394,13 +394,16 @@ AUX_MODE = 0 if os.environ.get("XVIT_GELU_AUX", "deriv") == "z" else 1
 # "auto" (default): low-rank wherever the GPU is the bound — XATTN_AUTO_ROWS token rows or more, or a step being captured into a HIP
 # graph — and the literal order on small eager batches, which are bound by the host: it is 15 launches per fusion instead of 22
 # (the reference's run shape at batch 8, eager: 13.0 vs 14.7 ms per step; captured: 8.59 vs 8.44 — tools/config_step_bench.py mist).
+# Above 16 heads the literal order is the only form, whatever XATTN_FORM says (captured steps included).  Heads narrower or wider than
+# 64 have neither: the CLS-query kernel refuses them like the self-attention kernels do (xvit_cls_xattn_fwd: "head dim .. unsupported").
 XATTN_FORM = os.environ.get("XVIT_XATTN_FORM", "auto")
 XATTN_AUTO_ROWS = 8192
 
 
 def _xattn_lowrank_ok(H, d, rows):
-    """Shapes the low-rank form is built for (otherwise the dense form runs): 64-wide heads, H <= 16 (one 16-column operand).  Dropout on
-    the probabilities is part of it (the kept weights feed the row sums; bv is weighted by their sum: csrc/head_linear.hip)."""
+    """Shapes the low-rank form is built for: H <= 16 (one 16-column operand).  Above that the dense form runs; it too needs 64-wide heads
+    (d == 64 H), which no form of the fusion goes without.  Dropout on the probabilities is part of it (the kept weights feed the row sums;
+    bv is weighted by their sum: csrc/head_linear.hip)."""
     if XATTN_FORM == "dense" or not (d == 64 * H and H <= 16 and d <= 1024):
         return False
     return XATTN_FORM == "lowrank" or rows >= XATTN_AUTO_ROWS or torch.cuda.is_current_stream_capturing()
@@ -631,7 +634,7 @@ def cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_
         g["bv"] = ops.head_bias_grad(doc, rz[2], H) if drop else ops.colsum(doc)
         g["bk"] = bk0                                                              # analytically zero: sum_n ds[n] = 0
         return _cross_backward_tail(g, dq, dhn, hn, q, xi, xj, mu, rs, ln1w, wq_s, B, N, d, dy, want_dcat_b16)
-    # the reference's literal order (XVIT_XATTN_FORM=dense, more than 16 heads, head widths other than 64): the K/V projection's
+    # the reference's literal order (XVIT_XATTN_FORM=dense, small eager batches under "auto", more than 16 heads): the K/V projection's
     # gradient through the [B N, 2 d] tensor — a K = 2 d dgrad GEMM, a wgrad GEMM and a column-sum pass
     doc = _dgrad(dyb1, wp_s)
     dq, dkv = ops.cls_xattn_bwd(q, kv, p, doc, B, N, H, scale, dropout=(pd, seeds[0]))

@@ -199,19 +199,29 @@ def tensor_sha256(t: torch.Tensor) -> str:
 # The single-token CLS path (wq, proj and the FFN of the cross fusion, the heads: `exact=True` below)
 # runs fp32 operands on the HIP side as well (xvit_linear_f32) and is therefore not rounded here.
 # GPU-vs-emulation isolates kernel bugs from the (expected) cost of bf16 operands.
+# The fusion's attention has two HIP forms with different rounding points (xvit.functional.XATTN_FORM): `xattn` picks the one
+# emulated where both apply (64-wide heads, H <= 16) — "lowrank" (default) or "literal", the dense form's order (K and V stored
+# bf16, q, P and proj fp32).  Above 16 heads only the literal order exists, on both sides.
 
 _QUANT = None
+_XATTN = "lowrank"
 
 
 class emulate_bf16:
+    def __init__(self, xattn="lowrank"):
+        if xattn not in ("lowrank", "literal"):
+            raise ValueError(f"emulate_bf16: xattn must be 'lowrank' or 'literal', not {xattn!r}")
+        self._xattn = xattn
+
     def __enter__(self):
-        global _QUANT
+        global _QUANT, _XATTN
         self._prev, _QUANT = _QUANT, bf16_round
+        self._prev_xattn, _XATTN = _XATTN, self._xattn
         return self
 
     def __exit__(self, *exc):
-        global _QUANT
-        _QUANT = self._prev
+        global _QUANT, _XATTN
+        _QUANT, _XATTN = self._prev, self._prev_xattn
         return False
 
 
@@ -306,9 +316,11 @@ def self_block(sd, p, x, H):
 
 
 def cls_cross_attention(sd, p, x, H):
-    """model_cross.py:88-102: the query is row 0 only; keys/values are all N rows."""
+    """model_cross.py:88-102: the query is row 0 only; keys/values are all N rows.  Emulation mode: this literal order rounds where the
+    dense HIP form does (q fp32, k and v stored bf16, P fp32 for the one query row, proj fp32); the low-rank form's rounding points
+    unless emulate_bf16(xattn="literal") asks for these."""
     d = x.shape[-1]
-    if _QUANT is not None and d == 64 * H and H <= 16:
+    if _QUANT is not None and _XATTN == "lowrank" and d == 64 * H and H <= 16:
         return _cls_cross_attention_lowrank_emulated(sd, p, x, H)
     q = _split_heads(linear(x[:, 0:1], sd[p + ".wq.weight"], sd[p + ".wq.bias"], exact=True), H)
     k = _split_heads(linear(x, sd[p + ".wk.weight"], sd[p + ".wk.bias"], store=True), H)

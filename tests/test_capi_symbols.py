@@ -85,6 +85,27 @@ def test_head_linear_argument_errors_do_not_launch():
     assert lib.xvit_set_dropout_epoch(P + 4) < 0 and lib.xvit_set_dropout_epoch(None) == 0                 # 8-byte aligned counter, NULL = off
 
 
+def test_cls_xattn_argument_errors_do_not_launch():
+    """The CLS-query attention kernels (csrc/cls_xattn.hip, the fusion's literal order) take 64-wide heads only and an N whose fp32 score row
+    fits the 160 KiB of LDS (N <= 38 908): anything else is refused on the host, with the reason, before any launch.  Dummy non-null
+    addresses, so the null-pointer check does not answer first."""
+    from xvit import _lib
+    lib = _lib.load()
+    P = 256
+    d, ld = 768, 1536
+    fwd = lambda H, N, dh: lib.xvit_cls_xattn_fwd(None, 0, P, d, P, P + 2 * d, N * ld, ld, P, d, P, d, P, 2, H, N, dh, 0.125, 0.0, 0, None)
+    bwd = lambda H, N, dh: lib.xvit_cls_xattn_bwd(P, d, P, P + 2 * d, N * ld, ld, P, P, d, P, d, P, P + 2 * d, None, 2, H, N, dh, 0.125, 0.0, 0, None)
+    for call, name in ((fwd, b"xvit_cls_xattn_fwd"), (bwd, b"xvit_cls_xattn_bwd")):
+        assert call(24, 513, 32) < 0
+        msg = lib.xvit_last_error_string()
+        assert name in msg and b"head dim 32 unsupported" in msg, msg
+        assert call(6, 513, 128) < 0 and b"head dim 128 unsupported" in lib.xvit_last_error_string()
+        assert call(12, 38909, 64) < 0
+        msg = lib.xvit_last_error_string()
+        assert name in msg and b"N=38909 too long" in msg, msg
+        assert call(12, 1 << 20, 64) < 0 and b"too long" in lib.xvit_last_error_string()
+
+
 def test_modules_have_reference_state_dict_keys():
     import ref_cpu as R
     import xvit

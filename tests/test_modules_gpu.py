@@ -258,6 +258,10 @@ def test_unobserved_last_block_cls_only_path_matches_full_path(name, over):
     """ModelCross runs its last MultiScaleBlock CLS-only when nothing observes the block's output (the heads read
     x[m][:, 0] only, model_cross.py:203); with a forward hook it produces the reference's full token tensors.  Both
     paths must give the same logits, loss and parameter gradients."""
+    _check_unobserved_matches_observed(name, over)
+
+
+def _check_unobserved_matches_observed(name, over):
     import xvit
     cfg = R.make_config(name, **over)
     img, labels = R.make_inputs(cfg, 3, seed=5)

@@ -209,3 +209,39 @@ def test_low_rank_emulation_is_the_same_function_as_the_literal_cross_attention(
     finally:
         R._QUANT = prev
     assert float((low - ref).norm() / ref.norm()) < 2e-6
+
+
+def test_literal_order_emulation_switch():
+    """emulate_bf16(xattn="literal") rounds the fusion's attention where the dense HIP form does (k and v stored bf16; q, P and proj fp32)
+    instead of where the low-rank form does.  Rounding off, it is the fp32 function; rounding on, it differs from the low-rank emulation
+    (the switch takes effect) by no more than bf16 storage of K and V, at the attention output and through the whole model; the
+    default stays the low-rank emulation and the switch is undone on exit."""
+    import ref_cpu as R
+    cfg = R.make_config("tiny")
+    sd = R.make_state_dict(cfg, seed=2)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(3, 17, cfg.hidden_dim, generator=g)
+    p = "transformer.0.fusion.0.attn.fn"
+    ref = R.cls_cross_attention(sd, p, x, cfg.num_heads)
+    with R.emulate_bf16(xattn="literal"):
+        prev, R._QUANT = R._QUANT, (lambda t: t)
+        try:
+            lit_exact = R.cls_cross_attention(sd, p, x, cfg.num_heads)
+        finally:
+            R._QUANT = prev
+        lit = R.cls_cross_attention(sd, p, x, cfg.num_heads)
+    with R.emulate_bf16():
+        low = R.cls_cross_attention(sd, p, x, cfg.num_heads)
+    assert R._QUANT is None and R._XATTN == "lowrank"
+    assert rel(lit_exact, ref) < TOL
+    assert not torch.equal(lit, low)
+    assert 1e-4 < rel(lit, ref) < 8e-3 and rel(lit, low) < 8e-3, (rel(lit, ref), rel(lit, low))
+    img, labels = R.make_inputs(cfg, 3, seed=1)
+    with R.emulate_bf16(xattn="literal"):
+        l_lit, _ = R.model_cross_forward(sd, img, labels, cfg)
+    with R.emulate_bf16():
+        l_low, _ = R.model_cross_forward(sd, img, labels, cfg)
+    l_ref, _ = R.model_cross_forward(sd, img, labels, cfg)
+    assert rel(l_lit, l_low) < 2e-2 and rel(l_lit, l_ref) < 2e-2, (rel(l_lit, l_low), rel(l_lit, l_ref))
+    with pytest.raises(ValueError):
+        R.emulate_bf16(xattn="dense")

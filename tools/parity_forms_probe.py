@@ -12,26 +12,9 @@ for name, batch in (("base", 2), ("small", 2)):
     ref_logits, _ = R.model_cross_forward(sd, img, labels, cfg)
     cap_ref = {}; R.model_cross_forward(sd, img, labels, cfg, capture=cap_ref)
     for emu_low in (True, False):
-        saved = R._cls_cross_attention_lowrank_emulated
-        if not emu_low:
-            R._cls_cross_attention_lowrank_emulated = None
-            orig = R.cls_cross_attention
         cap = {}
-        with R.emulate_bf16():
-            if not emu_low:
-                # literal emulation: bypass the low-rank branch
-                q0 = R._QUANT
-                def lit(sd_, p, x, H, _orig=orig):
-                    d = x.shape[-1]
-                    q = R._split_heads(R.linear(x[:, 0:1], sd_[p + ".wq.weight"], sd_[p + ".wq.bias"], exact=True), H)
-                    k = R._split_heads(R.linear(x, sd_[p + ".wk.weight"], sd_[p + ".wk.bias"], store=True), H)
-                    v = R._split_heads(R.linear(x, sd_[p + ".wv.weight"], sd_[p + ".wv.bias"], store=True), H)
-                    o, _ = R.softmax_attention(q, k, v, (d // H) ** -0.5)
-                    return R.linear(R._merge_heads(o), sd_[p + ".proj.weight"], sd_[p + ".proj.bias"], exact=True)
-                R.cls_cross_attention = lit
+        with R.emulate_bf16(xattn="lowrank" if emu_low else "literal"):
             emu_logits, _ = R.model_cross_forward(sd, img, labels, cfg, capture=cap)
-        if not emu_low:
-            R.cls_cross_attention = orig; R._cls_cross_attention_lowrank_emulated = saved
         for form in ("lowrank", "dense"):
             XF.XATTN_FORM = form
             model = xvit.ModelCross(cfg).to(dev); model.load_state_dict(sd); model.train()
