@@ -28,6 +28,14 @@ class PatchGeom(C.Structure):
     _fields_ = [(n, i32) for n in ("B", "M", "D", "H", "W", "dp", "hp", "wp", "cls_rows")]
 
 
+class GradSegment(C.Structure):
+    """struct xvit_grad_segment (include/xvit.h)."""
+    _fields_ = [("src", vp), ("dst_offset", i64), ("n", i64)]
+
+
+GRAD_PACK_MAX_SEGMENTS = 32   # XVIT_GRAD_PACK_MAX_SEGMENTS
+
+
 # name -> argtypes; every function returns int except the two noted below
 SIGNATURES = {
     "xvit_gemm": [C.POINTER(GemmArgs), vp],
@@ -66,6 +74,8 @@ SIGNATURES = {
     "xvit_set_option": [C.c_char_p, i32],
     "xvit_set_dropout_epoch": [C.c_void_p],
     "xvit_adam_step": [vp, vp, i32, f32, f32, f32, f32, f32, i32, f32, vp],
+    "xvit_grad_pack_bf16": [C.POINTER(GradSegment), i32, vp, i64, f32, vp],
+    "xvit_grad_unpack_bf16": [vp, vp, i64, f32, vp],
 }
 EXPORTS = sorted(list(SIGNATURES) + ["xvit_version", "xvit_last_error_string", "xvit_gemm_workspace_bytes", "xvit_linear_f32_workspace_bytes",
                                     "xvit_colsum_workspace_bytes", "xvit_layernorm_bwd_workspace_bytes", "xvit_patch_embed_wgrad_workspace_bytes", "xvit_attn_fp8_workspace_bytes",

@@ -22,24 +22,58 @@ whole step, collectives included, and they overlap the rest of the captured back
 
 The class is device-agnostic (CPU tensors + gloo skip the stream logic), which is what the
 world_size-2 tests in tests/test_ddp_gloo.py run.
+
+Wire format (`comm_dtype`, default from XVIT_GRAD_COMM = fp32 | bf16; fp32 when unset).  fp32 is the path described above.  bf16
+halves the bytes on the links: each bucket also owns a bf16 buffer of the same slot layout (bucket boundaries are planned in fp32
+bytes either way, so they are identical in both formats).  On the comm stream, behind the same events, one pack launch per bucket
+(xvit_grad_pack_bf16: 32 segments per launch) reads every gradient of the bucket (its fp32 view, or the separate 1-D p.grad) and writes
+bf16(g * scale) with zeroed slot padding; the all-reduce runs on the bf16 buffer; a second side stream (unpack_stream) waits for the
+collective and xvit_grad_unpack_bf16 writes the result back into the fp32 bucket; finish() waits for that unpack.  p.grad are the fp32
+bucket views exactly as in fp32 mode.
+Numerics: each rank's gradient is rounded to bf16 once (relative error <= 2^-8, the unit round-off of an 8-bit significand); RCCL
+then sums in bf16, which can add up to W - 1 further roundings on a ring of W ranks.  This is the contract of DDP's
+bf16_compress_hook.  On the CPU (gloo, no AVG) the same steps run as torch casts: pre-scale by 1/world and round in the pack, SUM,
+widen in finish().
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.distributed as dist
 
+from . import ops
+
+_COMM_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def comm_dtype_from(comm_dtype=None):
+    """The reducer's wire dtype: torch.float32 or torch.bfloat16 as given, or (None) from XVIT_GRAD_COMM (fp32, the default, or bf16)."""
+    if comm_dtype is None:
+        env = os.environ.get("XVIT_GRAD_COMM", "") or "fp32"
+        if env not in _COMM_DTYPES:
+            raise ValueError(f"XVIT_GRAD_COMM={env!r}: expected one of {sorted(_COMM_DTYPES)}")
+        return _COMM_DTYPES[env]
+    if isinstance(comm_dtype, torch.dtype) and comm_dtype in (torch.float32, torch.bfloat16):
+        return comm_dtype
+    raise ValueError(f"comm_dtype={comm_dtype!r}: expected None, torch.float32 or torch.bfloat16")
+
 
 class _Bucket:
-    __slots__ = ("params", "flat", "views", "pending", "work", "launched", "events")
+    __slots__ = ("params", "flat", "views", "offsets", "wire", "done", "pending", "work", "launched", "events")
 
-    def __init__(self, params, device):
+    def __init__(self, params, device, comm_dtype=torch.float32):
         self.params = params
         slot = lambda p: (p.numel() + 63) // 64 * 64          # noqa: E731 — every view starts on a 256-byte boundary: kernels write into them (16-byte stores)
         self.flat = torch.zeros(sum(slot(p) for p in params), dtype=torch.float32, device=device)
-        self.views, o = [], 0
+        self.views, self.offsets, o = [], [], 0
         for p in params:
             self.views.append(self.flat[o:o + p.numel()].view_as(p))
+            self.offsets.append(o)
             o += slot(p)
+        # bf16 wire format: the communication buffer (same slot layout) and, on the GPU, the event of its unpack (unpack_stream)
+        self.wire = torch.zeros(self.flat.numel(), dtype=comm_dtype, device=device) if comm_dtype != torch.float32 else None
+        self.done = torch.cuda.Event() if self.wire is not None and device.type == "cuda" else None
         self.pending, self.work, self.launched = len(params), None, False
         self.events = {}      # stream id -> (stream, event): the latest gradient write of this bucket on each stream
 
@@ -62,7 +96,12 @@ def plan_buckets(params, bucket_bytes: int):
 
 
 class BucketedGradReducer:
-    def __init__(self, params, process_group=None, bucket_bytes: int = 32 << 20, broadcast: bool = True):
+    """comm_dtype: the wire format of the all-reduces, torch.float32 or torch.bfloat16; None reads XVIT_GRAD_COMM (module docstring).
+    bf16: each rank's gradient is rounded to bf16 once (relative error <= 2^-8) and RCCL sums in bf16, up to W - 1 further roundings
+    on a ring of W ranks — the contract of DDP's bf16_compress_hook.  p.grad, the optimizer and the gradient sink see fp32 either way."""
+
+    def __init__(self, params, process_group=None, bucket_bytes: int = 32 << 20, broadcast: bool = True, comm_dtype=None):
+        self.comm_dtype = comm_dtype_from(comm_dtype)
         self.group = process_group
         self.world = dist.get_world_size(process_group)
         params = [p for p in params if p.requires_grad]
@@ -71,10 +110,11 @@ class BucketedGradReducer:
         self.device = params[0].device
         self.cuda = self.device.type == "cuda"
         self.comm_stream = torch.cuda.Stream(device=self.device) if self.cuda else None
+        self.unpack_stream = torch.cuda.Stream(device=self.device) if self.cuda and self.comm_dtype != torch.float32 else None
         if broadcast:  # replicas start identical (DDP does the same at wrap time)
             for p in params:
                 dist.broadcast(p.data, src=dist.get_global_rank(process_group, 0) if process_group is not None else 0, group=process_group)
-        self.buckets = [_Bucket(ps, self.device) for ps in plan_buckets(params, bucket_bytes)]
+        self.buckets = [_Bucket(ps, self.device, self.comm_dtype) for ps in plan_buckets(params, bucket_bytes)]
         self._bucket_of = {id(p): b for b in self.buckets for p in b.params}
         self._view_of = {id(p): v for b in self.buckets for p, v in zip(b.params, b.views)}
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in params]
@@ -129,6 +169,13 @@ class BucketedGradReducer:
             handles.append(a.register_hook(hook))
         return handles
 
+    def drain(self):
+        """Block until the process group's watchdog has retired every collective issued so far (RCCL).  It polls their events from its
+        own thread, and an event query while a graph is being captured aborts the process (hipErrorStreamCaptureUnsupported): the
+        captured step (xvit.graph.GraphedStep) calls this between its eager warm-up and the capture.  gloo keeps no such list."""
+        if self.cuda and dist.get_backend(self.group) == "nccl":
+            (self.group if self.group is not None else dist.group.WORLD)._wait_for_pending_works()
+
     def set_graph_mode(self, on: bool):
         """While True the gradients are taken to sit in the bucket views already (attach_leaves put them there) and p.grad is not read."""
         self._graph_mode = bool(on)
@@ -152,11 +199,27 @@ class BucketedGradReducer:
                 if not torch.cuda.is_current_stream_capturing():
                     for g in grads:                    # allocated on a branch stream, last read here
                         g.record_stream(self.comm_stream)
-                self._pack(b, grads, None if self._avg else scale)
-                b.work = dist.all_reduce(b.flat, op=dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM, group=self.group, async_op=True)
-        else:
+                op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
+                if b.wire is None:
+                    self._pack(b, grads, None if self._avg else scale)
+                    b.work = dist.all_reduce(b.flat, op=op, group=self.group, async_op=True)
+                else:
+                    self._pack_wire(b, grads, 1.0 if self._avg else scale)
+                    b.work = dist.all_reduce(b.wire, op=op, group=self.group, async_op=True)
+            if b.wire is not None:
+                # the unpack waits for the collective on a stream of its own: the comm stream cannot wait on the collective's stream,
+                # which waits on the comm stream: with two forked streams waiting on each other the capture crashed
+                with torch.cuda.stream(self.unpack_stream):
+                    b.work.wait()
+                    ops.grad_unpack_bf16(b.wire, b.flat)
+                    b.done.record(self.unpack_stream)
+        elif b.wire is None:
             self._pack(b, grads, scale)
             b.work = dist.all_reduce(b.flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+        else:
+            wire = [b.wire[o:o + g.numel()].view_as(g) for g, o in zip(grads, b.offsets)]
+            torch._foreach_copy_(wire, torch._foreach_mul(grads, scale))    # bf16(g / world): the same rounding as the GPU pack
+            b.work = dist.all_reduce(b.wire, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     @staticmethod
     def _pack(b, grads, scale):
@@ -169,6 +232,19 @@ class BucketedGradReducer:
         if scale is not None:
             b.flat.mul_(scale)
 
+    @staticmethod
+    def _pack_wire(b, grads, scale):
+        """bf16 wire buffer <- bf16(g * scale) for every gradient of the bucket, slot padding zeroed, in one launch per 32 gradients.
+        The kernel reads a gradient where it is (its bucket view, or a separate contiguous, 16-byte aligned fp32 p.grad); any other
+        layout is first copied into its view."""
+        segs = []
+        for g, v, o in zip(grads, b.views, b.offsets):
+            if g.data_ptr() != v.data_ptr() and not (g.dtype == torch.float32 and g.is_contiguous() and g.data_ptr() % 16 == 0):
+                v.copy_(g)
+                g = v
+            segs.append((g, o))
+        ops.grad_pack_bf16(segs, b.wire, scale)
+
     # ---- after backward ------------------------------------------------------------------------
     def finish(self):
         """Wait (stream-side on GPU) for every bucket and point p.grad at the reduced values."""
@@ -177,7 +253,12 @@ class BucketedGradReducer:
                 self.exposed_launches += 1
                 self._launch(b)
         for b in self.buckets:
-            b.work.wait()  # NCCL/RCCL: the current stream waits; gloo: the host waits
+            if b.done is not None:     # bf16 on the GPU: the current stream waits for the unpack behind the collective
+                torch.cuda.current_stream(self.device).wait_event(b.done)
+            else:
+                b.work.wait()  # NCCL/RCCL: the current stream waits; gloo: the host waits
+                if b.wire is not None:
+                    b.flat.copy_(b.wire)
             for p, v in zip(b.params, b.views):
                 p.grad = v
             b.pending, b.work, b.launched = len(b.params), None, False

@@ -83,6 +83,8 @@ class GraphedStep:
                     self._eager()
             torch.cuda.current_stream(img.device).wait_stream(side)
             torch.cuda.synchronize(img.device)
+            if reducer is not None:
+                reducer.drain()                    # no warm-up collective may still be polled by the RCCL watchdog during the capture
             self.graph = torch.cuda.CUDAGraph()
             for p in self.params:
                 p.grad = None                      # gradients are (re)allocated from the graph's private pool

@@ -532,6 +532,30 @@ def cast_bf16(src, out=None):
     return out
 
 
+def grad_pack_bf16(segments, dst, scale=1.0):
+    """dst[off : off + n] = bf16(src * scale) for each (src, off) in `segments`, zeros over the rest of each 64-element slot
+    (xvit_grad_pack_bf16): the bf16 wire buffer of a reducer bucket.  src: contiguous fp32, 16-byte aligned; off: a multiple of 64;
+    dst: contiguous bf16.  One launch per XVIT_GRAD_PACK_MAX_SEGMENTS segments."""
+    assert dst.dtype == torch.bfloat16 and dst.is_contiguous()
+    lib, base, m = _lib.load(), _ptr(dst), _lib.GRAD_PACK_MAX_SEGMENTS
+    for i in range(0, len(segments), m):
+        part = segments[i:i + m]
+        table = (_lib.GradSegment * len(part))()
+        for e, (src, off) in zip(table, part):
+            assert src.dtype == torch.float32 and src.is_contiguous()
+            e.src, e.dst_offset, e.n = _ptr(src), off, src.numel()
+        work = sum(src.numel() for src, _ in part) * 6.0
+        _run("grad_pack_bf16", work, "byte", lambda: lib.xvit_grad_pack_bf16(table, len(part), base, dst.numel(), float(scale), _stream()), "xvit_grad_pack_bf16")
+    return dst
+
+
+def grad_unpack_bf16(src, dst, scale=1.0):
+    """dst = float(src) * scale (xvit_grad_unpack_bf16): a reduced bf16 wire buffer back into its fp32 bucket; contiguous, same numel."""
+    assert src.dtype == torch.bfloat16 and dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
+    _run("grad_unpack_bf16", src.numel() * 6.0, "byte", lambda: _lib.load().xvit_grad_unpack_bf16(_ptr(src), _ptr(dst), src.numel(), float(scale), _stream()), "xvit_grad_unpack_bf16")
+    return dst
+
+
 def add_cast(a, b):
     """-> (a + b fp32, its bf16 copy) in one pass (xvit_add_cast_f32_bf16); contiguous fp32 tensors of one shape, numel % 8 == 0."""
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape and a.is_contiguous() and b.is_contiguous()

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 303 /* 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 304 /* 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1 };
@@ -331,6 +331,27 @@ int xvit_cu_trace(uint32_t* out, int nblocks, int linger_us, xvit_stream_t strea
 #define XVIT_ADAM_CHUNK 16384
 int xvit_adam_step(const void* table_dev, const void* chunks_dev, int n_chunks, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, float grad_scale, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * bf16 wire format of the data-parallel gradient reducer (xvit/ddp.py, comm_dtype=torch.bfloat16; the counterpart of DDP's
+ * bf16_compress_hook).  A bucket is a flat fp32 buffer of 64-element slots, one per parameter; its bf16 communication buffer has
+ * the same slot layout.
+ *
+ * pack: for each segment, dst_bf16[dst_offset + i] = bf16(src[i] * scale) for i < n (round to nearest even, bit-identical to
+ * (x * scale).to(torch.bfloat16); NaN stays NaN) and 0 for n <= i < round_up(n, 64), the slot padding.  `segments` is a HOST
+ * array, read during the call and passed to the kernel by value in its arguments: no device table, nothing to copy, so the launch
+ * can be captured into a graph.  At most XVIT_GRAD_PACK_MAX_SEGMENTS segments per call (a larger bucket takes several calls).
+ * src 16-byte aligned, dst_offset a multiple of 64, every slot inside [0, dst_n), dst_bf16 16-byte aligned.
+ * unpack: dst[i] = float(src_bf16[i]) * scale, i < n; both pointers 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_GRAD_PACK_MAX_SEGMENTS 32
+typedef struct xvit_grad_segment {
+  const float* src;
+  int64_t dst_offset; /* elements */
+  int64_t n;
+} xvit_grad_segment;
+int xvit_grad_pack_bf16(const xvit_grad_segment* segments, int n_segments, void* dst_bf16, int64_t dst_n, float scale, xvit_stream_t stream);
+int xvit_grad_unpack_bf16(const void* src_bf16, float* dst, int64_t n, float scale, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Head tail (model_cross.py:205-211): logits = mean_m logits_m;  loss = CE(logits, labels,
