@@ -2,7 +2,7 @@
 """Headline benchmark: 3-D patch-tokens/sec, forward + backward, 2-modality 128^3 p16 cross-attention
 ViT (BASELINE.json configs[1]: d=768, 12 heads, mlp 3072, 2x2 blocks, N=513) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = zero-grad, per-step bf16 re-cast of the fp32 master weights (what an optimizer step
@@ -11,10 +11,13 @@ all-reduce over RCCL (overlapped with backward on a side stream).  Optimizer ste
 loading are excluded (metric definition).  Inputs are synthetic and already resident
 in HBM; weak scaling (fixed per-GPU batch).  Rank 0 prints ONE JSON line.
 
-Also reported in that line:
+A plain run does only what the headline needs: set up, warm up, time the steps, dump the outputs
+if asked, print the line.  With --full the line also reports, each measured after the timed region:
   roofline      the kernel family with the largest share of step time, priced live with HIP events
-                on the launch stream (extra profiled steps after the timed region)
+                on the launch stream (extra profiled steps)
   kernels       the same pricing for every kernel family (MFMA TFLOP/s or HBM GB/s)
+  small_batch   the step at the reference's batch 8 and 32, eager and as one HIP-graph replay
+                (a child process; N=1 only)
   cpu_baseline  the CPU oracle (oracle/ref_cpu.py, a port of the reference path) timed on this
                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only)
 """
@@ -174,7 +177,7 @@ def dry_run(args, rank, world):
     dist.all_gather_object(seen, {"rank": rank, "local_rank": int(os.environ.get("LOCAL_RANK", "0")), "world": world, "pid": os.getpid()})
     dist.barrier()
     if rank == 0:
-        emit({"dryrun": True, "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ranks": seen})
+        emit({"dryrun": True, "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full, "ranks": seen})
     dist.destroy_process_group()
 
 
@@ -295,13 +298,15 @@ def main():
     ap.add_argument("--batch", type=int, default=126, help="per-GPU batch of volume pairs.  Throughput rises with batch until ~126 (42: 2.79 M, 84: 2.99 M, 126: 3.03 M, "
                     "252: 3.06 M tokens/s; 18.7 GB of the 288 GB HBM at 126); 126*513 rows = 253 row tiles of 256 -> 759 / 1518 / 2277 / 3036 tiles per GEMM "
                     "= 2.96 .. 11.9 rounds of 256 CUs, so the last round of every launch is nearly full")
-    ap.add_argument("--profile-steps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need, after the timed region: per-kernel "
+                    "pricing (roofline, kernels), the small-batch points and the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=2, help="--full: steps priced per kernel")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-clock-probe", action="store_true", help="(accepted for old command lines; the rocm-smi clock field is gone: the in-kernel clock of the "
                     "GEMM / attention loops is measured by the diagnostic builds under tools/ and kept in profiles/)")
     ap.add_argument("--small-batch-only", action="store_true", help="internal: print the small-batch points as one JSON line and exit (run by the parent bench in a child process)")
-    ap.add_argument("--no-small-batch", action="store_true", help="skip the extra B=8 / B=32 points (eager and HIP-graph replay)")
-    ap.add_argument("--detail", action="store_true", help="per-shape GEMM table on stderr (diagnostic)")
+    ap.add_argument("--no-small-batch", action="store_true", help="--full: skip the extra B=8 / B=32 points (eager and HIP-graph replay)")
+    ap.add_argument("--detail", action="store_true", help="--full: per-shape GEMM table on stderr (diagnostic)")
     ap.add_argument("--graph", action="store_true", help="replay the step as one captured HIP graph (xvit.graph.GraphedStep); "
                     "pays off when the step is host-bound, i.e. at small per-GPU batch")
     ap.add_argument("--single-stream", action="store_true", help="run the modality branches on one stream (used for the rocprof "
@@ -311,6 +316,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.detail and not args.full:
+        ap.error("--detail prints the per-kernel pricing, which only a --full run does")
 
     if args.single_stream:
         os.environ["XVIT_STREAMS"] = "0"
@@ -441,11 +448,11 @@ def main():
                              "exposed_ms_note": "per step, rank 0: time reducer.finish() holds the compute stream waiting for the tail of the bucket all-reduces "
                                                 "(eager launches; with --graph the collectives are nodes of the replayed graph and are not separable)"}
 
-    # ---- per-kernel pricing with HIP events on the launch stream (rank 0) --------------------
+    # ---- --full: per-kernel pricing with HIP events on the launch stream (rank 0) -------------
     if args.graph:
         step = eager_step                             # per-kernel pricing needs individual launches
     rec = None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         # kernels are priced one at a time: the two modality streams are merged for these extra steps, otherwise
         # concurrently running kernels stretch each other's event brackets (the timed region above keeps them).
         # EVERY rank runs the same extra steps (their backward launches the reducer's collectives from its hooks, so a
@@ -508,12 +515,12 @@ def main():
         if "attn_fwd" in kernels:
             out["attention_mfma_frac"] = {"fwd": kernels["attn_fwd"]["frac"], "bwd": kernels.get("attn_bwd", {}).get("frac")}
 
-    # ---- the reference's own batch sizes (main_mist.py:206 trains at 8 per GPU), next to the headline batch -------------
+    # ---- --full: the reference's own batch sizes (main_mist.py:206 trains at 8 per GPU), next to the headline batch -----
     # Measured in a FRESH CHILD PROCESS after the headline: the points capture HIP graphs, and a native crash inside a capture
     # (seen in round 2) must not cost the line above.  The child is a new `python bench.py --small-batch-only`, never a re-exec.
-    if world == 1 and not use_dist and not args.no_small_batch:
+    if args.full and world == 1 and not use_dist and not args.no_small_batch:
         out["small_batch"] = small_batch_child()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg)
     if rank == 0:
         emit(out)

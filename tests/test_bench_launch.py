@@ -28,6 +28,13 @@ def test_bare_gpus_2_launches_two_ranks():
     assert all(r["world"] == 2 for r in ranks) and ranks[0]["pid"] != ranks[1]["pid"]
 
 
+def test_full_reaches_the_ranks():
+    # a plain run unless --full is given
+    assert _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1")["full"] is False
+    out = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
+    assert out["full"] is True and out["n_gpus"] == 2
+
+
 def test_under_torch_distributed_run_env_no_second_launch():
     # the driver's form: RANK / WORLD_SIZE already set -> main() must use them, not spawn again
     out = _run({"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29577"}, "--gpus", "1")
@@ -39,3 +46,8 @@ def test_child_failure_propagates():
     env.update(XVIT_BENCH_DRYRUN="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-such-flag"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
+
+
+def test_detail_without_full_is_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr

@@ -7,7 +7,7 @@ S=${1:-gpurun_out/prof}
 R=$PWD
 mkdir -p $S && S=$(cd $S && pwd)
 export TMPDIR=/tmp
-python3 bench.py > $S/bench_default.json 2> $S/bench_default.err || exit 1
+python3 bench.py --full > $S/bench_default.json 2> $S/bench_default.err || exit 1
 cd /tmp
 Q="--no-cpu-baseline --profile-steps 0 --no-small-batch"
 rocprofv3 --kernel-trace --stats --output-format csv -d $S/stats -- python3 $R/bench.py --steps 10 --warmup 3 $Q --single-stream > $S/stats.log 2>&1 || exit 2

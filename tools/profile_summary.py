@@ -57,7 +57,7 @@ def main():
     L = []
     rf, cb = bench["roofline"], bench["cpu_baseline"]
     L.append(f"# Profile {tag} (1x MI355X, {bench['config']['workload']}, per-GPU batch {bench['config']['per_gpu_batch']})\n")
-    L.append(f"Headline (`python bench.py`, `{tag}_bench.json`): **{bench['value']:.0f} {bench['unit']}**, {bench['ms_per_step']} ms/step, "
+    L.append(f"Headline (`python bench.py --full`, `{tag}_bench.json`): **{bench['value']:.0f} {bench['unit']}**, {bench['ms_per_step']} ms/step, "
              f"{bench['model_tflops_per_gpu']} TFLOP/s of model FLOPs ({100 * bench['mfma_frac_of_peak_step']:.1f} % of the 2516 TFLOP/s bf16 MFMA peak over the whole step); "
              f"CPU oracle {cb['value']} {cb['unit']} on {cb['cores']} host cores ({cb['sample']}).\n")
     L.append(f"`roofline`: `{rf['kernel']}` — {rf['achieved']} {rf['unit']} algorithmic = {100 * rf['frac']:.1f} % of peak, average launch {rf['avg_launch_us']} us by HIP events.\n")
