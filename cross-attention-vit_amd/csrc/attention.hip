@@ -1028,6 +1028,110 @@ __global__ __launch_bounds__(256) void attn_cls_bwd_merge_kernel(const bf16* __r
   dv[off0 + lane] = f2bf(fmaf(p00, g0, sv));
 }
 
+// ------------------------------------------------------------------------------------------
+// attention rollout step (xvit_attn_rollout_step):  r_out[b, n] = r_in[b, n] / 2 + 1 / (2 H) sum_h sum_m r_in[b, m] P_h[b, m, n]
+// with P_h recomputed from q, k and the forward's lse (P = exp2(s c - lse log2e)), never stored.  One workgroup per (b, 64-key
+// tile); the key is on the MFMA lane as in the dK/dV kernel (S = Q K^T: a lane's accumulators hold P[m, n] of its key n for 32
+// queries m), so the r-weighted sum over the queries is lane-local fp32 FMAs and one exchange of the lane halves.  The workgroup's
+// (head, 64-query tile) items are cut into RO_WAVES contiguous ranges, head-major: a wave loads its K fragments again only where
+// its range enters a new head, and streams its Q tiles straight into registers (one tile ahead).  The waves' partial sums meet in
+// LDS and are added in wave order: a fixed summation order, no atomics, bit-reproducible.
+// ------------------------------------------------------------------------------------------
+constexpr int RO_WAVES = 8;
+
+__device__ __forceinline__ float buffer_f32(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {   // 0 past the resource's end
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
+}
+
+__global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k, int64_t sb, int64_t sn,
+                                                                     const float* __restrict__ lse, const float* __restrict__ r_in, float* __restrict__ r_out,
+                                                                     int H, int N, float scale) {
+  __shared__ __attribute__((aligned(16))) float rows[RO_WAVES][2][64];   // per wave: -lse log2e | r of the current item's 64 queries
+  __shared__ float part[RO_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6), h = lane >> 5;
+  const BlockCoord bc = xcd_block_coord();   // grid (key tiles, 1, B): the key tiles of one sample share an XCD and its L2
+  const int b = bc.b, key0 = bc.x * 64;
+  const int nqt = (N + 63) / 64;
+  const int64_t items = (int64_t)H * nqt;
+  const int lo = (int)(items * wave / RO_WAVES), hi = (int)(items * (wave + 1) / RO_WAVES);
+  const float c = scale * LOG2E;
+  const __amdgpu_buffer_rsrc_t rr = make_rsrc(r_in + (int64_t)b * N, clamp_bytes((int64_t)N * 4));
+
+  // item it = (head, query tile): Q rows as A operands (query on the accumulator rows; rows past N read 0), and one lse / r value per lane
+  // (lane = query; past N both read 0: P = 1 there, weighted by r = 0)
+  bf16x8 qn[2][4];
+  float nl_n = 0.f, r_n = 0.f;
+  auto fetch = [&](int it) {
+    const int head = it / nqt, m0 = (it - head * nqt) * 64;
+    const int64_t off = (int64_t)b * sb + head * DH;
+    load_lane_operand(qn[0], q + off, sn, m0, N, lane);
+    load_lane_operand(qn[1], q + off, sn, m0 + 32, N, lane);
+    const __amdgpu_buffer_rsrc_t rl = make_rsrc(lse + ((int64_t)b * H + head) * N, clamp_bytes((int64_t)N * 4));
+    nl_n = buffer_f32(rl, (uint32_t)(m0 + lane) * 4);
+    r_n = buffer_f32(rr, (uint32_t)(m0 + lane) * 4);
+  };
+  if (lo < hi) fetch(lo);
+
+  f32x2 acc[2] = {{0.f, 0.f}, {0.f, 0.f}};   // per 32-key block: this lane half's rows, even / odd accumulator registers
+  bf16x8 kf[2][4];
+  int kf_head = -1;
+  const f32x2 c2 = {c, c};
+  for (int it = lo; it < hi; ++it) {
+    bf16x8 qf[2][4];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) qf[qb][ks] = qn[qb][ks];
+    __builtin_amdgcn_wave_barrier();
+    rows[wave][0][lane] = -nl_n * LOG2E;   // staged before the next item's loads overwrite nl_n / r_n
+    rows[wave][1][lane] = r_n;
+    __builtin_amdgcn_wave_barrier();   // the wave's own LDS rows: its LDS operations complete in order
+    const int head = it / nqt;
+    if (head != kf_head) {   // wave-uniform: the range enters a new head.  Issued BEFORE the next item's loads, so that waiting for
+      const int64_t off = (int64_t)b * sb + head * DH;   // these leaves those in flight (the counter retires in order)
+      load_lane_operand(kf[0], k + off, sn, key0, N, lane);
+      load_lane_operand(kf[1], k + off, sn, key0 + 32, N, lane);
+      kf_head = head;
+    }
+    fetch(min(it + 1, hi - 1));   // unconditional (the last item loads itself again): one path, so hipcc's counted waits for K stay exact
+    __builtin_amdgcn_sched_barrier(0);   // keep the next item's loads in front of this item's math (the scheduler sinks them otherwise)
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      f32x16 s[2];
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[qb][ks], kf[kb][ks], ks == 0 ? ZERO16 : s[kb], 0, 0, 0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {   // accumulator registers 4g .. 4g + 3 hold the queries 32 qb + 8 g + 4 h + (0 .. 3)
+        const f32x4 nl4 = *(const f32x4*)&rows[wave][0][qb * 32 + 8 * g + 4 * h];
+        const f32x4 r4 = *(const f32x4*)&rows[wave][1][qb * 32 + 8 * g + 4 * h];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int e = 0; e < 4; e += 2) {
+            const f32x2 t = f32x2{s[kb][4 * g + e], s[kb][4 * g + e + 1]} * c2 + f32x2{nl4[e], nl4[e + 1]};
+            const f32x2 p = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+            acc[kb] += f32x2{r4[e], r4[e + 1]} * p;
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb) {
+    const float tot = half_sum(acc[kb].x + acc[kb].y);
+    if (h == 0) part[wave][kb * 32 + lane] = tot;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    float sum = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < RO_WAVES; ++w) sum += part[w][lane];
+    const int n = key0 + lane;
+    if (n < N) r_out[(int64_t)b * N + n] = 0.5f * r_in[(int64_t)b * N + n] + (0.5f / (float)H) * sum;
+  }
+}
+
 }  // namespace xvit
 
 using namespace xvit;
@@ -1144,4 +1248,15 @@ extern "C" int xvit_attn_bwd(const void* q, const void* k, const void* v, int64_
   else if (dropout_p > 0.f) launch_attn_bwd<true, false>(q, k, v, sb, sn, o, d_o, osb, osn, lse, workspace, dq, dk, dv, B, H, N, scale, da, s);
   else launch_attn_bwd<false, false>(q, k, v, sb, sn, o, d_o, osb, osn, lse, workspace, dq, dk, dv, B, H, N, scale, da, s);
   return check_launch("xvit_attn_bwd");
+}
+
+extern "C" int xvit_attn_rollout_step(const void* q, const void* k, int64_t sb, int64_t sn, const float* lse, const float* r_in, float* r_out,
+                                      int B, int H, int N, int dh, float scale, xvit_stream_t stream) {
+  XVIT_REQUIRE(q && k && lse && r_in && r_out, "xvit_attn_rollout_step: null pointer");
+  if (int e = attn_check("xvit_attn_rollout_step", B, H, N, dh, sb, sn, sb, sn)) return e;
+  const uintptr_t a = (uintptr_t)r_in, o = (uintptr_t)r_out, bytes = (uintptr_t)B * (uintptr_t)N * 4;
+  XVIT_REQUIRE(a + bytes <= o || o + bytes <= a, "xvit_attn_rollout_step: r_in and r_out must not alias");
+  hipLaunchKernelGGL(attn_rollout_kernel, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k, sb, sn,
+                     lse, r_in, r_out, H, N, scale);
+  return check_launch("xvit_attn_rollout_step");
 }

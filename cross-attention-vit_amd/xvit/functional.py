@@ -9,6 +9,7 @@ are re-cast whenever a parameter's version changes (i.e. after every optimizer s
 """
 from __future__ import annotations
 
+import contextvars
 import os
 import weakref
 
@@ -409,6 +410,12 @@ def _xattn_lowrank_ok(H, d, rows):
     return XATTN_FORM == "lowrank" or rows >= XATTN_AUTO_ROWS or torch.cuda.is_current_stream_capturing()
 
 
+# Attention-map recorder (xvit.interpret.attention_maps): None — the default — everywhere else.  When set, the self-attention blocks
+# and the fusions hand it what their forward computed (rec.self_block / rec.fusion, keyed by their first LayerNorm weight); the
+# forward's own kernels and launches stay the same either way.
+ATTN_RECORDER: "contextvars.ContextVar" = contextvars.ContextVar("xvit_attn_recorder", default=None)
+
+
 def _attn_fwd(qkv, B, N, H, scale, p=0.0, seed=0):
     """Forward attention of the all-token blocks.  XVIT_ATTN_FP8=1 (opt-in, SURVEY.md 8 / configs[4]) runs QK^T and P.V on the
     MX-fp8 matrix instruction where the kernel applies (d_h = 64, no probability dropout): ~5e-2 output error instead of 2e-3
@@ -426,6 +433,9 @@ def block_forward(x, B, N, H, eps, scale, ln1w, ln1b, wqkv_s, bqkv, wo_s, bo, ln
     h1, mu1, rs1 = ops.layernorm_fwd(x, ln1w, ln1b, eps)
     qkv = _linear(h1, wqkv_s, bias=bqkv)
     o, lse = _attn_fwd(qkv, B, N, H, scale, p_attn, seed_attn)       # model.py:169: dropout on the probabilities
+    rec = ATTN_RECORDER.get()
+    if rec is not None:
+        rec.self_block(ln1w, qkv, lse, B, N, H, scale)
     x1 = _linear(o, wo_s, bias=bo, residual=x, out_dtype=torch.float32, dropout=_dp(p_out, seeds[0]))
     h2, mu2, rs2 = ops.layernorm_fwd(x1, ln2w, ln2b, eps)
     z = torch.empty(x.shape[0], w1_s.shape[0], dtype=torch.bfloat16, device=x.device)
@@ -575,6 +585,12 @@ def cross_forward(xi, xj, B, N, H, eps, ln1w, ln1b, wq, bq, wkv_s, bkv, wp, bp, 
         kv = _linear(hn, wkv_s, bias=bkv)
         # dropout sites (model_cross.py:97,101,25,27): probabilities, proj output, after GELU, FFN output
         oc, pr, ocf = ops.cls_xattn_fwd(qf, kv, B, N, H, scale, dropout=(p, seeds[0]), want_f32=True)
+    rec = ATTN_RECORDER.get()
+    if rec is not None:   # the CLS-query probabilities: p [B, H, N], or the low-rank form's weights e [B, N, 16] and 1 / sum e
+        if lowrank:
+            rec.fusion(ln1w, B, N, H, e=e, rz=rz)
+        else:
+            rec.fusion(ln1w, B, N, H, p=pr)
     y, _, _ = ops.linear_f32(ocf, wp, bp, residual=cls_in, dropout=_dp(p, seeds[1]))
     h2f, h2, mu2, rs2 = ops.layernorm_fwd_f32(y, ln2w, ln2b, eps)
     af, a, z = ops.linear_f32(h2f, w1, b1, act=ops.ACT_GELU, want_z=True, want_bf16=True, dropout=_dp(p, seeds[2]))

@@ -278,6 +278,21 @@ def attn_fwd(qkv, B, N, H, scale, dropout=(0.0, 0)):
     return o, lse
 
 
+def attn_rollout_step(qkv, lse, r, B, N, H, scale):
+    """One attention-rollout step through a self-attention block (xvit_attn_rollout_step): qkv bf16 [B*N, 3d] and lse fp32 [B, H, N] of
+    the block's forward, r fp32 [B, N] -> r_out fp32 [B, N] = r / 2 + (r . mean_h P_h) / 2.  P is recomputed from q, k and lse, never stored."""
+    d = qkv.shape[1] // 3
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, N)
+    assert r.dtype == torch.float32 and r.is_contiguous() and tuple(r.shape) == (B, N)
+    out = torch.empty_like(r)
+    ld = _rows2d(qkv)
+    p = _ptr(qkv)
+    _run("attn_rollout", 2.0 * B * H * N * N * (d // H), "flop",
+         lambda: _lib.load().xvit_attn_rollout_step(p, p + 2 * d, N * ld, ld, _ptr(lse), _ptr(r), _ptr(out), B, H, N, d // H, scale, _stream()),
+         "xvit_attn_rollout_step")
+    return out
+
+
 def attn_fwd_fp8(qkv, B, N, H, scale):
     """MX-fp8 forward attention (xvit_attn_fwd_fp8): qkv bf16 [B*N, 3d] -> (o bf16 [B*N, d], lse fp32 [B, H, N]); opt-in."""
     d = qkv.shape[1] // 3
