@@ -1036,6 +1036,10 @@ __global__ __launch_bounds__(256) void attn_cls_bwd_merge_kernel(const bf16* __r
 // (head, 64-query tile) items are cut into RO_WAVES contiguous ranges, head-major: a wave loads its K fragments again only where
 // its range enters a new head, and streams its Q tiles straight into registers (one tile ahead).  The waves' partial sums meet in
 // LDS and are added in wave order: a fixed summation order, no atomics, bit-reproducible.
+//
+// REL (xvit_attn_relevance_step, Chefer et al. 2021):  r_out[b, n] = r_in[b, n] + 1 / H sum_h sum_m r_in[b, m] max(0, P_h dP_h)[b, m, n]
+// with dP_h = dO_h V_h^T recomputed the same way: a second 32x32x16 product per (query block, key block), dO fragments streamed like
+// Q (one item ahead), V fragments loaded with K.  The rollout instantiation's code is the REL = false branch of every `if constexpr`.
 // ------------------------------------------------------------------------------------------
 constexpr int RO_WAVES = 8;
 
@@ -1043,8 +1047,11 @@ __device__ __forceinline__ float buffer_f32(__amdgpu_buffer_rsrc_t r, uint32_t b
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
 }
 
-__global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k, int64_t sb, int64_t sn,
-                                                                     const float* __restrict__ lse, const float* __restrict__ r_in, float* __restrict__ r_out,
+template <bool REL>
+__global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
+                                                                     int64_t sb, int64_t sn, const float* __restrict__ lse,
+                                                                     const bf16* __restrict__ d_o, int64_t sbo, int64_t sno,
+                                                                     const float* __restrict__ r_in, float* __restrict__ r_out,
                                                                      int H, int N, float scale) {
   __shared__ __attribute__((aligned(16))) float rows[RO_WAVES][2][64];   // per wave: -lse log2e | r of the current item's 64 queries
   __shared__ float part[RO_WAVES][64];
@@ -1058,14 +1065,19 @@ __global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16*
   const __amdgpu_buffer_rsrc_t rr = make_rsrc(r_in + (int64_t)b * N, clamp_bytes((int64_t)N * 4));
 
   // item it = (head, query tile): Q rows as A operands (query on the accumulator rows; rows past N read 0), and one lse / r value per lane
-  // (lane = query; past N both read 0: P = 1 there, weighted by r = 0)
-  bf16x8 qn[2][4];
+  // (lane = query; past N both read 0: P = 1 there, weighted by r = 0).  REL: the dO rows likewise (past N: 0, so dP = 0 there)
+  bf16x8 qn[2][4], dn[2][4];
   float nl_n = 0.f, r_n = 0.f;
   auto fetch = [&](int it) {
     const int head = it / nqt, m0 = (it - head * nqt) * 64;
     const int64_t off = (int64_t)b * sb + head * DH;
     load_lane_operand(qn[0], q + off, sn, m0, N, lane);
     load_lane_operand(qn[1], q + off, sn, m0 + 32, N, lane);
+    if constexpr (REL) {
+      const int64_t ooff = (int64_t)b * sbo + head * DH;
+      load_lane_operand(dn[0], d_o + ooff, sno, m0, N, lane);
+      load_lane_operand(dn[1], d_o + ooff, sno, m0 + 32, N, lane);
+    }
     const __amdgpu_buffer_rsrc_t rl = make_rsrc(lse + ((int64_t)b * H + head) * N, clamp_bytes((int64_t)N * 4));
     nl_n = buffer_f32(rl, (uint32_t)(m0 + lane) * 4);
     r_n = buffer_f32(rr, (uint32_t)(m0 + lane) * 4);
@@ -1073,15 +1085,18 @@ __global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16*
   if (lo < hi) fetch(lo);
 
   f32x2 acc[2] = {{0.f, 0.f}, {0.f, 0.f}};   // per 32-key block: this lane half's rows, even / odd accumulator registers
-  bf16x8 kf[2][4];
+  bf16x8 kf[2][4], vf[2][4];
   int kf_head = -1;
   const f32x2 c2 = {c, c};
   for (int it = lo; it < hi; ++it) {
-    bf16x8 qf[2][4];
+    bf16x8 qf[2][4], df[2][4];
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) qf[qb][ks] = qn[qb][ks];
+      for (int ks = 0; ks < 4; ++ks) {
+        qf[qb][ks] = qn[qb][ks];
+        if constexpr (REL) df[qb][ks] = dn[qb][ks];
+      }
     __builtin_amdgcn_wave_barrier();
     rows[wave][0][lane] = -nl_n * LOG2E;   // staged before the next item's loads overwrite nl_n / r_n
     rows[wave][1][lane] = r_n;
@@ -1091,17 +1106,27 @@ __global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16*
       const int64_t off = (int64_t)b * sb + head * DH;   // these leaves those in flight (the counter retires in order)
       load_lane_operand(kf[0], k + off, sn, key0, N, lane);
       load_lane_operand(kf[1], k + off, sn, key0 + 32, N, lane);
+      if constexpr (REL) {
+        load_lane_operand(vf[0], v + off, sn, key0, N, lane);
+        load_lane_operand(vf[1], v + off, sn, key0 + 32, N, lane);
+      }
       kf_head = head;
     }
     fetch(min(it + 1, hi - 1));   // unconditional (the last item loads itself again): one path, so hipcc's counted waits for K stay exact
     __builtin_amdgcn_sched_barrier(0);   // keep the next item's loads in front of this item's math (the scheduler sinks them otherwise)
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
-      f32x16 s[2];
+      f32x16 s[2], dp[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[qb][ks], kf[kb][ks], ks == 0 ? ZERO16 : s[kb], 0, 0, 0);
+      if constexpr (REL) {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) dp[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df[qb][ks], vf[kb][ks], ks == 0 ? ZERO16 : dp[kb], 0, 0, 0);
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {   // accumulator registers 4g .. 4g + 3 hold the queries 32 qb + 8 g + 4 h + (0 .. 3)
         const f32x4 nl4 = *(const f32x4*)&rows[wave][0][qb * 32 + 8 * g + 4 * h];
@@ -1112,7 +1137,12 @@ __global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16*
           for (int e = 0; e < 4; e += 2) {
             const f32x2 t = f32x2{s[kb][4 * g + e], s[kb][4 * g + e + 1]} * c2 + f32x2{nl4[e], nl4[e + 1]};
             const f32x2 p = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-            acc[kb] += f32x2{r4[e], r4[e + 1]} * p;
+            if constexpr (REL) {
+              const f32x2 pd = p * f32x2{dp[kb][4 * g + e], dp[kb][4 * g + e + 1]};
+              acc[kb] += f32x2{r4[e], r4[e + 1]} * f32x2{fmaxf(pd.x, 0.f), fmaxf(pd.y, 0.f)};
+            } else {
+              acc[kb] += f32x2{r4[e], r4[e + 1]} * p;
+            }
           }
       }
     }
@@ -1128,7 +1158,12 @@ __global__ __launch_bounds__(RO_WAVES * 64) void attn_rollout_kernel(const bf16*
 #pragma unroll
     for (int w = 1; w < RO_WAVES; ++w) sum += part[w][lane];
     const int n = key0 + lane;
-    if (n < N) r_out[(int64_t)b * N + n] = 0.5f * r_in[(int64_t)b * N + n] + (0.5f / (float)H) * sum;
+    if (n < N) {
+      if constexpr (REL)   // the add is the last operation: r_in >= 0 gives sum >= 0, so r_out >= r_in exactly; sum == 0 gives r_out == r_in
+        r_out[(int64_t)b * N + n] = r_in[(int64_t)b * N + n] + (1.f / (float)H) * sum;
+      else
+        r_out[(int64_t)b * N + n] = 0.5f * r_in[(int64_t)b * N + n] + (0.5f / (float)H) * sum;
+    }
   }
 }
 
@@ -1256,7 +1291,19 @@ extern "C" int xvit_attn_rollout_step(const void* q, const void* k, int64_t sb, 
   if (int e = attn_check("xvit_attn_rollout_step", B, H, N, dh, sb, sn, sb, sn)) return e;
   const uintptr_t a = (uintptr_t)r_in, o = (uintptr_t)r_out, bytes = (uintptr_t)B * (uintptr_t)N * 4;
   XVIT_REQUIRE(a + bytes <= o || o + bytes <= a, "xvit_attn_rollout_step: r_in and r_out must not alias");
-  hipLaunchKernelGGL(attn_rollout_kernel, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k, sb, sn,
-                     lse, r_in, r_out, H, N, scale);
+  hipLaunchKernelGGL(attn_rollout_kernel<false>, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k,
+                     nullptr, sb, sn, lse, nullptr, 0, 0, r_in, r_out, H, N, scale);
   return check_launch("xvit_attn_rollout_step");
+}
+
+extern "C" int xvit_attn_relevance_step(const void* q, const void* k, const void* v, int64_t sb, int64_t sn, const float* lse, const void* d_o,
+                                        int64_t sbo, int64_t sno, const float* r_in, float* r_out, int B, int H, int N, int dh, float scale,
+                                        xvit_stream_t stream) {
+  XVIT_REQUIRE(q && k && v && lse && d_o && r_in && r_out, "xvit_attn_relevance_step: null pointer");
+  if (int e = attn_check("xvit_attn_relevance_step", B, H, N, dh, sb, sn, sbo, sno)) return e;
+  const uintptr_t a = (uintptr_t)r_in, o = (uintptr_t)r_out, bytes = (uintptr_t)B * (uintptr_t)N * 4;
+  XVIT_REQUIRE(a + bytes <= o || o + bytes <= a, "xvit_attn_relevance_step: r_in and r_out must not alias");
+  hipLaunchKernelGGL(attn_rollout_kernel<true>, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k,
+                     (const bf16*)v, sb, sn, lse, (const bf16*)d_o, sbo, sno, r_in, r_out, H, N, scale);
+  return check_launch("xvit_attn_relevance_step");
 }

@@ -47,6 +47,7 @@ SIGNATURES = {
     "xvit_attn_fwd": [vp, vp, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, i32, f32, f32, u64, vp, i64, vp],
     "xvit_attn_bwd": [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp],
     "xvit_attn_rollout_step": [vp, vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "xvit_attn_relevance_step": [vp, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, i32, i32, i32, i32, f32, vp],
     "xvit_attn_fwd_fp8": [vp, vp, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, i32, f32, vp, i64, vp],
     "xvit_cls_xattn_fwd": [vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, f32, u64, vp],
     "xvit_cls_xattn_bwd": [vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp],

@@ -410,9 +410,11 @@ def _xattn_lowrank_ok(H, d, rows):
     return XATTN_FORM == "lowrank" or rows >= XATTN_AUTO_ROWS or torch.cuda.is_current_stream_capturing()
 
 
-# Attention-map recorder (xvit.interpret.attention_maps): None — the default — everywhere else.  When set, the self-attention blocks
-# and the fusions hand it what their forward computed (rec.self_block / rec.fusion, keyed by their first LayerNorm weight); the
-# forward's own kernels and launches stay the same either way.
+# Attention-map recorder (xvit.interpret.attention_maps / relevance_maps): None — the default — everywhere else.  When set, the
+# self-attention blocks and the fusions hand it what their forward computed (rec.self_block / rec.fusion, keyed by their first LayerNorm
+# weight); the forward's own kernels and launches stay the same either way.  The backward hands it the gradients of the attention
+# outputs (rec.self_block_grad / rec.fusion_grad).  The backward runs on autograd's device thread, where this variable has its default
+# value: SelfAttentionBlockFn / CrossFusionFn capture the recorder in their forward (on ctx, only when it is set) and pass it on.
 ATTN_RECORDER: "contextvars.ContextVar" = contextvars.ContextVar("xvit_attn_recorder", default=None)
 
 
@@ -445,10 +447,11 @@ def block_forward(x, B, N, H, eps, scale, ln1w, ln1b, wqkv_s, bqkv, wo_s, bo, ln
 
 
 def block_backward(dy, saved, B, N, H, scale, ln1w, wqkv_s, has_bqkv, wo_s, ln2w, w1_s, w2_s, p_out=0.0, p_ffn=0.0, seeds=(0, 0, 0), p_attn=0.0, seed_attn=0,
-                   dy_b16=None, want_dx_b16=False):
+                   dy_b16=None, want_dx_b16=False, rec=None):
     """dy fp32 [B*N, d] -> (dx, grads dict).  Bias gradients cost no extra pass: b2 and bo fall out of the
     LN2 backward (column sums of its dres and dx), b1 out of the GELU' dgrad epilogue.  dy_b16: the bf16 copy of dy when the producer
-    supplied one (b16_of); want_dx_b16: also return dx in bf16 (g["dx_b16"]) for the block in front."""
+    supplied one (b16_of); want_dx_b16: also return dx in bf16 (g["dx_b16"]) for the block in front.  rec: the attention-map recorder
+    the forward saw (ATTN_RECORDER), handed the attention output's gradient."""
     x, mu1, rs1, h1, qkv, o, lse, x1, mu2, rs2, h2, z, a = saved
     d, f = x.shape[1], z.shape[1]
     zero = _zeros(6 * d + f, x)                               # every atomically-accumulated vector of this block
@@ -470,6 +473,8 @@ def block_backward(dy, saved, B, N, H, scale, ln1w, wqkv_s, has_bqkv, wo_s, ln2w
         ops.colsum(dx1b, out=g["bo"], accumulate=True)
     # attention
     do = _dgrad(dx1b, wo_s)
+    if rec is not None:
+        rec.self_block_grad(ln1w, do)
     g["wo"] = _wgrad(dx1b, o, wo_s)
     dqkv = ops.attn_bwd(qkv, o, do, lse, B, N, H, scale, dropout=(p_attn, seed_attn))
     dh1 = _dgrad(dqkv, wqkv_s)
@@ -498,6 +503,9 @@ class SelfAttentionBlockFn(Function):
         ctx.drop = (p, p, seeds)
         ctx.meta = (B, N, H, scale, x.dtype)
         ctx.save_for_backward(ln1w, ln2w, *sh, *saved)
+        rec = ATTN_RECORDER.get()
+        if rec is not None:
+            ctx.rec = rec
         return x2.reshape(B, N, d)
 
     @staticmethod
@@ -506,7 +514,7 @@ class SelfAttentionBlockFn(Function):
         ln1w, ln2w, wqkv_s, wo_s, w1_s, w2_s, *saved = ctx.saved_tensors
         d = ln1w.shape[0]
         dx, g = block_backward(_f32c(dy).reshape(B * N, -1), saved, B, N, H, scale, ln1w, wqkv_s, False, wo_s, ln2w, w1_s, w2_s, *ctx.drop,
-                               dy_b16=b16_of(dy, (B * N, d)), want_dx_b16=ctx.feeds_a_block and B16_HANDOFF)
+                               dy_b16=b16_of(dy, (B * N, d)), want_dx_b16=ctx.feeds_a_block and B16_HANDOFF, rec=getattr(ctx, "rec", None))
         keep(dx, dy)
         out = attach_b16(dx.reshape(B, N, -1).to(xdt), g["dx_b16"])
         return (out, g["ln1w"], g["ln1b"], g["wqkv"], g["wo"], g["bo"], g["ln2w"], g["ln2b"], g["w1"], g["b1"], g["w2"], g["b2"], None, None, None, None)
@@ -588,7 +596,7 @@ def cross_forward(xi, xj, B, N, H, eps, ln1w, ln1b, wq, bq, wkv_s, bkv, wp, bp, 
     rec = ATTN_RECORDER.get()
     if rec is not None:   # the CLS-query probabilities: p [B, H, N], or the low-rank form's weights e [B, N, 16] and 1 / sum e
         if lowrank:
-            rec.fusion(ln1w, B, N, H, e=e, rz=rz)
+            rec.fusion(ln1w, B, N, H, e=e, rz=rz, bv=bv)
         else:
             rec.fusion(ln1w, B, N, H, p=pr)
     y, _, _ = ops.linear_f32(ocf, wp, bp, residual=cls_in, dropout=_dp(p, seeds[1]))
@@ -603,9 +611,10 @@ def cross_forward(xi, xj, B, N, H, eps, ln1w, ln1b, wq, bq, wkv_s, bkv, wp, bp, 
     return y2, (keep_xi, xj, mu, rs, hn, kv, qb, oc, pr, y, mu2, rs2, h2, z, a)
 
 
-def cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_s, pd=0.0, seeds=(0, 0, 0, 0), wk=None, wv=None, want_dcat_b16=False):
+def cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_s, pd=0.0, seeds=(0, 0, 0, 0), wk=None, wv=None, want_dcat_b16=False, rec=None):
     """dy2 fp32 [B, d] -> (dcat fp32 [B*N, d] = grad of the normed concat input, dcls_res fp32 [B, d], grads); want_dcat_b16: g["dcat_b16"] is
-    dcat's bf16 copy, written by the same LayerNorm backward (attach_b16)."""
+    dcat's bf16 copy, written by the same LayerNorm backward (attach_b16).  rec: the attention-map recorder the forward saw (ATTN_RECORDER),
+    handed the attention output's gradient doc and dp[b, n, h] = dO_h . (v_h[n] - bv_h) (low-rank form) or v (literal order)."""
     lowrank = len(saved) == 18                                            # the forward ran the low-rank form: (R, e, rz, S, qf) instead of (kv, p)
     if lowrank:
         xi, xj, mu, rs, hn, R, e, rz, S, qf, q, oc, y, mu2, rs2, h2, z, a = saved
@@ -639,6 +648,8 @@ def cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_
         ops.head_rows(doc, wv, R[H:].transpose(0, 1), H, out_bf16=Yb)             # Y[b, h] = dO_h Wv_h: dp[b, n, h] = hn[b, n] . Y[b, h]
         dp = torch.empty(B, N, 16, dtype=torch.float32, device=xi.device)
         ops.gemm(ops.NT, hn3, Yb, dp)
+        if rec is not None:
+            rec.fusion_grad(ln1w, B, N, H, doc, dp=dp)
         drop = pd > 0.0                                                            # rz is then the forward's stat block (rz, rz / (1 - p), bv's weight)
         coef, dsb = ops.cls_softmax_bwd(e, rz[0] if drop else rz, dp, H, scale, dropout=(pd, seeds[0]))   # (ds | p') per token and head
         dhn = ops.xattn_kv_dgrad(coef, R, B, N, H, d)                              # dhn[n] = sum_h ds U_h + p Y_h
@@ -653,6 +664,8 @@ def cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_
     # the reference's literal order (XVIT_XATTN_FORM=dense, small eager batches under "auto", more than 16 heads): the K/V projection's
     # gradient through the [B N, 2 d] tensor — a K = 2 d dgrad GEMM, a wgrad GEMM and a column-sum pass
     doc = _dgrad(dyb1, wp_s)
+    if rec is not None:
+        rec.fusion_grad(ln1w, B, N, H, doc, v=kv[:, d:])
     dq, dkv = ops.cls_xattn_bwd(q, kv, p, doc, B, N, H, scale, dropout=(pd, seeds[0]))
     dhn = _dgrad(dkv, wkv_s)                                # [B*N, d] bf16
     g["wkv"] = _wgrad(dkv, hn)
@@ -703,6 +716,9 @@ class CrossFusionFn(Function):
         ctx.drop = (p, seeds)
         ctx.meta = (B, N, H, d, concat, inplace, narrow)
         ctx.save_for_backward(ln1w, ln2w, *sh, wk.detach(), wv.detach(), *saved)
+        rec = ATTN_RECORDER.get()
+        if rec is not None:
+            ctx.rec = rec
         if not concat:
             return y2.reshape(B, 1, d)
         if inplace:
@@ -720,7 +736,7 @@ class CrossFusionFn(Function):
         dy2 = ops.rows_combine(torch.empty(B, d, dtype=torch.float32, device=dout.device), a=dout[:, 0])
         # a cls-only fusion's patch-row gradient is (up to the CLS rows) the whole gradient of the partner's last block: hand it on in bf16 too
         dcat, dcls_res, g = cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_s, *ctx.drop, wk=wk_m, wv=wv_m,
-                                           want_dcat_b16=not concat and B16_HANDOFF)
+                                           want_dcat_b16=not concat and B16_HANDOFF, rec=getattr(ctx, "rec", None))
         dcat = dcat.reshape(B, N, d)
         # cls row -> x_i (normed-concat path + the un-normed residual path); patch rows -> x_j
         if concat:

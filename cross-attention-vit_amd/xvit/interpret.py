@@ -7,10 +7,16 @@
     maps.rollout[m]                               # [B, N] fp32: rollout of modality m's self-attention chain (ModelVIT: key 0)
     grid = xvit.interpret.patch_grid(maps.rollout[0][:, 1:], cfg.img_size, cfg.patch_size)   # [B, D/p1, H/p2, W/p3]
 
+    rel = xvit.interpret.relevance_maps(model, img, target=None)         # class-specific: which tokens drove the logit of `target`
+    rel.relevance[m]                              # [B, N] fp32: gradient-weighted relevance of modality m's self-attention chain
+    rel.fusion["transformer.1.fusion.0"]          # [B, N] fp32: gradient-weighted CLS-query map of that fusion
+
 The reference builds its attention probabilities as tensors (model_cross.py:55-59, :93-97); the fused kernels here never write them.
 The maps are taken inside one forward pass instead: the CLS row of a self-attention block is the CLS-query kernel
 (xvit_cls_xattn_fwd) run on the block's own qkv, a fusion's map is the probabilities its forward computes anyway, and rollout
-recomputes each block's probabilities from its q, k and log-sum-exp (xvit_attn_rollout_step) without storing them.
+recomputes each block's probabilities from its q, k and log-sum-exp (xvit_attn_rollout_step) without storing them.  Relevance adds
+one backward: each block's attention-output gradient dO is recorded there, and xvit_attn_relevance_step recomputes P and dP = dO V^T
+the same way.
 """
 from __future__ import annotations
 
@@ -34,32 +40,64 @@ class AttentionMaps:
     logits: torch.Tensor | None = None     # the forward's logits: those of model(img, labels) in eval mode
 
 
+@dataclass
+class RelevanceMaps:
+    """Class-specific maps keyed like AttentionMaps' rollout (relevance) and fusion (fusion)."""
+    relevance: dict = field(default_factory=dict)
+    fusion: dict = field(default_factory=dict)
+    logits: torch.Tensor | None = None     # the forward's logits: those of model(img, labels) in eval mode
+    target: torch.Tensor | None = None     # int64 [B]: the class explained per sample
+
+
 class _Recorder:
     """Receives what the forward computed (xvit.functional.ATTN_RECORDER) for the modules it knows, by their first LayerNorm weight."""
 
-    def __init__(self, names, rollout):
+    def __init__(self, names, rollout=False, relevance=False):
         self.names = names               # data_ptr of the block's first LayerNorm weight -> qualified name
-        self.rollout = rollout
+        self.rollout, self.relevance = rollout, relevance     # relevance: no CLS maps; keep qkv / lse, take dO and the fusions' gradients
         self.self_maps, self.fusion_maps, self.saved = {}, {}, {}
+        self.grads, self.fusion_rel, self.bv = {}, {}, {}
 
     def self_block(self, ln1w, qkv, lse, B, N, H, scale):
         name = self.names.get(ln1w.data_ptr())
         if name is None:
             return
-        d = qkv.shape[1] // 3
-        q0 = qkv.view(B, N, 3 * d)[:, 0, :d]            # each sample's CLS query row (row stride N * 3d)
-        _, p = ops.cls_xattn_fwd(q0, qkv[:, d:], B, N, H, scale)
-        self.self_maps[name] = p
-        if self.rollout:
+        if not self.relevance:
+            d = qkv.shape[1] // 3
+            q0 = qkv.view(B, N, 3 * d)[:, 0, :d]            # each sample's CLS query row (row stride N * 3d)
+            _, p = ops.cls_xattn_fwd(q0, qkv[:, d:], B, N, H, scale)
+            self.self_maps[name] = p
+        if self.rollout or self.relevance:
             self.saved[name] = (qkv, lse, B, N, H, scale)
 
-    def fusion(self, ln1w, B, N, H, p=None, e=None, rz=None):
+    def self_block_grad(self, ln1w, do):
+        name = self.names.get(ln1w.data_ptr())
+        if name is not None:
+            self.grads[name] = do            # bf16 [B*N, d]: the gradient of the block's attention output
+
+    def fusion(self, ln1w, B, N, H, p=None, e=None, rz=None, bv=None):
         name = self.names.get(ln1w.data_ptr())
         if name is None:
             return
         if p is None:   # low-rank form: p[b, h, n] = e[b, n, h] / sum_n e[b, n, h] (rz is computed from the rounded e: head_linear.hip)
             p = (e[:, :, :H].float() * rz[:, None, :]).permute(0, 2, 1).contiguous()
         self.fusion_maps[name] = p
+        if self.relevance and bv is not None:
+            self.bv[name] = bv
+
+    def fusion_grad(self, ln1w, B, N, H, doc, dp=None, v=None):
+        """doc [B, d]: the gradient of the fusion's attention output.  Low-rank form: dp [B, N, 16] = dO_h . (v_h[n] - bv_h), the
+        backward's own product, plus the bias term dO_h . bv_h (constant in n); literal order: v [B*N, d], the second half of kv."""
+        name = self.names.get(ln1w.data_ptr())
+        if name is None or not self.relevance:
+            return
+        dh = doc.shape[1] // H
+        do = doc.float().view(B, H, dh)
+        if v is None:
+            dpv = dp[:, :, :H].permute(0, 2, 1) + (do * self.bv[name].float().view(H, dh)).sum(-1)[:, :, None]
+        else:
+            dpv = torch.einsum("bhk,bnhk->bhn", do, v.float().view(B, N, H, dh))
+        self.fusion_rel[name] = (self.fusion_maps[name] * dpv).clamp_min(0).mean(dim=1)
 
 
 def _chains(model):
@@ -78,15 +116,16 @@ def _chains(model):
     return names, {k: v for k, v in chains.items() if v}
 
 
-def _check(model, img):
+def _check(model, img, who):
+    """The refusals of attention_maps and relevance_maps (`who`: the caller's name in the messages)."""
     if not isinstance(model, (ModelCross, ModelVIT)):
-        raise TypeError(f"attention_maps: need a ModelCross or a ModelVIT, got {type(model).__name__}")
+        raise TypeError(f"{who}: need a ModelCross or a ModelVIT, got {type(model).__name__}")
     if model.training:
-        raise RuntimeError("attention_maps: the model is in training mode (dropout would make the maps random); call model.eval() first")
+        raise RuntimeError(f"{who}: the model is in training mode (dropout would make the maps random); call model.eval() first")
     if os.environ.get("XVIT_ATTN_FP8", "0") == "1":
-        raise RuntimeError("attention_maps: the maps are defined on the bf16 attention forward; unset XVIT_ATTN_FP8")
+        raise RuntimeError(f"{who}: the maps are defined on the bf16 attention forward; unset XVIT_ATTN_FP8")
     if not (img.is_cuda and model.pos_embedding.is_cuda):
-        raise RuntimeError("attention_maps: model and img must be on the GPU (the maps come from the HIP kernels; there is no CPU path)")
+        raise RuntimeError(f"{who}: model and img must be on the GPU (the maps come from the HIP kernels; there is no CPU path)")
     if isinstance(model, ModelCross):
         blocks = [m for m in model.modules() if isinstance(m, (SelfAttentionBlock, CrossAttentionBlock))]
         heads = [b.attn.fn.heads if isinstance(b, SelfAttentionBlock) else b.attn.fn.num_heads for b in blocks]
@@ -95,7 +134,7 @@ def _check(model, img):
     d = model.pos_embedding.shape[-1]
     for H in heads:
         if d // H != 64:
-            raise ValueError(f"attention_maps: head dim {d // H} unsupported (only 64)")
+            raise ValueError(f"{who}: head dim {d // H} unsupported (only 64)")
 
 
 def attention_maps(model, img, rollout=False) -> AttentionMaps:
@@ -112,7 +151,7 @@ def attention_maps(model, img, rollout=False) -> AttentionMaps:
     Runs under torch.no_grad() with zero labels, on the current stream only.  Refuses training mode (dropout would make the maps
     random), XVIT_ATTN_FP8=1 (the maps are defined on the bf16 forward), tensors off the GPU and head dims other than 64.  With rollout
     the qkv and lse of every self-attention block stay alive until the rollout is done (19 MB per block at configs[1], B = 8)."""
-    _check(model, img)
+    _check(model, img, "attention_maps")
     names, chains = _chains(model)
     rec = _Recorder(names, rollout)
     labels = torch.zeros(img.shape[0], dtype=torch.long, device=img.device)
@@ -135,6 +174,73 @@ def attention_maps(model, img, rollout=False) -> AttentionMaps:
         XF.ATTN_RECORDER.reset(tok_rec)
         rec.saved.clear()
     return maps
+
+
+def relevance_maps(model, img, target=None) -> RelevanceMaps:
+    """Class-specific relevance (Chefer, Gur & Wolf, ICCV 2021, "Generic Attention-model Explainability for Interpreting Bi-Modal and
+    Encoder-Decoder Transformers") of `model` on `img`: which tokens drove the logit of `target`, per sample.
+
+    target          : None (each sample's argmax), an int, or an int64 tensor [B].
+    relevance[key]  : [B, N] fp32.  Starting from r = e_0, r <- r + r . mean_h relu(P_h * dP_h) through the branch's self-attention blocks
+                      from the last to the first, across all MultiScaleBlocks (the chains of attention_maps' rollout; keys likewise: the
+                      modality index m for ModelCross, 0 for ModelVIT).  dP_h = dO_h V_h^T is the gradient of the target logit with
+                      respect to P_h; P and dP are recomputed per block by xvit_attn_relevance_step, never stored.
+    fusion[name]    : [B, N] fp32, mean_h relu(p_h * dp_h) of the fusion's CLS-query probabilities p and their gradient dp (key 0 = CLS_i,
+                      keys 1.. = modality j's patches).
+    logits, target  : the forward's logits (bit-identical to those of model(img, labels) in eval mode) and the classes explained.
+
+    Costs one eval forward with grad enabled and one backward, on the current stream only: torch.autograd.grad of the logits with
+    grad_outputs one_hot(target) (samples are independent, so one backward serves the batch).  Every p.grad stays as it was, and no
+    weight gradient reaches a data-parallel reducer's buckets (XF.GRAD_SINK is unset for the duration).  Memory: the qkv, lse and dO of
+    every self-attention block stay alive until the chains are done (8 d bytes per token: 25 MB per block at configs[1], B = 8).
+    Refuses what attention_maps refuses: training mode, XVIT_ATTN_FP8=1, tensors off the GPU and head dims other than 64."""
+    _check(model, img, "relevance_maps")
+    names, chains = _chains(model)
+    B = img.shape[0]
+    if target is not None:
+        target = torch.as_tensor(target, dtype=torch.int64, device=img.device)
+        target = target.expand(B).contiguous() if target.dim() == 0 else target
+        if tuple(target.shape) != (B,):
+            raise ValueError(f"relevance_maps: target must be an int or an int64 tensor [{B}], got shape {tuple(target.shape)}")
+    rec = _Recorder(names, relevance=True)
+    labels = torch.zeros(B, dtype=torch.long, device=img.device)
+    params = [p for p in model.parameters() if p.requires_grad]
+    if not params:
+        raise RuntimeError("relevance_maps: no parameter of the model requires grad (the backward would not run)")
+    tok_rec, tok_mode = XF.ATTN_RECORDER.set(rec), STREAM_MODE.set("0")   # one stream: the backward and the steps are ordered on it
+    sink, arena = XF.GRAD_SINK, list(XF._ARENA)   # the forward opens a zero arena of its own: a pending training backward keeps its one
+    XF.GRAD_SINK = None                  # weight gradients go to fresh tensors, never into a reducer's bucket
+    try:
+        with torch.enable_grad():
+            logits, _ = model(img, labels)
+            C = logits.shape[1]
+            if target is None:
+                target = logits.detach().argmax(dim=1)
+            elif int(target.min()) < 0 or int(target.max()) >= C:
+                raise ValueError(f"relevance_maps: target out of range [0, {C})")
+            seed = torch.nn.functional.one_hot(target, C).to(logits.dtype)
+            grads = torch.autograd.grad(logits, params, grad_outputs=seed, allow_unused=True)
+            del grads
+        out = RelevanceMaps(fusion=rec.fusion_rel, logits=logits.detach(), target=target)
+        for key, chain in chains.items():
+            missing = [n for n in chain if n not in rec.grads]
+            if missing:
+                raise RuntimeError(f"relevance_maps: the backward did not reach {missing[0]} (do its parameters require grad?)")
+            B, N = rec.saved[chain[-1]][2:4]
+            r = torch.zeros(B, N, dtype=torch.float32, device=img.device)
+            r[:, 0] = 1.0
+            for name in reversed(chain):
+                qkv, lse, B, N, H, scale = rec.saved[name]
+                r = ops.attn_relevance_step(qkv, lse, rec.grads[name], r, B, N, H, scale)
+            out.relevance[key] = r
+    finally:
+        XF.GRAD_SINK = sink
+        XF._ARENA[:] = arena
+        STREAM_MODE.reset(tok_mode)
+        XF.ATTN_RECORDER.reset(tok_rec)
+        rec.saved.clear()
+        rec.grads.clear()
+    return out
 
 
 def patch_grid(t, img_size, patch_size, num_modalities=1):

@@ -293,6 +293,24 @@ def attn_rollout_step(qkv, lse, r, B, N, H, scale):
     return out
 
 
+def attn_relevance_step(qkv, lse, do, r, B, N, H, scale):
+    """One class-specific relevance step through a self-attention block (xvit_attn_relevance_step): qkv bf16 [B*N, 3d] and lse fp32
+    [B, H, N] of the block's forward, do bf16 [B*N, d] the gradient of its attention output, r fp32 [B, N] -> r_out fp32 [B, N] =
+    r + r . mean_h relu(P_h * dP_h), dP_h = dO_h V_h^T.  P and dP are recomputed, never stored."""
+    d = qkv.shape[1] // 3
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, N)
+    assert r.dtype == torch.float32 and r.is_contiguous() and tuple(r.shape) == (B, N)
+    assert do.dtype == torch.bfloat16 and tuple(do.shape) == (B * N, d)
+    out = torch.empty_like(r)
+    ld, ldo = _rows2d(qkv), _rows2d(do)
+    p = _ptr(qkv)
+    _run("attn_relevance", 4.0 * B * H * N * N * (d // H), "flop",
+         lambda: _lib.load().xvit_attn_relevance_step(p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(lse), _ptr(do), N * ldo, ldo, _ptr(r), _ptr(out),
+                                                      B, H, N, d // H, scale, _stream()),
+         "xvit_attn_relevance_step")
+    return out
+
+
 def attn_fwd_fp8(qkv, B, N, H, scale):
     """MX-fp8 forward attention (xvit_attn_fwd_fp8): qkv bf16 [B*N, 3d] -> (o bf16 [B*N, d], lse fp32 [B, H, N]); opt-in."""
     d = qkv.shape[1] // 3

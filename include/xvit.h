@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 305 /* 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 306 /* 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1 };
@@ -178,6 +178,16 @@ int64_t xvit_attn_bwd_workspace_bytes(int B, int H, int N);
  * (no atomics: bit-reproducible).  r_in and r_out must not overlap.  dh = 64 only. */
 int xvit_attn_rollout_step(const void* q, const void* k, int64_t stride_b, int64_t stride_n, const float* lse, const float* r_in, float* r_out,
                            int B, int H, int N, int dh, float scale, xvit_stream_t stream);
+/* One step of class-specific relevance (Chefer, Gur & Wolf 2021) through one self-attention block, for a row vector r_in [B, N] (fp32,
+ * contiguous):
+ *   r_out[b, n] = r_in[b, n] + 1 / H sum_h sum_m r_in[b, m] max(0, P_h[b, m, n] dP_h[b, m, n]),   dP_h[b, m, n] = dO[b, m, h] . v[b, n, h]
+ * P_h as in xvit_attn_rollout_step; q / k / v: the addressing of xvit_attn_fwd (pointers into the block's qkv); d_o: the gradient of
+ * the block's attention output, bf16 (ptr + b stride_b_do + n stride_n_do + 64 h).  P and dP are recomputed and never stored; the sum
+ * runs in fp32 in a fixed order (no atomics: bit-reproducible) and 1 / H times it is added to r_in last (r_in >= 0: r_out >= r_in
+ * exactly; dO = 0: r_out == r_in).  r_in and r_out must not overlap.  dh = 64 only. */
+int xvit_attn_relevance_step(const void* q, const void* k, const void* v, int64_t stride_b, int64_t stride_n, const float* lse, const void* d_o,
+                             int64_t stride_b_do, int64_t stride_n_do, const float* r_in, float* r_out, int B, int H, int N, int dh, float scale,
+                             xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * CLS-query cross-attention (model_cross.py:91-99): one query row per (b, h) against N keys.
