@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import ref_cpu as R
+from _attn_check import attn_bwd_emulated as _attn_bwd_emulated
 from _util import assert_close, dev, randn, rel, rt
 
 pytestmark = pytest.mark.gpu
@@ -98,21 +99,6 @@ def test_attention_fwd_bwd(B, H, N):
     else:
         assert rel(dk, kr.grad) < 6e-3, rel(dk, kr.grad)
         assert rel(dq, qr.grad) < 6e-3, rel(dq, qr.grad)
-
-
-def _attn_bwd_emulated(q, k, v, o_dev, do, lse, scale):
-    """The backward kernels' arithmetic on the CPU: P recomputed from the forward's lse, delta from the DEVICE o (bf16), and
-    P / dS rounded to bf16 where they feed the second MFMA of their product (attention.hip: dV^T += dO^T P, dK^T += Q^T dS,
-    dQ += dS K).  fp32 everywhere else."""
-    s = (q @ k.transpose(-1, -2)) * scale
-    p = torch.exp(s - lse[..., None])
-    dp = do @ v.transpose(-1, -2)
-    delta = (do * o_dev).sum(-1, keepdim=True)
-    ds = p * (dp - delta)
-    dv = rt(p).transpose(-1, -2) @ do
-    dk = rt(ds).transpose(-1, -2) @ q * scale
-    dq = rt(ds) @ k * scale
-    return dq, dk, dv
 
 
 @pytest.mark.parametrize("B,H,N", [(2, 12, 513), (1, 2, 3376), (1, 2, 4097), (2, 3, 130), (2, 2, 193)])
