@@ -46,6 +46,7 @@ struct GemmParams {
     int64_t sBt, sMd;      // element strides of batch and modality in the volume tensor
     uint32_t vol_bytes;
     uint32_t m_pcount, m_dn, m_wn, m_nb;   // floor(2^32 / divisor): mode 3 divides by these every K-step (fast_div)
+    uint32_t m_ntok;                       // mode 4 (input gradient): its scatter epilogue divides token rows by ntok
   } g;
 };
 
@@ -966,6 +967,83 @@ __device__ __forceinline__ void wave_tile_epilogue(const GemmParams& p, const f3
   else big_epilogue<XVIT_ACT_NONE, false>(p, e, acc, slice, woff, roff);
 }
 
+// ---- scatter epilogue (GATHER == 4, xvit_patch_embed_dgrad): output (row, col) = (token row, feature f) is written straight to its voxel ----
+// The mirror image of mode 1's gathering loaders: the [rows, dp hp wp] patch-gradient matrix is never stored.  Same LDS transpose as the
+// wide epilogue: a lane owns 8 consecutive features of one row, and with wp % 8 == 0 those are 8 consecutive voxels of one wp run, so
+// every store is one whole 16-byte run (bf16) or two (fp32).  Patches do not overlap: each voxel is written by exactly one (row, col)
+// and no atomics are needed.  CLS rows and rows / columns past the edge are computed but not stored.
+struct ScatterEpi {
+  char* vol;          // the volume gradient, fp32 (p.c_f32) or bf16
+  uint32_t eoff;      // this lane's 8-feature chunk inside a patch, in volume elements (gather_elem_off)
+  bool col_ok;
+  uint32_t row;       // the lane's current token row, advanced by 8 rows per body
+};
+
+__device__ __forceinline__ void scatter_body(const GemmParams& p, ScatterEpi& e, f32x4 v0, f32x4 v1) {
+  const GemmParams::PatchGather& g = p.g;
+  const uint32_t row = e.row;
+  e.row += 8;
+  if (!e.col_ok || row >= (uint32_t)p.M) return;
+  uint32_t n, b, d, w;
+  const uint32_t smp = fast_div(row, (uint32_t)g.ntok, g.m_ntok, n);   // sample (modality-major) and row inside it
+  if (n < (uint32_t)g.cls) return;                                      // CLS row: carries no patch
+  const uint32_t t = fast_div(n - (uint32_t)g.cls, (uint32_t)g.Dn, g.m_dn, d);
+  const uint32_t h = fast_div(t, (uint32_t)g.Wn, g.m_wn, w);
+  const uint32_t mod = fast_div(smp, (uint32_t)g.nb, g.m_nb, b);
+  // element offset < 2^30 (xvit_patch_embed_dgrad_supported); the byte address is formed in 64 bits (an fp32 volume may exceed 2 GiB)
+  const uint32_t off = b * (uint32_t)g.sBt + mod * (uint32_t)g.sMd + d * (uint32_t)(g.dp * g.Sz) + h * (uint32_t)(g.hp * g.Sy) + w * (uint32_t)g.wp + e.eoff;
+  if (p.c_f32) {
+    f32x4* dst = (f32x4*)((float*)e.vol + off);
+    dst[0] = v0;
+    dst[1] = v1;
+  } else {
+    *(u32x4_t*)((bf16*)e.vol + off) = pack_bf16x8(v0, v1);   // rounded once from the fp32 accumulators
+  }
+}
+
+template <int R>
+__device__ __forceinline__ void scatter_regions(const GemmParams& p, ScatterEpi& e, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, const uint32_t (&woff)[4],
+                                                const uint32_t (&roffw)[2][2]) {
+  if constexpr ((R & 3) == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) *(XVIT_LDS f32x4*)(slice + i * 4096 + woff[j]) = acc[(R >> 2) * 4 + i][j];
+  }
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const int it = (R & 3) * 2 + b;
+    const f32x4 v0 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][0]);
+    const f32x4 v1 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][1]);
+    scatter_body(p, e, v0, v1);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (R < 7) scatter_regions<R + 1>(p, e, acc, slice, woff, roffw);
+}
+
+__device__ __forceinline__ void scatter_epilogue(const GemmParams& p, const f32x4 (&acc)[8][4], XVIT_LDS char* smem, int wave, int lane, int row0, int col0) {
+  int pin = 0;                       // keep the address arithmetic below the K loop (see wave_tile_epilogue)
+  asm volatile("" : "+v"(pin));
+  const int wl = lane + pin;
+  uint32_t woff[4], roffw[2][2];     // the layout of wave_tile_epilogue_wide
+  {
+    const int r = wl & 15, g = wl >> 4, c = wl & 7, rr = wl >> 3;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) woff[j] = (uint32_t)(r * 256 + (((j * 4 + g) ^ r) << 4));
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) roffw[par][k] = (uint32_t)(rr * 256 + (((2 * c + k) ^ ((par * 8 + rr) & 15)) << 4));
+  }
+  ScatterEpi e;
+  e.vol = (char*)p.C;
+  const uint32_t col = (uint32_t)(col0 + (wl & 7) * 8);
+  e.col_ok = col < (uint32_t)p.N;
+  e.eoff = e.col_ok ? gather_elem_off(p.g, (int)col) : 0u;
+  e.row = (uint32_t)(row0 + (wl >> 3));
+  scatter_regions<0>(p, e, acc, smem + wave * EPI_WAVE_BYTES, woff, roffw);
+}
+
 // WIDE_ACT >= 0: the 16-byte-per-lane bf16 epilogue with that activation and no dropout, as its own instantiation (with
 // several fully unrolled epilogue variants behind one K loop the register allocator spills: one variant per kernel here;
 // the narrow kernels keep the run-time switch over activation x dropout and do not spill).  WIDE_ACT = -1: narrow.
@@ -1086,7 +1164,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last iteration's (zero-fill) DMAs have landed before the stage buffers are recycled
   __syncthreads();   // every wave is done reading the last stage: the stage buffers become the transpose slices
-  if constexpr (WIDE_ACT >= 0) wave_tile_epilogue_wide<WIDE_ACT>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch);
+  if constexpr (GATHER == 4) scatter_epilogue(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64);
+  else if constexpr (WIDE_ACT >= 0) wave_tile_epilogue_wide<WIDE_ACT>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch);
   else wave_tile_epilogue<GATHER == 1>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch, split);
 }
 
@@ -1297,7 +1376,7 @@ static void pe_fill(GemmParams& p, const xvit_patch_geom* g, int mode) {
   p.g.sMd = (int64_t)g->D * g->H * g->W; p.g.sBt = p.g.sMd * g->M;
   p.g.vol_bytes = (uint32_t)((int64_t)g->B * g->M * g->D * g->H * g->W * 2);
   auto magic = [](int d) { return d <= 1 ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / (uint64_t)d); };
-  p.g.m_pcount = magic(p.g.pcount); p.g.m_dn = magic(p.g.Dn); p.g.m_wn = magic(p.g.Wn); p.g.m_nb = magic(p.g.nb);
+  p.g.m_pcount = magic(p.g.pcount); p.g.m_dn = magic(p.g.Dn); p.g.m_wn = magic(p.g.Wn); p.g.m_nb = magic(p.g.nb); p.g.m_ntok = magic(p.g.ntok);
 }
 
 static void pe_defaults(GemmParams& p) {
@@ -1315,6 +1394,7 @@ static void pe_attrs() {
     (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, -1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
     (void)hipFuncSetAttribute((const void*)gemm_big_kernel<true, true, -1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
     (void)hipFuncSetAttribute((const void*)gemm_big_kernel<true, true, -1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
+    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, true, -1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
   });
 }
 
@@ -1389,6 +1469,51 @@ extern "C" int xvit_patch_embed_wgrad(const void* img, const xvit_patch_geom* g,
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(gsz), dim3(256), 0, s, p, 1);
   }
   return check_launch("xvit_patch_embed_wgrad");
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Input gradient of the patch embedding: dimg = dX W scattered onto the volume grid (the NN dgrad of the forward's NT product, GATHER
+// mode 4).  Operand A = the bf16 token gradient with its CLS rows, operand B = the bf16 weight [d, pd]; the scatter epilogue writes
+// each (token row, feature) to its voxel, so the [rows, pd] patch-gradient matrix never reaches HBM.  No split-K: deterministic.
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int xvit_patch_embed_dgrad_supported(const xvit_patch_geom* g, int d) {
+  if (!g || g->B <= 0 || g->M <= 0 || g->dp <= 0 || g->hp <= 0 || g->wp <= 0 || (g->cls_rows != 0 && g->cls_rows != 1)) return 0;
+  if (g->D % g->dp || g->H % g->hp || g->W % g->wp) return 0;
+  if (g->wp % 8) return 0;                                                 // a lane's 8 features = 8 voxels of one run: whole 16-byte stores
+  if (d % 64 || d < 64) return 0;                                          // the contraction runs in 64-deep K-steps of k-contiguous rows
+  const int64_t rows = pe_rows(g);
+  if (rows < 2048) return 0;                                               // small problems: xvit_gemm (NN) + xvit_unpatchify
+  if ((int64_t)g->B * g->M * g->D * g->H * g->W >= (1ll << 30)) return 0; // voxel offsets fit 30 bits (an fp32 result may exceed 2 GiB)
+  if (rows * d * 2 >= (1ll << 31)) return 0;
+  if ((int64_t)(g->D / g->dp) * (g->H / g->hp) * (g->W / g->wp) > (1 << 24)) return 0;
+  return 1;
+}
+
+extern "C" int xvit_patch_embed_dgrad(const void* dx, int64_t lddx, const void* W, int64_t ldw, const xvit_patch_geom* g, int d, void* dimg, int dimg_dtype,
+                                      xvit_stream_t stream) {
+  XVIT_REQUIRE(dx && W && g && dimg, "xvit_patch_embed_dgrad: null pointer");
+  XVIT_REQUIRE(dimg_dtype == XVIT_F32 || dimg_dtype == XVIT_BF16, "xvit_patch_embed_dgrad: bad output dtype %d", dimg_dtype);
+  XVIT_REQUIRE(xvit_patch_embed_dgrad_supported(g, d) == 1, "xvit_patch_embed_dgrad: geometry not supported by the fused kernel (xvit_patch_embed_dgrad_supported)");
+  const int64_t pd = (int64_t)g->dp * g->hp * g->wp;
+  XVIT_REQUIRE(lddx >= d && lddx % 8 == 0 && ldw >= pd && ldw % 8 == 0, "xvit_patch_embed_dgrad: bad leading dimension");
+  XVIT_REQUIRE(aligned16(dx) && aligned16(W) && aligned16(dimg), "xvit_patch_embed_dgrad: pointers must be 16-byte aligned");
+  XVIT_REQUIRE(pe_rows(g) * lddx * 2 < (1ll << 31) && (int64_t)d * ldw * 2 < (1ll << 31), "xvit_patch_embed_dgrad: an operand exceeds 2 GiB (unsupported addressing range)");
+  GemmParams p;
+  pe_defaults(p);
+  pe_fill(p, g, 4);
+  p.A = (const bf16*)dx; p.B = (const bf16*)W; p.C = dimg;
+  p.lda = lddx; p.ldb = ldw;
+  p.M = (int)pe_rows(g); p.N = (int)pd; p.K = d;
+  p.k_per_split = p.K;
+  p.c_f32 = dimg_dtype == XVIT_F32;
+  p.ntm = (p.M + TBM - 1) / TBM; p.ntn = (p.N + TBN - 1) / TBN;
+  {
+    const int forced = g_gemm_group.load(std::memory_order_relaxed);
+    p.ncg = forced > 0 ? std::min(forced, p.ntn) : p.ntn;
+  }
+  pe_attrs();
+  hipLaunchKernelGGL((gemm_big_kernel<false, true, -1, 4>), dim3(p.ntm * p.ntn, 1, 1), dim3(512), T_LDS, (hipStream_t)stream, p);
+  return check_launch("xvit_patch_embed_dgrad");
 }
 
 #ifdef XVIT_GEMM_CLOCK_PROBE

@@ -45,6 +45,44 @@ __global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ ou
   }
 }
 
+// unpatchify: the exact inverse of patchify_kernel (fp32 patch rows -> fp32 / bf16 volume).  Threads walk the OUTPUT in memory
+// order, 8 voxels = one 32 / 16-byte run each, so the volume is written fully coalesced; each reads its 32 bytes from one patch row.
+template <typename T, int VEC>
+__global__ void unpatchify_kernel(const float* __restrict__ in, T* __restrict__ img, int B, int M, int D, int H, int W, int dp, int hp, int wp,
+                                  int64_t stride_b, int64_t stride_m, int row_off, int64_t total_vec) {
+  const int Wv = W / VEC;
+  const int Dn = D / dp, Wn = W / wp;
+  const int pd = dp * hp * wp;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int wv = (int)(idx % Wv);
+    int64_t r = idx / Wv;
+    const int hh = (int)(r % H); r /= H;
+    const int dd = (int)(r % D); r /= D;
+    const int vol = (int)r;  // b*M + m
+    const int b = vol / M, m = vol - b * M;
+    const int w0 = wv * VEC;
+    const int w = w0 / wp, p3 = w0 - w * wp;
+    const int h = hh / hp, p2 = hh - h * hp;
+    const int d = dd / dp, p1 = dd - d * dp;
+    const int t = (h * Wn + w) * Dn + d;
+    const int f = (p1 * hp + p2) * wp + p3;
+    const float* src = in + ((int64_t)b * stride_b + (int64_t)m * stride_m + t + row_off) * pd + f;
+    T* dst = img + idx * VEC;
+    if constexpr (VEC == 8) {
+      const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
+      if constexpr (sizeof(T) == 4) {
+        ((f32x4*)dst)[0] = a;
+        ((f32x4*)dst)[1] = c;
+      } else {
+        *(bf16x8*)dst = bf16x8{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(c[0]), f2bf(c[1]), f2bf(c[2]), f2bf(c[3])};
+      }
+    } else {
+      if constexpr (sizeof(T) == 4) *dst = *src;
+      else *dst = f2bf(*src);
+    }
+  }
+}
+
 // zero row 0 of every [rows_per, pd] sample (the CLS slot of the padded patch matrix)
 __global__ void zero_rows_kernel(bf16* __restrict__ out, int samples, int64_t sample_stride, int pd) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -307,6 +345,27 @@ extern "C" int xvit_patchify(const void* img, int img_dtype, void* out, int B, i
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, o, zero_rows, zero_row_stride * pd, pd);
   }
   return check_launch("xvit_patchify");
+}
+
+extern "C" int xvit_unpatchify(const float* patches, void* img, int img_dtype, int B, int M, int D, int H, int W, int dp, int hp, int wp, int64_t stride_b,
+                               int64_t stride_m, int row_off, xvit_stream_t stream) {
+  XVIT_REQUIRE(patches && img, "xvit_unpatchify: null pointer");
+  XVIT_REQUIRE(B > 0 && M > 0 && D > 0 && H > 0 && W > 0 && dp > 0 && hp > 0 && wp > 0, "xvit_unpatchify: bad sizes");
+  XVIT_REQUIRE(D % dp == 0 && H % hp == 0 && W % wp == 0, "xvit_unpatchify: image dimensions must be divisible by the patch size");
+  XVIT_REQUIRE(img_dtype == XVIT_F32 || img_dtype == XVIT_BF16, "xvit_unpatchify: bad dtype");
+  XVIT_REQUIRE(stride_b > 0 && stride_m > 0 && row_off >= 0, "xvit_unpatchify: bad input placement");
+  const int64_t total = (int64_t)B * M * D * H * W;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = (wp % 8 == 0) && ((reinterpret_cast<uintptr_t>(patches) & 31) == 0) && ((reinterpret_cast<uintptr_t>(img) & 31) == 0);
+  if (vec) {
+    const int64_t tv = total / 8;
+    if (img_dtype == XVIT_F32) hipLaunchKernelGGL((unpatchify_kernel<float, 8>), dim3(grid_for(tv, 256)), dim3(256), 0, s, patches, (float*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, tv);
+    else hipLaunchKernelGGL((unpatchify_kernel<bf16, 8>), dim3(grid_for(tv, 256)), dim3(256), 0, s, patches, (bf16*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, tv);
+  } else {
+    if (img_dtype == XVIT_F32) hipLaunchKernelGGL((unpatchify_kernel<float, 1>), dim3(grid_for(total, 256)), dim3(256), 0, s, patches, (float*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, total);
+    else hipLaunchKernelGGL((unpatchify_kernel<bf16, 1>), dim3(grid_for(total, 256)), dim3(256), 0, s, patches, (bf16*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, total);
+  }
+  return check_launch("xvit_unpatchify");
 }
 
 extern "C" int xvit_cls_row_fwd(const float* cls, const float* pos, float* x, int MB, int N, int d, xvit_stream_t stream) {

@@ -6,6 +6,7 @@ own nn.Module signatures (vsahni3/cross-attention-ViT: model_cross.py, model.py)
     from xvit.model import Encoder                   # drop-in for reference model.Encoder
     xvit.interpret.attention_maps(model, img)        # CLS attention maps and attention rollout (eval mode)
     xvit.interpret.relevance_maps(model, img)        # class-specific relevance (one backward, eval mode)
+    xvit.interpret.input_attributions(model, img)    # voxel attributions: gradient, grad x input, integrated gradients (eval mode)
 """
 from . import _lib  # noqa: F401
 from .functional import invalidate_shadows  # noqa: F401

@@ -62,6 +62,9 @@ SIGNATURES = {
     "xvit_patch_embed_supported": [C.POINTER(PatchGeom), i32],
     "xvit_patch_embed_fwd": [vp, C.POINTER(PatchGeom), vp, i64, vp, vp, i64, vp, i64, i32, vp],
     "xvit_patch_embed_wgrad": [vp, C.POINTER(PatchGeom), vp, i64, vp, i64, i32, vp, i64, vp],
+    "xvit_patch_embed_dgrad_supported": [C.POINTER(PatchGeom), i32],
+    "xvit_patch_embed_dgrad": [vp, i64, vp, i64, C.POINTER(PatchGeom), i32, vp, i32, vp],
+    "xvit_unpatchify": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i32, vp],
     "xvit_cls_row_fwd": [vp, vp, vp, i32, i32, i32, vp],
     "xvit_embed_bwd": [vp, vp, vp, i32, i32, i32, vp],
     "xvit_cast_f32_bf16": [vp, vp, i64, vp],

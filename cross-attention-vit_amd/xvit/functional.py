@@ -797,6 +797,10 @@ class PatchEmbedFn(Function):
         if p > 0.0:                       # self.dropout on the embedded tokens (model_cross.py:198)
             ops.dropout(x, p, seed, out=x)
         ctx.meta = (M, Bn, N, d, p, seed, patch if fused else None)
+        ctx.vol = (tuple(img.shape), img.dtype, patch, concat)    # the input gradient needs the volume's geometry only, never its values
+        rec = ATTN_RECORDER.get()
+        if rec is not None and getattr(rec, "input_grad", False):
+            ctx.rec = rec                      # xvit.interpret.input_attributions: the fp32 volume gradient goes to the recorder
         ctx.save_for_backward(patches, w_s)     # fused: the volume tensor itself
         if concat:
             return x.reshape(Bn, N, d)
@@ -829,8 +833,50 @@ class PatchEmbedFn(Function):
         else:
             dW = _wgrad(dxb, patches, w_s)   # the zero CLS rows of `patches` drop the CLS-row gradients
         db = ops.colsum(dpos[1:])            # bias reaches the P patch rows of every sample
+        dimg = None
+        rec = getattr(ctx, "rec", None)
+        if ctx.needs_input_grad[0] or rec is not None:    # nothing is launched for a volume that does not require grad
+            shape, dtype, patch, concat = ctx.vol
+            if rec is not None:              # fp32 out of band: autograd would cast a returned gradient to the volume's dtype
+                rec.take_input_grad(_input_grad(dxb, w_s, shape, patch, concat, torch.float32))
+            else:
+                dimg = _input_grad(dxb, w_s, shape, patch, concat, dtype)
         _join_wgrads(dev)
-        return None, dW, db, dcls.reshape(1, 1, d), dpos.reshape(1, N, d), None, None, None
+        return dimg, dW, db, dcls.reshape(1, 1, d), dpos.reshape(1, N, d), None, None, None
+
+
+_PATCH_GRAD_CHUNK_BYTES = 1 << 30   # the fallback's fp32 patch-gradient matrix per batch chunk (each batch entry of its GEMM stays below 2 GiB)
+
+
+def _input_grad(dxb, w_s, shape, patch, concat, dtype):
+    """The volume gradient dimg [B, M, 1, D, H, W] (`dtype`) = dx W on the voxel grid; dxb: the bf16 token gradient with its CLS rows
+    (embedding dropout applied).  The fused scatter GEMM (xvit_patch_embed_dgrad) where the geometry allows; otherwise, as the forward
+    falls back to patchify + GEMM, an NN GEMM into an fp32 patch matrix and xvit_unpatchify, in batch chunks of at most
+    _PATCH_GRAD_CHUNK_BYTES."""
+    d, pd = w_s.shape
+    if not concat and ops.patch_embed_dgrad_supported(shape, patch, d, cls_rows=1):
+        return ops.patch_embed_dgrad(dxb, w_s, shape, patch, dtype)
+    B, M = shape[0], shape[1]
+    P = (shape[3] // patch[0]) * (shape[4] // patch[1]) * (shape[5] // patch[2])
+    out = torch.empty(shape, dtype=dtype, device=dxb.device)
+    if concat:   # ModelVIT: one sequence per sample, cls + the patches of every modality
+        S = M * P + 1
+        step = max(1, _PATCH_GRAD_CHUNK_BYTES // (S * pd * 4))
+        for b0 in range(0, B, step):
+            b1 = min(B, b0 + step)
+            dp = torch.empty((b1 - b0) * S, pd, dtype=torch.float32, device=dxb.device)
+            ops.gemm(ops.NN, dxb[b0 * S:b1 * S], w_s, dp)
+            ops.unpatchify(dp, out[b0:b1], patch, concat=True)
+    else:        # ModelCross: rows [modality][sample][cls + P]; a batch chunk is a strided batch over the modalities
+        N = P + 1
+        dx3 = dxb.view(M, B * N, d)
+        step = max(1, _PATCH_GRAD_CHUNK_BYTES // (M * N * pd * 4))
+        for b0 in range(0, B, step):
+            b1 = min(B, b0 + step)
+            dp = torch.empty(M, (b1 - b0) * N, pd, dtype=torch.float32, device=dxb.device)
+            ops.gemm(ops.NN, dx3[:, b0 * N:b1 * N], w_s.expand(M, d, pd), dp)
+            ops.unpatchify(dp, out[b0:b1], patch, pad_cls_row=True)
+    return out
 
 
 # ------------------------------------------------------------------------------------------

@@ -11,12 +11,16 @@
     rel.relevance[m]                              # [B, N] fp32: gradient-weighted relevance of modality m's self-attention chain
     rel.fusion["transformer.1.fusion.0"]          # [B, N] fp32: gradient-weighted CLS-query map of that fusion
 
+    att = xvit.interpret.input_attributions(model, img, method="integrated_gradients", steps=32)   # voxel resolution
+    att.attributions                              # [B, M, D, H, W] fp32; att.delta [B]: the completeness residual
+
 The reference builds its attention probabilities as tensors (model_cross.py:55-59, :93-97); the fused kernels here never write them.
 The maps are taken inside one forward pass instead: the CLS row of a self-attention block is the CLS-query kernel
 (xvit_cls_xattn_fwd) run on the block's own qkv, a fusion's map is the probabilities its forward computes anyway, and rollout
 recomputes each block's probabilities from its q, k and log-sum-exp (xvit_attn_rollout_step) without storing them.  Relevance adds
 one backward: each block's attention-output gradient dO is recorded there, and xvit_attn_relevance_step recomputes P and dP = dO V^T
-the same way.
+the same way.  Voxel attributions (input_attributions) take the gradient through the patch embedding back onto the volume grid: the
+fused input-gradient GEMM (xvit_patch_embed_dgrad) scatters dX W straight to the voxels.
 """
 from __future__ import annotations
 
@@ -47,6 +51,15 @@ class RelevanceMaps:
     fusion: dict = field(default_factory=dict)
     logits: torch.Tensor | None = None     # the forward's logits: those of model(img, labels) in eval mode
     target: torch.Tensor | None = None     # int64 [B]: the class explained per sample
+
+
+@dataclass
+class InputAttributions:
+    """Voxel attributions of input_attributions."""
+    attributions: torch.Tensor | None = None   # fp32 [B, M, D, H, W]
+    logits: torch.Tensor | None = None     # the forward's logits on img: those of model(img, labels) in eval mode
+    target: torch.Tensor | None = None     # int64 [B]: the class explained per sample
+    delta: torch.Tensor | None = None      # fp32 [B], integrated_gradients only: sum(attributions) - (logit_t(img) - logit_t(baseline))
 
 
 class _Recorder:
@@ -98,6 +111,19 @@ class _Recorder:
         else:
             dpv = torch.einsum("bhk,bnhk->bhn", do, v.float().view(B, N, H, dh))
         self.fusion_rel[name] = (self.fusion_maps[name] * dpv).clamp_min(0).mean(dim=1)
+
+
+class _InputGradRecorder(_Recorder):
+    """Knows no attention module (every map hook returns at once); takes the fp32 volume gradient PatchEmbedFn's backward computes
+    when a recorder with input_grad is set (xvit.functional.ATTN_RECORDER)."""
+    input_grad = True
+
+    def __init__(self):
+        super().__init__({})
+        self.dimg = None
+
+    def take_input_grad(self, dimg):
+        self.dimg = dimg
 
 
 def _chains(model):
@@ -240,6 +266,131 @@ def relevance_maps(model, img, target=None) -> RelevanceMaps:
         XF.ATTN_RECORDER.reset(tok_rec)
         rec.saved.clear()
         rec.grads.clear()
+    return out
+
+
+ATTRIBUTION_METHODS = ("gradient", "grad_x_input", "integrated_gradients")
+
+
+def input_attributions(model, img, target=None, method="integrated_gradients", steps=32, baseline=None, batch_size=16) -> InputAttributions:
+    """Voxel-level attributions of `model` on `img` [B, M, 1, D, H, W]: which voxels drove the logit of `target`, per sample.
+
+    method          : "gradient"              d logit_t / d img;
+                      "grad_x_input"          that gradient times (img - baseline);
+                      "integrated_gradients"  (Sundararajan, Taly & Yan, ICML 2017) (img - baseline) times the mean gradient at the
+                                              `steps` points baseline + a_k (img - baseline), a_k = (k + 1/2) / steps (midpoint rule).
+    target          : None (each sample's argmax), an int, or an integer tensor [B] (floating-point targets are refused); a class
+                      out of range is refused before any gradient is seeded.
+    baseline        : None (zeros) or a GPU tensor [1 or B, M, 1, D, H, W].
+    batch_size      : the volumes of one pass (interpolants of every sample laid along the batch): at most this many per forward +
+                      backward, so a single volume's IG scan still fills the GPU.
+    attributions    : fp32 [B, M, D, H, W], also for bf16 volumes (the gradient comes out of the fused input-gradient kernel in fp32).
+    logits, target  : the forward's logits on img and the classes explained.
+    delta           : integrated_gradients only, fp32 [B]: the completeness residual sum(attributions) - (logit_t(img) - logit_t(baseline));
+                      it shrinks as `steps` grows.
+
+    Interpolants are built in img's dtype (a bf16 volume keeps the fused patch-embedding forward).  Each pass is one eval forward with
+    grad enabled and one backward on the current stream.  The backward computes every weight gradient too (each backward Function
+    does): an attribution pass costs a full training backward plus the input-gradient GEMM.  Every p.grad stays as it was, no weight
+    gradient reaches a data-parallel reducer's buckets, and the zero arena and stream mode are restored.  Refuses training mode,
+    XVIT_ATTN_FP8=1, tensors off the GPU and head dims other than 64."""
+    who = "input_attributions"
+    if method not in ATTRIBUTION_METHODS:
+        raise ValueError(f"{who}: method must be one of {ATTRIBUTION_METHODS}, got {method!r}")
+    if int(steps) < 1 or int(batch_size) < 1:
+        raise ValueError(f"{who}: steps and batch_size must be >= 1 (got {steps}, {batch_size})")
+    steps, batch_size = int(steps), int(batch_size)
+    if img.dim() != 6 or img.shape[2] != 1:
+        raise ValueError(f"{who}: img must be [B, M, 1, D, H, W], got shape {tuple(img.shape)}")
+    B = img.shape[0]
+    if target is not None:
+        t_in = torch.as_tensor(target)
+        if t_in.is_floating_point() or t_in.is_complex() or t_in.dtype == torch.bool:
+            raise ValueError(f"{who}: target must be an int or an integer tensor [{B}], got dtype {t_in.dtype} (a class index is never rounded)")
+        target = t_in.to(torch.int64)
+        target = target.expand(B).contiguous() if target.dim() == 0 else target
+        if tuple(target.shape) != (B,):
+            raise ValueError(f"{who}: target must be an int or an int64 tensor [{B}], got shape {tuple(target.shape)}")
+        if B > 0 and int(target.min()) < 0:
+            raise ValueError(f"{who}: target out of range: negative class {int(target.min())}")
+    if baseline is not None and (baseline.dim() != 6 or baseline.shape[0] not in (1, B) or baseline.shape[1:] != img.shape[1:]):
+        raise ValueError(f"{who}: baseline must be [1 or {B}, {', '.join(str(s) for s in img.shape[1:])}], got shape {tuple(baseline.shape)}")
+    _check(model, img, who)
+    if baseline is not None and not baseline.is_cuda:
+        raise RuntimeError(f"{who}: baseline must be on the GPU")
+    dev = img.device
+    img = img.detach()
+    base = torch.zeros((1,) + tuple(img.shape[1:]), dtype=img.dtype, device=dev) if baseline is None else baseline.detach().to(img.dtype)
+    rec = _InputGradRecorder()
+    tok_rec, tok_mode = XF.ATTN_RECORDER.set(rec), STREAM_MODE.set("0")   # one stream: forward, backward and the sums are ordered on it
+    sink, arena = XF.GRAD_SINK, list(XF._ARENA)
+    XF.GRAD_SINK = None                  # weight gradients go to fresh tensors, never into a reducer's bucket
+
+    def forward(x):                      # logits of x in passes of at most batch_size volumes, no graph
+        with torch.no_grad():
+            return torch.cat([model(x[i:i + batch_size], torch.zeros(min(batch_size, x.shape[0] - i), dtype=torch.long, device=dev))[0]
+                              for i in range(0, x.shape[0], batch_size)])
+
+    def check_target(t, C):              # before any one_hot: on the GPU, one_hot leaves its bounds to the scatter kernel
+        if int(t.min()) < 0 or int(t.max()) >= C:
+            raise ValueError(f"{who}: target out of range [0, {C})")
+
+    def grad_pass(x, t):                 # fp32 d(sum_i logits[i, t[i]]) / dx and the logits: one forward + backward
+        xin = x.detach().requires_grad_(True)
+        with torch.enable_grad():
+            logits, _ = model(xin, torch.zeros(x.shape[0], dtype=torch.long, device=dev))
+            if t is None:
+                t = logits.detach().argmax(dim=1)
+            check_target(t, logits.shape[1])
+            seed = torch.nn.functional.one_hot(t, logits.shape[1]).to(logits.dtype)
+            rec.dimg = None
+            torch.autograd.grad(logits, xin, grad_outputs=seed, allow_unused=True)
+        g, rec.dimg = rec.dimg, None
+        return g, logits.detach(), t
+
+    try:
+        if target is not None:
+            target = target.to(dev)
+        if method == "integrated_gradients":
+            logits = forward(img)
+            C = logits.shape[1]
+            if target is None:
+                target = logits.argmax(dim=1)
+            check_target(target, C)
+            lb = forward(base)
+            lb = lb.expand(B, C) if lb.shape[0] == 1 else lb
+            diff = img.float() - base.float()                       # [B, ...] (a [1, ...] baseline broadcasts)
+            gsum = torch.zeros(img.shape, dtype=torch.float32, device=dev)
+            smp = torch.arange(B, device=dev).repeat_interleave(steps)     # (sample, step) pairs, sample-major
+            alpha = ((torch.arange(steps, dtype=torch.float32, device=dev) + 0.5) / steps).repeat(B)
+            for i in range(0, B * steps, batch_size):
+                j = min(B * steps, i + batch_size)
+                idx, a = smp[i:j], alpha[i:j]
+                b0 = base[idx] if base.shape[0] == B else base.expand(j - i, *base.shape[1:])
+                x = (b0.float() + a.view(-1, 1, 1, 1, 1, 1) * diff[idx]).to(img.dtype)
+                g, _, _ = grad_pass(x, target[idx])
+                for s in range(i // steps, (j - 1) // steps + 1):           # each sample's rows of this pass, summed in a fixed order
+                    lo, hi = max(i, s * steps) - i, min(j, (s + 1) * steps) - i
+                    gsum[s] += g[lo:hi].sum(dim=0)
+            attr = diff * (gsum / steps)
+            gather = lambda l: l.gather(1, target.view(B, 1)).view(B)   # noqa: E731
+            delta = attr.reshape(B, -1).sum(dim=1) - (gather(logits) - gather(lb))
+            out = InputAttributions(attributions=attr[:, :, 0], logits=logits, target=target, delta=delta)
+        else:
+            parts, lparts, tparts = [], [], []
+            for i in range(0, B, batch_size):
+                g, l, t = grad_pass(img[i:i + batch_size], None if target is None else target[i:i + batch_size])
+                parts.append(g); lparts.append(l); tparts.append(t)
+            g = torch.cat(parts) if len(parts) > 1 else parts[0]
+            if method == "grad_x_input":
+                g = g * (img.float() - base.float())
+            out = InputAttributions(attributions=g[:, :, 0], logits=torch.cat(lparts), target=torch.cat(tparts))
+    finally:
+        XF.GRAD_SINK = sink
+        XF._ARENA[:] = arena
+        STREAM_MODE.reset(tok_mode)
+        XF.ATTN_RECORDER.reset(tok_rec)
+        rec.dimg = None
     return out
 
 

@@ -495,7 +495,11 @@ def patchify(img, patch, pad_cls_row=False, concat=False):
 
 
 def _patch_geom(img, patch, cls_rows):
-    B, M, _, D, H, W = img.shape
+    return _patch_geom_of(tuple(img.shape), patch, cls_rows)
+
+
+def _patch_geom_of(shape, patch, cls_rows):
+    B, M, _, D, H, W = shape
     g = _lib.PatchGeom()
     g.B, g.M, g.D, g.H, g.W = B, M, D, H, W
     g.dp, g.hp, g.wp = patch
@@ -546,6 +550,53 @@ def patch_embed_wgrad(img, patch, dx_b, cls_rows=1, out=None):
          lambda: _lib.load().xvit_patch_embed_wgrad(_ptr(img), C.byref(g), _ptr(dx_b), dx_b.stride(0), _ptr(dW), dW.stride(0), d, _ptr(ws), need, _stream()),
          "xvit_patch_embed_wgrad")
     return dW
+
+
+def patch_embed_dgrad_supported(shape, patch, d, cls_rows=1):
+    """True when the fused input gradient (xvit_patch_embed_dgrad) takes a volume of `shape` [B, M, 1, D, H, W]: any dtype, since the
+    volume is only written.  XVIT_PATCH_EMBED=unfused forces the NN GEMM + xvit_unpatchify path, as it does for the forward."""
+    if os.environ.get("XVIT_PATCH_EMBED", "fused") == "unfused":
+        return False
+    if len(shape) != 6 or shape[2] != 1:
+        return False
+    return _lib.load().xvit_patch_embed_dgrad_supported(C.byref(_patch_geom_of(tuple(shape), patch, cls_rows)), int(d)) == 1
+
+
+def patch_embed_dgrad(dx_b, w_b, shape, patch, dtype=torch.float32, cls_rows=1, out=None):
+    """dimg [B, M, 1, D, H, W] (fp32 | bf16) = dx W scattered onto the voxel grid, the patch-gradient matrix never stored
+    (xvit_patch_embed_dgrad).  dx_b: bf16 [M*B*(cls_rows + P), d] with its CLS rows (never stored); w_b: bf16 [d, pd]."""
+    shape = tuple(shape)
+    g = _patch_geom_of(shape, patch, cls_rows)
+    B, M, _, D, H, W = shape
+    P, pd = (D // patch[0]) * (H // patch[1]) * (W // patch[2]), patch[0] * patch[1] * patch[2]
+    d = w_b.shape[0]
+    assert dx_b.dtype == torch.bfloat16 and dx_b.shape == (M * B * (cls_rows + P), d) and dx_b.stride(1) == 1
+    assert w_b.dtype == torch.bfloat16 and w_b.shape == (d, pd) and w_b.stride(1) == 1
+    out = out if out is not None else torch.empty(shape, dtype=dtype, device=dx_b.device)
+    assert tuple(out.shape) == shape and out.is_contiguous()
+    _run("patch_embed_dgrad", 2.0 * M * B * P * d * pd, "flop",
+         lambda: _lib.load().xvit_patch_embed_dgrad(_ptr(dx_b), dx_b.stride(0), _ptr(w_b), w_b.stride(0), C.byref(g), d, _ptr(out), _dt(out), _stream()),
+         "xvit_patch_embed_dgrad")
+    return out
+
+
+def unpatchify(patches, out, patch, pad_cls_row=False, concat=False):
+    """The inverse of patchify (xvit_unpatchify): fp32 patch rows laid out as patchify(..., pad_cls_row, concat) lays them out ->
+    out [B, M, 1, D, H, W] (fp32 | bf16, contiguous; every voxel written).  CLS rows are never read."""
+    assert out.dim() == 6 and out.shape[2] == 1 and out.is_contiguous()
+    B, M, _, D, H, W = out.shape
+    dp, hp, wp = patch
+    P, pd = (D // dp) * (H // hp) * (W // wp), dp * hp * wp
+    if concat:
+        rows = M * P + 1
+        place, n = (rows, P, 1), B * rows
+    else:
+        pad = int(bool(pad_cls_row))
+        place, n = (P + pad, B * (P + pad), pad), M * B * (P + pad)
+    assert patches.dtype == torch.float32 and patches.is_contiguous() and patches.numel() == n * pd
+    _run("unpatchify", out.numel() * (4.0 + out.element_size()), "byte",
+         lambda: _lib.load().xvit_unpatchify(_ptr(patches), _ptr(out), _dt(out), B, M, D, H, W, dp, hp, wp, *place, _stream()), "xvit_unpatchify")
+    return out
 
 
 def cls_row_fwd(cls, pos, x, MB, N, d):

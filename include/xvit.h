@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 306 /* 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 307 /* 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1 };
@@ -261,6 +261,12 @@ int xvit_attn_fwd_fp8(const void* q, const void* k, const void* v, int64_t strid
  * ---------------------------------------------------------------------------------------- */
 int xvit_patchify(const void* img, int img_dtype, void* patches_bf16, int B, int M, int D, int H, int W, int dp, int hp, int wp,
                   int64_t stride_b, int64_t stride_m, int row_off, int zero_rows, int64_t zero_row_stride, xvit_stream_t stream);
+/* The exact inverse of xvit_patchify, for gradients: patches fp32 [*, pd] -> img [B, M, 1, D, H, W] (fp32 or bf16 by img_dtype, contiguous,
+ * rounded once to nearest even).  Voxel (b, m, z, y, x) is read from row  b*stride_b + m*stride_m + t + row_off, column f  (token and
+ * feature order of xvit_patchify), so the same placements apply (ModelCross: stride_b = P+1, stride_m = B*(P+1), row_off = 1; ModelVIT:
+ * stride_b = M*P+1, stride_m = P, row_off = 1) and the CLS rows are never read.  Every voxel of img is written. */
+int xvit_unpatchify(const float* patches, void* img, int img_dtype, int B, int M, int D, int H, int W, int dp, int hp, int wp, int64_t stride_b,
+                    int64_t stride_m, int row_off, xvit_stream_t stream);
 /* ------------------------------------------------------------------------------------------
  * Patch embedding straight from the volume (model_cross.py:193-197: rearrange -> patch_to_embedding -> + pos_embedding):
  *   x[(m*B + b)*(cls_rows + P) + cls_rows + t, :] = patch(b, m, t) W^T + bias + pos[cls_rows + t, :]
@@ -287,6 +293,18 @@ int xvit_patch_embed_fwd(const void* img_bf16, const xvit_patch_geom* g, const v
 int64_t xvit_patch_embed_wgrad_workspace_bytes(const xvit_patch_geom* g, int d);
 int xvit_patch_embed_wgrad(const void* img_bf16, const xvit_patch_geom* g, const void* dx_bf16, int64_t lddx, float* dW, int64_t lddw, int d, void* workspace,
                            int64_t workspace_bytes, xvit_stream_t stream);
+/* Input gradient of the patch embedding, the patch-gradient matrix never stored:
+ *   dimg[b, m, 0, z, y, x] = sum_c dx[(m*B + b)*(cls_rows + P) + cls_rows + t, c] W[c, f]
+ * for the voxel at feature f of patch t (the token / feature order of xvit_patchify).  The 256x256 NN GEMM with dx (bf16, CLS rows
+ * included, row stride lddx) as A and W (bf16 [d, pd], row stride ldw) as B; its epilogue maps each (row, column) to its voxel and stores
+ * whole 16-byte runs.  CLS rows are computed but never stored.  dimg [B, M, 1, D, H, W] contiguous, fp32 or bf16 by dimg_dtype (bf16:
+ * rounded once from the fp32 accumulator), independent of the forward volume's dtype; every voxel is written exactly once (patches do
+ * not overlap), no atomics, no split-K: bit-reproducible.
+ * xvit_patch_embed_dgrad_supported: 1 when the geometry fits (wp % 8 == 0, d % 64 == 0, >= 2048 token rows, < 2^30 voxels); a superset of
+ * xvit_patch_embed_supported.  Otherwise: xvit_gemm (NN, fp32 C) into a patch matrix, then xvit_unpatchify. */
+int xvit_patch_embed_dgrad_supported(const xvit_patch_geom* g, int d);
+int xvit_patch_embed_dgrad(const void* dx_bf16, int64_t lddx, const void* W_bf16, int64_t ldw, const xvit_patch_geom* g, int d, void* dimg, int dimg_dtype,
+                           xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Input stage (dataset_ucsf.py:84-88, 152-158): MONAI `ResizeWithPadOrCropd(spatial_size, constant_values=pad_value)`
