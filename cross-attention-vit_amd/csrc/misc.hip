@@ -476,14 +476,30 @@ namespace xvit {
 struct AdamTensor { float* p; const float* g; float* m; float* v; bf16* shadow; int64_t n; };
 constexpr int ADAM_CHUNK = 16384;   // elements per block
 
+// 16-byte accesses for every array of the tensor (the chunk start is a multiple of 16384 elements, so the base decides)
+__device__ __forceinline__ bool adam_vec_ok(const AdamTensor& t) {
+  return ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
+           reinterpret_cast<uintptr_t>(t.v)) & 15) == 0 && (!t.shadow || (reinterpret_cast<uintptr_t>(t.shadow) & 7) == 0);
+}
+
+// FROM_RECORD = false: step size, bias correction and gradient scale arrive by value (xvit_adam_step).  true: they are read from the
+// device-resident record the step prologue wrote (xvit_adam_step_dev), so a captured launch follows the step count, the learning rate
+// and the clip coefficient of each replay; a step the prologue flagged as skipped returns before touching anything.
+template <bool FROM_RECORD>
 __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict__ table, const int2* __restrict__ chunks, float lr_over_bc1,
-                                                   float beta1, float beta2, float eps, float wd, float inv_sqrt_bc2, float grad_scale) {
+                                                   float beta1, float beta2, float eps, float wd, float inv_sqrt_bc2, float grad_scale,
+                                                   const xvit_adam_state* __restrict__ st) {
+  if constexpr (FROM_RECORD) {
+    if (st->skip) return;
+    lr_over_bc1 = st->lr_over_bc1;
+    inv_sqrt_bc2 = st->inv_sqrt_bc2;
+    grad_scale = st->clip_coef;
+  }
   const int2 ch = chunks[blockIdx.x];
   const AdamTensor t = table[ch.x];
   const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
   const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
-  const bool vec = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
-                     reinterpret_cast<uintptr_t>(t.v)) & 15) == 0 && (!t.shadow || (reinterpret_cast<uintptr_t>(t.shadow) & 7) == 0);
+  const bool vec = adam_vec_ok(t);
   auto upd = [&](float& p, float g, float& m, float& v) {
     g = g * grad_scale + wd * p;
     m = beta1 * m + (1.0f - beta1) * g;
@@ -515,6 +531,70 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict_
     }
   }
 }
+
+// Sum of g*g over one 16384-element chunk per block, written with ONE plain store to partials[blockIdx.x]: no float atomics, so the
+// norm is bit-identical from run to run.  Summation order per chunk (all fp32, the products fused into the adds): 16-byte path: four
+// accumulators per thread, 16 sequential adds each, 2 adds to join them; scalar path: 64 sequential adds; then 6 levels across the
+// wave and 3 adds across the four waves.  With non-negative terms that is a relative error of at most (64 + 6 + 3 + 1) * 2^-24 = 4.4e-6.
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const AdamTensor* __restrict__ table, const int2* __restrict__ chunks, float* __restrict__ partials) {
+  __shared__ float wave_part[4];
+  const int2 ch = chunks[blockIdx.x];
+  const AdamTensor t = table[ch.x];
+  const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
+  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  if (adam_vec_ok(t)) {
+#pragma unroll 4
+    for (int64_t i = begin + threadIdx.x * 4; i + 3 < end; i += 256 * 4) {
+      const f32x4 g = *(const f32x4*)(t.g + i);
+      a0 = fmaf(g[0], g[0], a0); a1 = fmaf(g[1], g[1], a1); a2 = fmaf(g[2], g[2], a2); a3 = fmaf(g[3], g[3], a3);
+    }
+    const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
+    for (int64_t i = tail + threadIdx.x; i < end; i += 256) a0 = fmaf(t.g[i], t.g[i], a0);
+  } else {
+#pragma unroll 4
+    for (int64_t i = begin + threadIdx.x; i < end; i += 256) a0 = fmaf(t.g[i], t.g[i], a0);
+  }
+  const float w = wave_sum((a0 + a1) + (a2 + a3));   // every lane of every wave gets here: the DPP steps need the full wave
+  if (lane_id() == 0) wave_part[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+
+// One block.  Sums the chunk partials in a fixed order in double (thread i takes i, i + 256, ...; then a fixed tree), and thread 0
+// writes the record the Adam kernel reads: norm, clip coefficient, the advanced step count and its bias corrections.
+__global__ __launch_bounds__(256) void adam_prologue_kernel(const float* __restrict__ partials, int n_partials, xvit_adam_state* __restrict__ st, float max_norm,
+                                                            float beta1, float beta2, int skip_nonfinite) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_partials; i += 256) s += (double)partials[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(part[0]);
+  float coef = 1.0f;
+  if (max_norm < INFINITY) {            // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max=1), a NaN stays a NaN
+    const float c = max_norm / (norm + 1e-6f);
+    coef = (c < 1.0f || c != c) ? c : 1.0f;
+  }
+  st->grad_norm = norm;
+  st->clip_coef = coef;
+  if (skip_nonfinite && !(fabsf(norm) < INFINITY)) {   // inf or NaN: the step did not happen
+    st->skip = 1;
+    st->skipped += 1;
+    return;
+  }
+  const int64_t step = st->step + 1;
+  st->step = step;
+  st->skip = 0;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);   // as xvit_adam_step does on the host
+  st->lr_over_bc1 = (float)((double)st->lr / bc1);
+  st->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+}
 }  // namespace xvit
 
 extern "C" int xvit_adam_step(const void* table_dev, const void* chunks_dev, int n_chunks, float lr, float beta1, float beta2, float eps,
@@ -522,9 +602,37 @@ extern "C" int xvit_adam_step(const void* table_dev, const void* chunks_dev, int
   XVIT_REQUIRE(table_dev && chunks_dev && n_chunks > 0 && step >= 1, "xvit_adam_step: bad arguments");
   XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adam_step: bad hyper-parameters");
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  hipLaunchKernelGGL(xvit::adam_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev,
-                     (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale);
+  hipLaunchKernelGGL(xvit::adam_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev,
+                     (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale, (const xvit_adam_state*)nullptr);
   return xvit::check_launch("xvit_adam_step");
+}
+
+extern "C" int xvit_grad_sqnorm_partials(const void* table_dev, const void* chunks_dev, int n_chunks, float* partials_dev, xvit_stream_t stream) {
+  XVIT_REQUIRE(table_dev && chunks_dev && partials_dev, "xvit_grad_sqnorm_partials: null table, chunk list or partials");
+  XVIT_REQUIRE(n_chunks > 0, "xvit_grad_sqnorm_partials: n_chunks=%d must be positive", n_chunks);
+  hipLaunchKernelGGL(xvit::grad_sqnorm_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev, partials_dev);
+  return xvit::check_launch("xvit_grad_sqnorm_partials");
+}
+
+extern "C" int xvit_adam_prologue(const float* partials_dev, int n_partials, xvit_adam_state* state_dev, float max_norm, float beta1, float beta2,
+                                  int skip_nonfinite, xvit_stream_t stream) {
+  XVIT_REQUIRE(state_dev, "xvit_adam_prologue: null state record");
+  XVIT_REQUIRE((partials_dev && n_partials > 0) || (!partials_dev && n_partials == 0),
+               "xvit_adam_prologue: partials and n_partials=%d must be given together (n_partials > 0) or both left out", n_partials);
+  XVIT_REQUIRE(max_norm > 0.f, "xvit_adam_prologue: max_norm must be positive (INFINITY switches clipping off)");
+  XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "xvit_adam_prologue: betas must lie in [0, 1)");
+  hipLaunchKernelGGL(xvit::adam_prologue_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials_dev, n_partials, state_dev, max_norm, beta1, beta2, skip_nonfinite);
+  return xvit::check_launch("xvit_adam_prologue");
+}
+
+extern "C" int xvit_adam_step_dev(const void* table_dev, const void* chunks_dev, int n_chunks, const xvit_adam_state* state_dev, float beta1, float beta2,
+                                  float eps, float weight_decay, xvit_stream_t stream) {
+  XVIT_REQUIRE(table_dev && chunks_dev && state_dev, "xvit_adam_step_dev: null table, chunk list or state record");
+  XVIT_REQUIRE(n_chunks > 0, "xvit_adam_step_dev: n_chunks=%d must be positive", n_chunks);
+  XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adam_step_dev: bad hyper-parameters");
+  hipLaunchKernelGGL(xvit::adam_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev,
+                     0.f, beta1, beta2, eps, weight_decay, 0.f, 0.f, state_dev);
+  return xvit::check_launch("xvit_adam_step_dev");
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""HIP-graph capture of one training step (zero-grad + weight cast + forward + loss + backward).
+"""HIP-graph capture of one training step (zero-grad + weight cast + forward + loss + backward, optionally clip + optimizer).
 
 At the reference's batch size (8 volume pairs per GPU, main_mist.py:206) the ~480 kernel launches of a step cost more
 host time (8 ms of Python + launch issue) than GPU time (~4 ms): replaying them as ONE graph launch removes the host
@@ -9,6 +9,15 @@ graph's private pool.
     step = GraphedStep(model, img_example, labels_example)   # warm-up + capture
     logits, loss = step(img, labels)                         # copies into the static inputs, replays; p.grad are filled
     optimizer.step()                                         # outside the graph
+
+or, with the optimizer inside the graph (xvit.optim.FusedAdam(capturable=True): gradient norm, clip coefficient, step count, bias
+corrections and learning rate are all device-side), the whole training step as one replay:
+
+    opt = xvit.optim.FusedAdam(model.parameters(), lr=1e-4, max_grad_norm=1.0, capturable=True)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=epochs)
+    step = GraphedStep(model, img_example, labels_example, optimizer=opt)   # trains nothing: the warm-up runs the model step only
+    logits, loss = step(img, labels)                         # replay: gradients, clip, Adam; p.grad stay the UNCLIPPED gradients
+    sched.step()                                             # the next call writes the new rate to the device before it replays
 
 Restrictions: static shapes.  Dropout (the reference trains with p = 0.1 .. 0.25, main_mist.py:71-77): the host-side seeds of the
 capture are frozen into the graph, so the step registers a device counter (xvit_set_dropout_epoch), increments it at the head of the
@@ -42,11 +51,22 @@ class GraphedStep:
     """reducer (xvit.ddp.BucketedGradReducer, optional): data-parallel runs.  The reducer's bucket views become the gradient buffers
     (weight-gradient kernels write into them, functional.GRAD_SINK) and its bucket all-reduces are captured INTO the graph, each
     forked onto the comm stream behind its last gradient and joined before the graph ends — the reference's setting (8 volume
-    pairs per GPU under DDP, main_mist.py:206, 211-218) is exactly where only the graph removes the host bound."""
+    pairs per GPU under DDP, main_mist.py:206, 211-218) is exactly where only the graph removes the host bound.
 
-    def __init__(self, model, img, labels, warmup: int = 3, reducer=None):
+    optimizer (xvit.optim.FusedAdam(capturable=True), optional): its launches are appended to the capture, behind reducer.finish() when
+    there is a reducer (the clipped norm is that of the averaged gradients, the same on every rank).  Construction leaves parameters,
+    moments and step count untouched: the warm-up runs the model step alone, and a capture executes nothing."""
+
+    def __init__(self, model, img, labels, warmup: int = 3, reducer=None, optimizer=None):
         if not img.is_cuda:
             raise RuntimeError("GraphedStep needs GPU tensors")
+        if optimizer is not None:
+            from .optim import FusedAdam
+            if not (isinstance(optimizer, FusedAdam) and optimizer.capturable):
+                raise RuntimeError("GraphedStep: only xvit.optim.FusedAdam(..., capturable=True) can run inside the graph (any other optimizer's step "
+                                   f"keeps host-side numbers or allocates); got {type(optimizer).__name__}"
+                                   + ("(capturable=False)" if isinstance(optimizer, FusedAdam) else "") + ". Leave optimizer=None and step it after the replay")
+        self.optimizer = optimizer
         # dropout active anywhere in the step: a device-side epoch makes every replay draw new masks (module docstring)
         self._epoch = torch.zeros(1, dtype=torch.int64, device=img.device) if model.training and _has_dropout(model) else None
         if os.environ.get("XVIT_FANOUT", "1") != "1" and os.environ.get("XVIT_GRAPH_STREAMS", "1") == "1":
@@ -85,6 +105,8 @@ class GraphedStep:
             torch.cuda.synchronize(img.device)
             if reducer is not None:
                 reducer.drain()                    # no warm-up collective may still be polled by the RCCL watchdog during the capture
+            if optimizer is not None:
+                optimizer.prepare()                # device tables sized by the parameters the warm-up gave a gradient (allocates: before the capture)
             self.graph = torch.cuda.CUDAGraph()
             for p in self.params:
                 p.grad = None                      # gradients are (re)allocated from the graph's private pool
@@ -92,12 +114,16 @@ class GraphedStep:
             try:
                 with torch.cuda.graph(self.graph):
                     self.logits, self.loss = self._eager(zero=False)
+                    if optimizer is not None:
+                        optimizer.enqueue()        # norm, prologue, Adam: serial nodes at the end of the capture stream
             finally:
                 XF.arena_reset()
                 XF.release_capture_keep()         # tensors that crossed streams were kept alive up to here (functional.keep)
             if reducer is not None:
                 for p in self.params:              # from now on p.grad IS the bucket view the graph's collectives reduce in place
                     p.grad = reducer._view_of[id(p)]
+            if optimizer is not None:
+                optimizer.rebind()                 # the tables are read at replay time: point them at the gradient buffers the capture allocated
             self._grads = [p.grad for p in self.params]   # static buffers of the graph: handed back at every call (zero_grad(set_to_none=True) drops them)
             # the graph holds raw addresses: remember where the parameters (and the flat weight buffers) live
             self._ptrs = [p.data_ptr() for p in self.params]
@@ -153,6 +179,9 @@ class GraphedStep:
         if any(p.data_ptr() != q for p, q in zip(self.params, self._ptrs)) or getattr(self.model, "_flat", None) is not self._flat:
             raise RuntimeError("GraphedStep: the model's parameter storage changed after capture (model.to(...), a re-built flat weight buffer): "
                                "the captured graph would keep training the old buffers; build a new GraphedStep")
+        if self.optimizer is not None:
+            self.optimizer.check_addresses(grads=False)    # the graph owns the gradient buffers; the optimizer's parameters must not have moved
+            self.optimizer.sync_lr()
         if img is not None:
             self.img.copy_(img, non_blocking=True)
         if labels is not None:
@@ -160,4 +189,6 @@ class GraphedStep:
         self.graph.replay()
         for p, g in zip(self.params, self._grads):
             p.grad = g
+        if self.optimizer is not None:
+            self.optimizer.mark_updated()          # no Python step() ran: mark / drop the bf16 operand copies the replay made stale
         return self.logits, self.loss

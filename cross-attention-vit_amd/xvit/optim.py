@@ -5,23 +5,71 @@ by the same kernel (so `FlatWeights.refresh` has nothing to re-cast after a step
 
     opt = xvit.optim.FusedAdam(model.parameters(), lr=1e-4, weight_decay=0.0)
     ... loss.backward(); opt.step(); opt.zero_grad()
+
+Three keyword-only options, all off by default (without them `step()` runs exactly the launches it always ran):
+
+`max_grad_norm=c`: global-norm gradient clipping fused into the step, `torch.nn.utils.clip_grad_norm_(params, c)` followed by Adam:
+one extra read of the gradients (per-chunk sums of squares, fixed order, no atomics: bit-identical from run to run), a one-block
+prologue that turns them into the norm and the clip coefficient on the device, and the Adam kernel multiplies every gradient by that
+coefficient in registers.  The norm runs over all parameter groups together.  UNLIKE `clip_grad_norm_`, `p.grad` IS NOT RESCALED IN
+MEMORY: it stays the unclipped gradient (that saves a read-modify-write pass over all gradients); `opt.last_grad_norm` is the
+pre-clip norm as a 0-dim device tensor (reading it is the caller's synchronisation).
+
+`capturable=True`: nothing about a step is a host number any more.  The tensor tables, the per-group step count, the learning rate,
+the bias corrections and the clip coefficient live on the device; they are built once (at the first `step()`, or `prepare()`, from
+the parameters that have a gradient then) and after that `step()` allocates nothing, copies nothing and synchronises nothing: it
+enqueues the norm, prologue and Adam launches on the current stream, so it can be captured into a HIP graph (`torch.cuda.graph`, or
+`xvit.graph.GraphedStep(..., optimizer=opt)` for the whole training step).  The graph holds addresses: parameters and gradients must stay
+where they were (`zero_grad(set_to_none=False)` in an eager loop), which `step()` checks.  The learning rate is the one hyper-parameter
+that may change after a capture: `sync_lr()` writes `group["lr"]` into the device record when it differs from what is there, so any
+torch scheduler works; betas, eps, weight decay and max_grad_norm are frozen into a captured launch.
+
+`skip_nonfinite=True` (needs `capturable=True`: only a device-side step count can stand still without a synchronisation): a step whose
+gradient norm is inf or NaN changes no parameter, no moment and not the step count; `opt.skipped_steps` counts them on the device.
 """
 from __future__ import annotations
+
+import math
+import weakref
 
 import numpy as np
 import torch
 
 from . import _lib
 from . import functional as XF
+from . import ops
 
 CHUNK = 16384
+# struct xvit_adam_state (include/xvit.h) as 6 int64 words / 12 fp32 words
+_REC_WORDS = 6
+_REC_DTYPE = np.dtype([("step", "<i8"), ("skipped", "<i8"), ("lr", "<f4"), ("grad_norm", "<f4"), ("clip_coef", "<f4"), ("lr_over_bc1", "<f4"),
+                       ("inv_sqrt_bc2", "<f4"), ("skip", "<i4"), ("reserved", "<i4", (2,))])
+_F_LR, _F_NORM = 4, 5          # fp32 word index of lr / grad_norm
+assert _REC_DTYPE.itemsize == 8 * _REC_WORDS
+
+
+class _Entry:
+    """The static launch arguments of one parameter group in capturable mode."""
+    __slots__ = ("gi", "params", "idx", "table", "chunks", "n_chunks", "off", "p_ptrs", "g_ptrs", "rec", "lr_view", "lr")
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *, max_grad_norm=None, capturable=False,
+                 skip_nonfinite=False):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameter")
+        if max_grad_norm is not None and not (max_grad_norm > 0 and math.isfinite(max_grad_norm)):
+            raise ValueError(f"max_grad_norm must be a positive finite number or None, got {max_grad_norm!r}")
+        if skip_nonfinite and not capturable:
+            raise ValueError("skip_nonfinite=True needs capturable=True (the step count has to live on the device to stand still without a sync)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.capturable = bool(capturable)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.lr_copies = 0            # how many times sync_lr() wrote a learning rate to the device
+        self._entries = None          # capturable mode: built by prepare()
+        self._records = self._partials = self._last_norm = None
+        self._touched, self._unshadowed = [], []
 
     @staticmethod
     def _shadow_of(p):
@@ -31,33 +79,73 @@ class FusedAdam(torch.optim.Optimizer):
                 return grp, grp.view16[i]
         return None, None
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = _lib.load()
-        touched, unshadowed = set(), []
+    @staticmethod
+    def _validate(p):
+        if not p.is_cuda or p.dtype != torch.float32 or p.grad.dtype != torch.float32 or p.grad.is_sparse:
+            raise RuntimeError("xvit FusedAdam: parameters and gradients must be dense fp32 tensors on the GPU")
+        if not p.is_contiguous():
+            raise RuntimeError("xvit FusedAdam: non-contiguous parameter")
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if not st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st
+
+    @property
+    def _needs_norm(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def last_grad_norm(self):
+        """Total L2 norm of the last step's gradients before clipping: 0-dim fp32 device tensor (no sync here), or None when the
+        optimizer takes no norm (neither max_grad_norm nor skip_nonfinite) or has not stepped yet."""
+        return self._last_norm
+
+    @property
+    def skipped_steps(self):
+        """Number of steps skip_nonfinite dropped: 0-dim int64 device tensor (capturable mode after the first step), else None."""
+        return None if self._entries is None else self._records[0, 1]
+
+    def _describe(self, e, i):
+        names = self.param_groups[e.gi].get("param_names")
+        p = e.params[i]
+        return f"parameter {e.idx[i]} of group {e.gi}" + (f" ({names[e.idx[i]]})" if names else "") + f", shape {tuple(p.shape)}"
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # host bookkeeping after the kernels wrote the parameters
+    # ------------------------------------------------------------------------------------------------------------------------
+    def mark_updated(self):
+        """Host bookkeeping that belongs to a step, without launching anything (xvit.graph.GraphedStep calls it after a replay, when no
+        Python step() ran).  The kernel rewrote p in place through raw pointers (no version bump) AND its bf16 copy: the flat weight
+        groups are marked fresh; every other parameter (ModelVIT, the model.py Encoder, stand-alone modules, XVIT_FLAT_WEIGHTS=0) keeps
+        a per-parameter bf16 copy keyed by the version counter, which a raw-pointer write does not move, so those copies are dropped."""
+        for ref in self._touched:
+            grp = ref()
+            if grp is not None:
+                grp.stamp = sum(q._version for q in grp.params)
+        XF.SHADOWS.drop(self._unshadowed)
+        self._opt_called = True       # what torch's lr_scheduler checks before its first step(): a replayed step counts as one
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # eager mode: tables per step, as the step count is kept per parameter on the host
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _step_eager(self, lib):
+        touched, unshadowed, launches = {}, [], []
         for group in self.param_groups:
             buckets, keep = {}, []          # step count -> (rows, chunks): torch keeps the step per parameter
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                if not p.is_cuda or p.dtype != torch.float32 or p.grad.dtype != torch.float32 or p.grad.is_sparse:
-                    raise RuntimeError("xvit FusedAdam: parameters and gradients must be dense fp32 tensors on the GPU")
-                if not p.is_contiguous():
-                    raise RuntimeError("xvit FusedAdam: non-contiguous parameter")
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                self._validate(p)
+                st = self._state_of(p)
                 st["step"] += 1
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 grp, sh = self._shadow_of(p)
                 if grp is not None:
-                    touched.add(id(grp))
+                    touched[id(grp)] = grp
                 else:
                     unshadowed.append(p)
                 keep.append(g)
@@ -66,19 +154,221 @@ class FusedAdam(torch.optim.Optimizer):
                 rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                              sh.data_ptr() if sh is not None else 0, p.numel()))
                 chunks.extend((t, c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
-            b1, b2 = group["betas"]
-            for step, (rows, chunks) in buckets.items():
+            launches.extend((group, step, rows, chunks, keep) for step, (rows, chunks) in buckets.items())
+        if self.max_grad_norm is None:
+            for group, step, rows, chunks, _ in launches:
+                b1, b2 = group["betas"]
                 dev = group["params"][0].device
                 table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev, non_blocking=True)
                 chunk_t = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev, non_blocking=True)
                 _lib.check(lib.xvit_adam_step(table.data_ptr(), chunk_t.data_ptr(), len(chunks), float(group["lr"]), b1, b2, group["eps"],
                                               group["weight_decay"], step, 1.0, torch.cuda.current_stream().cuda_stream), "xvit_adam_step")
                 table.record_stream(torch.cuda.current_stream()); chunk_t.record_stream(torch.cuda.current_stream())
-        # the kernel rewrote p in place through raw pointers (no version bump) AND its bf16 copy: mark the flat groups fresh
-        for grp in XF.SHADOWS.groups:
-            if id(grp) in touched:
-                grp.stamp = sum(q._version for q in grp.params)
-        # ... and every other parameter (ModelVIT, the model.py Encoder, stand-alone modules, XVIT_FLAT_WEIGHTS=0) only in place:
-        # their per-parameter bf16 copies are keyed by the version counter, which a raw-pointer write does not move
-        XF.SHADOWS.drop(unshadowed)
+        elif launches:
+            # norm over ALL groups and step buckets -> one prologue per bucket (its own step count and learning rate) -> Adam
+            dev = launches[0][0]["params"][0].device
+            cur = torch.cuda.current_stream()
+            rec = np.zeros(len(launches), dtype=_REC_DTYPE)
+            rec["step"] = [step - 1 for _, step, _, _, _ in launches]          # the prologue advances it
+            rec["lr"] = [group["lr"] for group, _, _, _, _ in launches]
+            records = torch.from_numpy(rec.view(np.int64).reshape(-1, _REC_WORDS)).to(dev, non_blocking=True)
+            total = sum(len(chunks) for _, _, _, chunks, _ in launches)
+            partials = torch.empty(total, dtype=torch.float32, device=dev)
+            tables, off = [], 0
+            for _, _, rows, chunks, _ in launches:
+                table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev, non_blocking=True)
+                chunk_t = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev, non_blocking=True)
+                _lib.check(lib.xvit_grad_sqnorm_partials(table.data_ptr(), chunk_t.data_ptr(), len(chunks), partials.data_ptr() + 4 * off,
+                                                         cur.cuda_stream), "xvit_grad_sqnorm_partials")
+                tables.append((table, chunk_t))
+                off += len(chunks)
+            for k, ((group, _, _, chunks, _), (table, chunk_t)) in enumerate(zip(launches, tables)):
+                b1, b2 = group["betas"]
+                state_ptr = records.data_ptr() + 8 * _REC_WORDS * k
+                _lib.check(lib.xvit_adam_prologue(partials.data_ptr(), total, state_ptr, self.max_grad_norm, b1, b2, 0, cur.cuda_stream), "xvit_adam_prologue")
+                _lib.check(lib.xvit_adam_step_dev(table.data_ptr(), chunk_t.data_ptr(), len(chunks), state_ptr, b1, b2, group["eps"],
+                                                  group["weight_decay"], cur.cuda_stream), "xvit_adam_step_dev")
+                table.record_stream(cur); chunk_t.record_stream(cur)
+            records.record_stream(cur); partials.record_stream(cur)
+            self._last_norm = records[0].view(torch.float32)[_F_NORM]
+        self._touched = [weakref.ref(g) for g in touched.values()]
+        self._unshadowed = unshadowed
+        self.mark_updated()
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # capturable mode: everything built once
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _rows_of(self, e):
+        rows = []
+        for p in e.params:
+            st = self.state[p]
+            _, sh = self._shadow_of(p)
+            rows.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                         sh.data_ptr() if sh is not None else 0, p.numel()))
+        return rows
+
+    @torch.no_grad()
+    def prepare(self):
+        """capturable=True: build the device tables, chunk lists, norm partials and state records from the parameters that have a
+        gradient NOW (allocation + host-to-device copies: not capturable, so call it, or take one eager step, before a capture).
+        Later calls do nothing."""
+        if not self.capturable:
+            raise RuntimeError("xvit FusedAdam.prepare: only for capturable=True")
+        if self._entries is not None:
+            return
+        entries, touched, unshadowed, off = [], {}, [], 0
+        for gi, group in enumerate(self.param_groups):
+            e = _Entry()
+            e.gi, e.params, e.idx = gi, [], []
+            chunks, steps = [], set()
+            for i, p in enumerate(group["params"]):
+                if p.grad is None:
+                    continue
+                self._validate(p)
+                if not p.grad.is_contiguous():
+                    raise RuntimeError("xvit FusedAdam(capturable=True): non-contiguous gradient")
+                steps.add(int(self._state_of(p)["step"]))
+                grp, _ = self._shadow_of(p)
+                if grp is not None:
+                    touched[id(grp)] = grp
+                else:
+                    unshadowed.append(p)
+                chunks.extend((len(e.params), c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
+                e.params.append(p); e.idx.append(i)
+            if not e.params:
+                continue
+            if len(steps) != 1:
+                raise ValueError(f"xvit FusedAdam(capturable=True) keeps one step count per parameter group; group {gi} holds parameters at steps {sorted(steps)}")
+            dev = e.params[0].device
+            e.lr = float(group["lr"])
+            e.n_chunks, e.off = len(chunks), off
+            off += len(chunks)
+            e.chunks = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev)
+            e.table = torch.empty(len(e.params), 6, dtype=torch.int64, device=dev)
+            entries.append((e, steps.pop()))
+        if not entries:
+            raise RuntimeError("xvit FusedAdam.prepare: no parameter has a gradient yet (run one backward, or set the static .grad buffers, first)")
+        rec = np.zeros(len(entries), dtype=_REC_DTYPE)
+        rec["step"] = [step for _, step in entries]
+        rec["lr"] = [e.lr for e, _ in entries]
+        dev = entries[0][0].table.device
+        self._records = torch.from_numpy(rec.view(np.int64).reshape(-1, _REC_WORDS)).to(dev)
+        self._partials = torch.empty(off, dtype=torch.float32, device=dev) if self._needs_norm else None
+        for k, (e, _) in enumerate(entries):
+            e.rec = self._records[k]
+            e.lr_view = e.rec.view(torch.float32)[_F_LR]
+        self._entries = [e for e, _ in entries]
+        self._last_norm = self._records[0].view(torch.float32)[_F_NORM] if self._needs_norm else None
+        self._touched = [weakref.ref(g) for g in touched.values()]
+        self._unshadowed = unshadowed
+        self.rebind()
+
+    @torch.no_grad()
+    def rebind(self):
+        """Re-read the addresses of the parameters, their CURRENT .grad tensors and bf16 copies into the existing device tables (a
+        host-to-device copy: outside any capture).  The launches hold only the tables' own addresses, so a graph captured before stays
+        valid: xvit.graph.GraphedStep captures the step first and binds the gradient buffers the capture allocated afterwards."""
+        for e in self._entries:
+            for i, p in enumerate(e.params):
+                if p.grad is None or p.grad.shape != p.shape or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
+                    raise RuntimeError(f"xvit FusedAdam.rebind: {self._describe(e, i)} has no dense contiguous fp32 gradient to bind")
+            rows = self._rows_of(e)
+            e.table.copy_(torch.from_numpy(np.asarray(rows, dtype=np.int64)))
+            e.p_ptrs = [r[0] for r in rows]
+            e.g_ptrs = [r[1] for r in rows]
+
+    def check_addresses(self, grads: bool = True):
+        """capturable mode: every parameter (and, with grads=True, its .grad) still lives at the address in the device table."""
+        for e in self._entries or ():
+            for i, p in enumerate(e.params):
+                if p.data_ptr() != e.p_ptrs[i]:
+                    raise RuntimeError(f"xvit FusedAdam(capturable=True): the storage of {self._describe(e, i)} moved after the tables were built "
+                                       "(model.to(...), a re-built flat weight buffer); build a new optimizer")
+                if grads and (p.grad is None or p.grad.data_ptr() != e.g_ptrs[i]):
+                    raise RuntimeError(f"xvit FusedAdam(capturable=True): the gradient of {self._describe(e, i)} is no longer the tensor the device table "
+                                       "points to (typically zero_grad(set_to_none=True) in an eager loop, which makes backward allocate a new one): "
+                                       "use zero_grad(set_to_none=False), or xvit.graph.GraphedStep(..., optimizer=opt), which owns static gradient buffers")
+
+    def sync_lr(self):
+        """Write group["lr"] into the device record of every group whose rate changed since the last call (one tiny asynchronous fill
+        on the current stream, value passed as a kernel argument: no host buffer to keep alive); nothing is issued otherwise.  step()
+        calls it in eager mode, GraphedStep before each replay; call it yourself before replaying your own capture of step()."""
+        for e in self._entries or ():
+            lr = float(self.param_groups[e.gi]["lr"])
+            if lr != e.lr:
+                e.lr_view.fill_(lr)
+                e.lr = lr
+                self.lr_copies += 1
+
+    def enqueue(self):
+        """capturable mode: the launches of one step on the current stream and nothing else (no check, no bookkeeping)."""
+        lib = _lib.load()
+        stream = ops._stream()
+        if self._partials is not None:
+            for e in self._entries:
+                _lib.check(lib.xvit_grad_sqnorm_partials(e.table.data_ptr(), e.chunks.data_ptr(), e.n_chunks, self._partials.data_ptr() + 4 * e.off, stream),
+                           "xvit_grad_sqnorm_partials")
+        part, n_part = (self._partials.data_ptr(), self._partials.numel()) if self._partials is not None else (None, 0)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else math.inf
+        for e in self._entries:
+            group = self.param_groups[e.gi]
+            b1, b2 = group["betas"]
+            _lib.check(lib.xvit_adam_prologue(part, n_part, e.rec.data_ptr(), max_norm, b1, b2, int(self.skip_nonfinite), stream), "xvit_adam_prologue")
+            _lib.check(lib.xvit_adam_step_dev(e.table.data_ptr(), e.chunks.data_ptr(), e.n_chunks, e.rec.data_ptr(), b1, b2, group["eps"],
+                                              group["weight_decay"], stream), "xvit_adam_step_dev")
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if not self.capturable:
+            self._step_eager(_lib.load())
+            return loss
+        self.prepare()
+        self.check_addresses()
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()
+        self.enqueue()
+        self.mark_updated()
         return loss
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # state_dict: torch's key names in both modes
+    # ------------------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """exp_avg / exp_avg_sq / step per parameter, as torch.optim.Adam names them.  In capturable mode `step` is read from the
+        device counters here (a synchronisation)."""
+        if self._entries is not None:
+            steps = self._records[:, 0].tolist()
+            for e, step in zip(self._entries, steps):
+                for p in e.params:
+                    self.state[p]["step"] = int(step)
+        return super().state_dict()
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Accepts a state dict of either mode (or of torch.optim.Adam).  Once the capturable tables exist, the values are copied INTO the
+        existing moment buffers and device counters, so a captured graph stays valid."""
+        old = {p: self.state[p] for e in self._entries or () for p in e.params}
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if "step" in st:
+                st["step"] = int(st["step"])
+        for k, e in enumerate(self._entries or ()):
+            steps = set()
+            for i, p in enumerate(e.params):
+                new = self.state.get(p)
+                if not new or "exp_avg" not in new:
+                    raise ValueError(f"xvit FusedAdam.load_state_dict: no state for {self._describe(e, i)}, which the capturable tables hold")
+                keep = old[p]
+                keep["exp_avg"].copy_(new["exp_avg"])
+                keep["exp_avg_sq"].copy_(new["exp_avg_sq"])
+                keep["step"] = new["step"]
+                steps.add(new["step"])
+                self.state[p] = keep
+            if len(steps) != 1:
+                raise ValueError(f"xvit FusedAdam(capturable=True) keeps one step count per parameter group; the loaded state has steps {sorted(steps)} in group {e.gi}")
+            self._records[k, 0].fill_(steps.pop())

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 307 /* 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 308 /* 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1 };
@@ -367,6 +367,40 @@ int xvit_cu_trace(uint32_t* out, int nblocks, int linger_us, xvit_stream_t strea
 #define XVIT_ADAM_CHUNK 16384
 int xvit_adam_step(const void* table_dev, const void* chunks_dev, int n_chunks, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, float grad_scale, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same step with every per-step number on the device, so that its three launches can be captured into a graph and replayed:
+ * gradient norm -> prologue -> Adam.  Same table_dev / chunks_dev as above; nothing here allocates, copies or synchronises.
+ *
+ * xvit_grad_sqnorm_partials: partials_dev[i] = sum of g*g over chunk i (fp32, fixed summation order, one plain store per block, no
+ *   atomics: bit-identical from run to run).  partials_dev holds n_chunks floats.  Several tables may fill disjoint ranges of one
+ *   partials array; the prologue then sees the norm over all of them.
+ * xvit_adam_prologue (one block): sums partials_dev[0 .. n_partials) in index order in double and updates *state_dev:
+ *   grad_norm = sqrt(sum);  clip_coef = min(1, max_norm / (grad_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; exactly 1 under the limit,
+ *   and with max_norm = INFINITY, which switches clipping off);  step += 1;  lr_over_bc1 = lr / (1 - beta1^step) and
+ *   inv_sqrt_bc2 = 1 / sqrt(1 - beta2^step) in double from the record's own `lr`, which the host writes whenever the learning rate changes.
+ *   skip_nonfinite != 0: an inf / NaN norm leaves `step` alone, sets `skip` and increments `skipped`; a finite one clears `skip`.
+ *   partials_dev = NULL with n_partials = 0: no norm was taken (grad_norm = 0, clip_coef = 1).
+ * xvit_adam_step_dev: the update of the by-value entry point with lr / bias corrections / gradient scale (= clip_coef) read from *state_dev;
+ *   returns without writing anything when `skip` is set.  The gradients are scaled in registers: g in memory stays unclipped.
+ * A caller zero-fills the record, sets `lr`, and keeps one record per parameter group (one step count per group).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct xvit_adam_state {
+  int64_t step;       /* steps taken so far */
+  int64_t skipped;    /* steps skipped because the gradient norm was not finite */
+  float lr;           /* written by the host */
+  float grad_norm;    /* total L2 norm of the gradients of this step, before clipping */
+  float clip_coef;
+  float lr_over_bc1;
+  float inv_sqrt_bc2;
+  int32_t skip;       /* this step is skipped */
+  int32_t reserved[2];
+} xvit_adam_state;    /* 48 bytes */
+int xvit_grad_sqnorm_partials(const void* table_dev, const void* chunks_dev, int n_chunks, float* partials_dev, xvit_stream_t stream);
+int xvit_adam_prologue(const float* partials_dev, int n_partials, xvit_adam_state* state_dev, float max_norm, float beta1, float beta2,
+                       int skip_nonfinite, xvit_stream_t stream);
+int xvit_adam_step_dev(const void* table_dev, const void* chunks_dev, int n_chunks, const xvit_adam_state* state_dev, float beta1, float beta2,
+                       float eps, float weight_decay, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * bf16 wire format of the data-parallel gradient reducer (xvit/ddp.py, comm_dtype=torch.bfloat16; the counterpart of DDP's
