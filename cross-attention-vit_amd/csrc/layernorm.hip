@@ -264,8 +264,18 @@ extern "C" int xvit_layernorm_bwd(const void* dy, int64_t lddy, const float* x, 
     hipLaunchKernelGGL((ln_bwd_kernel<3>), grid, block, lds, s, dyb, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx, dxbb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
   else if (d <= 1024)
     hipLaunchKernelGGL((ln_bwd_kernel<4>), grid, block, lds, s, dyb, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx, dxbb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
-  else
+  else {
+    // 32 d bytes of dynamic LDS: over the 64 KiB a kernel may ask for by default once d > 2048 (128 KiB at d = 4096, one block per CU
+    // as this instance's launch bounds already assume), so the instance's limit is raised before such a launch
+    static size_t attr = 0;
+    if (lds > 64 * 1024 && lds > attr) {
+      const hipError_t e = hipFuncSetAttribute((const void*)ln_bwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      XVIT_REQUIRE(e == hipSuccess, "xvit_layernorm_bwd: d=%d needs %lld bytes of LDS and the kernel's limit could not be raised (%s)", d, (long long)lds,
+                   hipGetErrorString(e));
+      attr = lds;
+    }
     hipLaunchKernelGGL((ln_bwd_kernel<16>), grid, block, lds, s, dyb, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx, dxbb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
+  }
   if (workspace) {
     // without dxsum / dressum the kernel skips round 1: those slices of the workspace are never read either
     hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((d + 255) / 256), dim3(256), 0, s, workspace, dgamma, dbeta, dxsum, dressum, g, d);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """LayerNorm forward / backward at the step's shapes (rows = 126 x 513, d = 768), GB/s of algorithmic bytes.
-    [XVIT_LIB=other.so] python tools/ln_bench.py"""
+    [XVIT_LIB=other.so] python tools/ln_bench.py [batch [d]]"""
 import os
 import sys
 
@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(ROOT, "cross-attention-vit_amd"))
 from xvit import ops  # noqa: E402
 
 dev = torch.device("cuda:0")
-rows, d = (int(sys.argv[1]) if len(sys.argv) > 1 else 126) * 513, 768
+rows, d = (int(sys.argv[1]) if len(sys.argv) > 1 else 126) * 513, int(sys.argv[2]) if len(sys.argv) > 2 else 768
 x = torch.randn(rows, d, device=dev)
 g, b = torch.randn(d, device=dev), torch.randn(d, device=dev)
 dy = torch.randn(rows, d, device=dev).bfloat16()
