@@ -13,6 +13,7 @@
 // backward recomputes P from the saved log-sum-exp.  dQ and dK/dV are separate kernels, so no
 // atomics and bit-reproducible gradients.
 #include <atomic>
+#include <type_traits>
 
 #include "xvit_common.h"
 
@@ -25,7 +26,6 @@ namespace xvit {
 constexpr int DH = 64;          // head dim
 constexpr int TILE_ROWS = 64;   // streamed rows per iteration
 constexpr int IMG_BYTES = TILE_ROWS * DH * 2;  // 8 KiB
-constexpr float LOG2E = 1.4426950408889634f;
 #ifndef XVIT_FWD_NST
 #define XVIT_FWD_NST 2
 #endif
@@ -121,36 +121,45 @@ __device__ __forceinline__ void settle(bf16x8 (&f)[4]) {
   }
 }
 
-// Workgroups are dealt to the 8 XCDs round-robin in dispatch order (x fastest), each XCD with its own L2.
-// Remap the linear id so that a contiguous range of LOGICAL ids runs on one XCD: the query (or key) blocks of
-// one (batch, head) then share an L2 and its K/V (Q/dO) tiles are fetched from HBM once, not once per XCD
-// (measured before the remap: 350-390 MB fetched per launch against ~100 MB of q/k/v).
-struct BlockCoord { int x, head, b; };
-__device__ __forceinline__ BlockCoord xcd_block_coord() {
-  const int nx = gridDim.x, nh = gridDim.y, total = nx * nh * gridDim.z;
-  const int lin = blockIdx.x + nx * (blockIdx.y + nh * blockIdx.z);
-  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (lin >> 3);
-  BlockCoord c;
-  c.x = logical % nx;
-  const int rest = logical / nx;
-  c.head = rest % nh;
-  c.b = rest / nh;
-  return c;
-}
-
-// counted wait on the vector-memory counter (the LDS-DMA ring: "at most N loads still in flight")
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// top-of-iteration wait of an NST-deep ring whose waves issue PT DMA instructions per tile: tile t must have
-// landed, the (up to NST-2) younger tiles may stay in flight
-template <int NST, int PT>
-__device__ __forceinline__ void ring_wait(int t, int ntiles) {
-  const int ahead = min(NST - 2, ntiles - 1 - t);
-  if (NST >= 4 && ahead == 2) wait_vmcnt<2 * PT>();
-  else if (NST >= 3 && ahead >= 1) wait_vmcnt<PT>();
-  else wait_vmcnt<0>();
-}
+// The streamed tiles of all three kernels go through an NST-deep ring of STAGE_BYTES LDS stages, filled by LDS-DMA.  Loads stay in
+// flight ACROSS iterations.  INVARIANT: `issue(stage pointer, iteration)`, a lambda of the kernel, makes EVERY wave issue EXACTLY PT
+// DMA instructions, so "tile t has landed, the (up to NST - 2) younger tiles may still be in flight" is a counted s_waitcnt vmcnt;
+// barriers are raw s_barrier (a __syncthreads() would drain vmcnt to 0 and serialise every iteration behind a full HBM/L2 round trip).
+template <int NST, int STAGE_BYTES, int PT>
+struct TileRing {
+  XVIT_LDS char* base;
+  int stage;
+  __device__ __forceinline__ XVIT_LDS char* at(int st) const { return base + st * STAGE_BYTES; }
+  // the first NST - 1 tiles
+  template <class Issue>
+  __device__ __forceinline__ void prologue(XVIT_LDS char* smem, int ntiles, const Issue& issue) {
+    base = smem;
+    stage = 0;
+#pragma unroll
+    for (int st = 0; st < NST - 1; ++st)
+      if (st < ntiles) issue(at(st), st);
+  }
+  // top of iteration t: afterwards every wave's pieces of tile t are in LDS and every wave is done with tile t-1
+  __device__ __forceinline__ void wait(int t, int ntiles) const {
+    const int ahead = min(NST - 2, ntiles - 1 - t);
+    if (NST >= 4 && ahead == 2) wait_vmcnt<2 * PT>();
+    else if (NST >= 3 && ahead >= 1) wait_vmcnt<PT>();
+    else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+  }
+  // behind wait(): tile t + NST - 1 goes into the stage tile t-1 has left; returns tile t's stage
+  template <class Issue>
+  __device__ __forceinline__ const XVIT_LDS char* advance(int t, int ntiles, const Issue& issue) {
+    if (t + NST - 1 < ntiles) {
+      int ns = stage + NST - 1;
+      if (ns >= NST) ns -= NST;
+      issue(at(ns), t + NST - 1);
+    }
+    const XVIT_LDS char* cur = at(stage);
+    stage = stage + 1 == NST ? 0 : stage + 1;
+    return cur;
+  }
+};
 // PEEL: workgroup x of a (b, head) walks the streamed tiles in ROTATED order, ending with the two tiles (2x, 2x+1) that hold the
 // tokens with its own row indices.  Softmax statistics and the gradient sums do not depend on the order, and after the loop
 // those two tiles are still in the ring, so each wave runs its one token-0 block (see "CLS peel" below) THERE: all four waves
@@ -182,9 +191,6 @@ constexpr int BWD_NST = XVIT_BWD_NST;      // K/V (dQ kernel) and Q/dO (dK/dV ke
                                          // Same-box A/B at N = 512..4097: depth 2, 3 and 4 are within noise (the loops are not load-latency-bound)
 
 #define ZERO16 (f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f})
-
-// element index inside a 32-row accumulator block held in register i by lane half h
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 // store a [64 d][32 rows-on-lane] accumulator pair as bf16 rows of a [*, stride_n] matrix
 __device__ __forceinline__ void store_lane_rows(const f32x16 (&acc)[2], float mul, bf16* base, int64_t stride_n, int row, bool valid, int lane) {
@@ -220,6 +226,24 @@ __device__ __forceinline__ void store_lane_rows(const f32x16 (&acc)[2], float mu
 // bit-reproducible.  The extra block is 1/16 of a wave's work at N = 513 and 1/128 at N = 4097.
 // ------------------------------------------------------------------------------------------
 constexpr int CLS_SLOT = 80;   // floats per forward partial: o[64] (unnormalised) | m (raw max) | l | pad (16-B aligned rows)
+// the partials of (b, head) bh are the G = NK / 32 consecutive wave slots g = 4 x + wave (NK = N - 1 patch tokens): index of slot g
+__host__ __device__ constexpr int64_t peel_slot(int64_t bh, int NK, int g) { return bh * (NK / 32) + g; }
+// Workspaces, in floats.  Forward: CLS_SLOT per slot.  Backward: delta | nlse, [B, H, N] each (the dQ kernel leaves them for the dK/dV
+// kernel), then (PEEL) the dQ0 | dK0 | dV0 partials, 64 per slot each.  The partials are written with 16-byte stores and N is odd
+// in the peel form: they start at the next multiple of 4 floats.
+__host__ constexpr int64_t fwd_workspace_floats(int B, int H, int N) { return peel_slot((int64_t)B * H, N - 1, 0) * CLS_SLOT; }
+struct BwdWorkspace {
+  int64_t delta, nlse, pdq, pdk, pdv, total;
+  __host__ BwdWorkspace(int B, int H, int N, bool peel) {
+    const int64_t rows = (int64_t)B * H * N, part = peel ? peel_slot((int64_t)B * H, N - 1, 0) * 64 : 0;
+    delta = 0;
+    nlse = rows;
+    pdq = peel ? (2 * rows + 3) / 4 * 4 : 2 * rows;
+    pdk = pdq + part;
+    pdv = pdk + part;
+    total = pdv + part;
+  }
+};
 
 // row `rowp` (64 bf16) as an MFMA operand whose 32 columns (B) / rows (A) all equal that row
 __device__ __forceinline__ void load_row_bcast(bf16x8 (&f)[4], const bf16* rowp, int lane) {
@@ -244,6 +268,12 @@ __device__ __forceinline__ void load_row_acc(f32x16 (&x)[2], const bf16* rowp, i
 // (lane L fetches 16-byte chunk L & 7).  A global load after the loop would expose ~1-2 us of latency per workgroup (measured:
 // 12 us of a 170 us forward, 33 us of a 540 us backward at B = 126, N = 513).
 constexpr int ROW0_BYTES = 1024;
+// dynamic LDS of the three kernels: the ring's stages, then (PEEL) the token-0 rows
+constexpr int KV_STAGE = 2 * IMG_BYTES;         // K image | V image
+constexpr int DKV_STAGE = 2 * IMG_BYTES + 512;  // Q image | dO image | nlse[64] | delta[64]  (all four arrive by LDS-DMA)
+constexpr int fwd_lds_bytes(bool peel) { return FWD_NST * KV_STAGE + (peel ? ROW0_BYTES : 0); }        // [q0]
+constexpr int dq_lds_bytes(bool peel) { return BWD_NST * KV_STAGE + (peel ? 2 * ROW0_BYTES : 0); }     // [q0 | dO0]
+constexpr int dkv_lds_bytes(bool peel) { return BWD_NST * DKV_STAGE + (peel ? 2 * ROW0_BYTES : 0); }   // [k0 | v0]
 __device__ __forceinline__ void stage_row0(XVIT_LDS char* dst, const bf16* rowp, int lane) {
   glds16(make_rsrc(rowp, 128), dst, (uint32_t)((lane & 7) * 16), 0);
 }
@@ -306,7 +336,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
   const uint64_t wc_entry = wall_clock64();
 #endif
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  XVIT_LDS char* smem = (XVIT_LDS char*)smem_raw;  // [FWD_NST stages][K image | V image]
+  XVIT_LDS char* smem = (XVIT_LDS char*)smem_raw;  // fwd_lds_bytes(PEEL)
   const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6);
   const BlockCoord bc = xcd_block_coord();
   const int b = bc.b, head = bc.head;
@@ -316,25 +346,23 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
   const int64_t off = off0 + (PEEL ? sn : 0);                        // first token of the tile grid
   const int ntiles = (NK + TILE_ROWS - 1) / TILE_ROWS;
 
-  // K/V tiles stream through a FWD_NST-deep LDS ring.  Loads stay in flight ACROSS iterations: each wave
-  // issues exactly 4 LDS-DMA instructions per tile (2 K + 2 V), so "tile t has landed, tile t+1 may still be
-  // in flight" is a counted s_waitcnt vmcnt(4); barriers are raw s_barrier (a __syncthreads() would drain
-  // vmcnt to 0 and serialise every iteration behind a full HBM/L2 round trip).
   TileLoader lk, lv;
   lk.init(k + off, sn, NK, wave, lane);
   lv.init(v + off, sn, NK, wave, lane);
   TileOrder ord;
   ord.init(PEEL, bc.x, ntiles);
-  XVIT_LDS char* row0 = smem + FWD_NST * 2 * IMG_BYTES;   // PEEL: [q0] (ROW0_BYTES)
+  XVIT_LDS char* row0 = smem + fwd_lds_bytes(false);   // PEEL: [q0]
   if constexpr (PEEL) {
     if (wave == 0) stage_row0(row0, q + off0, lane);
   }
-#pragma unroll
-  for (int st = 0; st < FWD_NST - 1; ++st)
-    if (st < ntiles) {
-      lk.issue(smem + st * 2 * IMG_BYTES, wave, ord.tile(st));
-      lv.issue(smem + st * 2 * IMG_BYTES + IMG_BYTES, wave, ord.tile(st));
-    }
+  constexpr int PT = 4;   // DMAs per wave and tile: 2 K + 2 V
+  const auto issue = [&](XVIT_LDS char* st, int it) {
+    const int tile = ord.tile(it);
+    lk.issue(st, wave, tile);
+    lv.issue(st + IMG_BYTES, wave, tile);
+  };
+  TileRing<FWD_NST, KV_STAGE, PT> ring;
+  ring.prologue(smem, ntiles, issue);
   bf16x8 qf[QB][4];
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
@@ -374,21 +402,12 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
 #else
 #define TK(i)
 #endif
-  int stage = 0;
   for (int t = 0; t < ntiles; ++t) {
     TK(0)
-    ring_wait<FWD_NST, 4>(t, ntiles);   // tile t landed; up to FWD_NST - 2 younger tiles may be in flight
-    __builtin_amdgcn_s_barrier();   // every wave's pieces of tile t are in LDS; every wave is done with tile t-1
+    ring.wait(t, ntiles);
     TK(1)
-    if (t + FWD_NST - 1 < ntiles) {
-      int ns = stage + FWD_NST - 1;
-      if (ns >= FWD_NST) ns -= FWD_NST;
-      lk.issue(smem + ns * 2 * IMG_BYTES, wave, ord.tile(t + FWD_NST - 1));
-      lv.issue(smem + ns * 2 * IMG_BYTES + IMG_BYTES, wave, ord.tile(t + FWD_NST - 1));
-    }
-    const XVIT_LDS char* kimg = smem + stage * 2 * IMG_BYTES;
+    const XVIT_LDS char* kimg = ring.advance(t, ntiles, issue);
     const XVIT_LDS char* vimg = kimg + IMG_BYTES;
-    stage = stage + 1 == FWD_NST ? 0 : stage + 1;
 
     if (!wave_active) continue;   // this wave's queries are all past N: keep moving tiles and barriers, skip the math
     // keys of this tile past N: with <= 32 valid keys the second 32-key block is skipped entirely
@@ -523,7 +542,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
   }
   if constexpr (PEEL && !(XVIT_PEEL_DEBUG & 1)) {
     if (wave_active) {   // once per wave, after the loop: the CLS query against key block cls_kb of its own tile (still in the ring), q0 in all 32 columns
-      const XVIT_LDS char* kimg = smem + ord.stage_of(cls_g, FWD_NST) * 2 * IMG_BYTES;
+      const XVIT_LDS char* kimg = ring.at(ord.stage_of(cls_g, FWD_NST));
       const XVIT_LDS char* vimg = kimg + IMG_BYTES;
       bf16x8 q0f[4];
       lds_row_bcast(q0f, row0, lane);
@@ -545,7 +564,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
 #pragma unroll
         for (int db = 0; db < 2; ++db) oc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.tr_frag(vimg, db, cls_kb, ss), pf, ss == 0 ? ZERO16 : oc[db], 0, 0, 0);
       }
-      float* slot = cls_ws + ((((int64_t)b * H + head) * (NK / 32)) + cls_g) * CLS_SLOT;
+      float* slot = cls_ws + peel_slot((int64_t)b * H + head, NK, cls_g) * CLS_SLOT;
       store_col0(oc, slot, lane);
       if (lane == 0) { slot[64] = mx; slot[65] = ps; }
     }
@@ -557,16 +576,26 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
 // ------------------------------------------------------------------------------------------
 // (133 VGPRs: three blocks per CU; squeezing it to 128 for a fourth spills and measured 6 % slower)
 // one 32-key block of the dQ recomputation: S^T = K Q^T, dP^T = V dO^T -> dS^T = P^T (dP^T - delta) -> dQ^T += K^T dS^T.  qf / dof: the
-// queries on the lanes (or, for the CLS row, q0 / dO0 repeated in every column); nlse / dlt: their row statistics
+// queries on the lanes (or, for the CLS row, q0 / dO0 repeated in every column); nlse / dlt: their row statistics.  DROP only: the
+// mask of (b, head) bh_base, this lane's query, the keys key0 + acc_row(i, h)
+template <bool DROP>
 __device__ __forceinline__ void dq_block(const ImgReader& rd, const XVIT_LDS char* kimg, const XVIT_LDS char* vimg, int kb, const bf16x8 (&qf)[4],
-                                         const bf16x8 (&dof)[4], float c, float nlse, float dlt, f32x16 (&dqacc)[2]) {
+                                         const bf16x8 (&dof)[4], float c, float nlse, float dlt, f32x16 (&dqacc)[2], const DropArgs& drop = DropArgs{},
+                                         uint64_t bh_base = 0, int query = 0, int key0 = 0, int h = 0, int N = 0) {
   f32x16 s, dp;
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(kimg, kb, ks), qf[ks], ks == 0 ? ZERO16 : s, 0, 0, 0);
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(vimg, kb, ks), dof[ks], ks == 0 ? ZERO16 : dp, 0, 0, 0);
+  // keys past N have K = V = 0 (zero-filled by the DMA), so they add nothing to dQ
 #pragma unroll
-  for (int i = 0; i < 16; ++i) s[i] = __builtin_amdgcn_exp2f(fmaf(s[i], c, nlse)) * (dp[i] - dlt);
+  for (int i = 0; i < 16; ++i) {   // (hand-packed v_pk_fma / v_pk_mul here measured 4 % slower at N = 4097: left to the compiler)
+    const float pv = __builtin_amdgcn_exp2f(fmaf(s[i], c, nlse));
+    float dpe = dp[i];
+    if constexpr (DROP)   // dP = mask / (1-p) * (dO V^T)
+      dpe = drop_keep(drop, bh_base, query, key0 + acc_row(i, h), N) ? dpe * drop.inv : 0.f;
+    s[i] = pv * (dpe - dlt);  // dS^T
+  }
 #pragma unroll
   for (int ss = 0; ss < 2; ++ss) {
     const bf16x8 dsf = acc_frag(s, ss);
@@ -575,7 +604,6 @@ __device__ __forceinline__ void dq_block(const ImgReader& rd, const XVIT_LDS cha
   }
 }
 
-// PEEL workspace (after delta | nlse): per (b, head) and wave slot g, 64 floats each of dQ0, dK0, dV0 partials
 #ifndef XVIT_DQ_PEEL_WAVES
 #define XVIT_DQ_PEEL_WAVES 4
 #endif
@@ -606,19 +634,21 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DQ_PEEL_WAVES : 2) void attn_bwd_d
   lv.init(v + off, sn, NK, wave, lane);
   TileOrder ord;
   ord.init(PEEL, bc.x, ntiles);
-  XVIT_LDS char* row0 = smem + BWD_NST * 2 * IMG_BYTES;   // PEEL: [q0 | dO0] (2 ROW0_BYTES)
+  XVIT_LDS char* row0 = smem + dq_lds_bytes(false);   // PEEL: [q0 | dO0]
   if constexpr (PEEL) {
     if (wave == 0) {
       stage_row0(row0, q + off0, lane);
       stage_row0(row0 + ROW0_BYTES, d_o + ooff0, lane);
     }
   }
-#pragma unroll
-  for (int st = 0; st < BWD_NST - 1; ++st)
-    if (st < ntiles) {
-      lk.issue(smem + st * 2 * IMG_BYTES, wave, ord.tile(st));
-      lv.issue(smem + st * 2 * IMG_BYTES + IMG_BYTES, wave, ord.tile(st));
-    }
+  constexpr int PT = 4;   // DMAs per wave and tile: 2 K + 2 V
+  const auto issue = [&](XVIT_LDS char* st, int it) {
+    const int tile = ord.tile(it);
+    lk.issue(st, wave, tile);
+    lv.issue(st + IMG_BYTES, wave, tile);
+  };
+  TileRing<BWD_NST, KV_STAGE, PT> ring;
+  ring.prologue(smem, ntiles, issue);
 
   bf16x8 qf[4], dof[4];
   load_lane_operand(qf, q + off, sn, q0, NK, lane);
@@ -680,56 +710,28 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DQ_PEEL_WAVES : 2) void attn_bwd_d
   }
   asm volatile("" : "+v"(nlse0), "+v"(dlt0));
 
-  int stage = 0;
+  const uint64_t bh_base = ((uint64_t)b * H + head) * (uint64_t)N * (uint64_t)N;   // DROP: this (b, head)'s first mask element
   for (int t = 0; t < ntiles; ++t) {
-    ring_wait<BWD_NST, 4>(t, ntiles);
-    __builtin_amdgcn_s_barrier();   // every wave's pieces of tile t are in LDS; every wave is done with tile t-1
-    if (t + BWD_NST - 1 < ntiles) {
-      int ns = stage + BWD_NST - 1;
-      if (ns >= BWD_NST) ns -= BWD_NST;
-      lk.issue(smem + ns * 2 * IMG_BYTES, wave, ord.tile(t + BWD_NST - 1));
-      lv.issue(smem + ns * 2 * IMG_BYTES + IMG_BYTES, wave, ord.tile(t + BWD_NST - 1));
-    }
-    const XVIT_LDS char* kimg = smem + stage * 2 * IMG_BYTES;
-    const XVIT_LDS char* vimg = kimg + IMG_BYTES;
-    stage = stage + 1 == BWD_NST ? 0 : stage + 1;
+    ring.wait(t, ntiles);
+    const XVIT_LDS char* kimg = ring.advance(t, ntiles, issue);
     if (!wave_active) continue;
     const int nkb = PEEL || (N - t * TILE_ROWS) > 32 ? 2 : 1;   // a tail tile with <= 32 keys needs one key block only (PEEL: 64 | NK, no tail)
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       if (kb >= nkb) break;
-      f32x16 s, dp;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(kimg, kb, ks), qf[ks], ks == 0 ? ZERO16 : s, 0, 0, 0);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(vimg, kb, ks), dof[ks], ks == 0 ? ZERO16 : dp, 0, 0, 0);
-      // keys past N have K = V = 0 (zero-filled by the DMA), so they add nothing to dQ
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {   // (hand-packed v_pk_fma / v_pk_mul here measured 4 % slower at N = 4097: left to the compiler)
-        const float pv = __builtin_amdgcn_exp2f(fmaf(s[i], c, nlse));
-        float dpe = dp[i];
-        if constexpr (DROP)   // dP = mask / (1-p) * (dO V^T)
-          dpe = drop_keep(drop, ((uint64_t)b * H + head) * (uint64_t)N * (uint64_t)N, qrow, t * TILE_ROWS + kb * 32 + acc_row(i, lane >> 5), N) ? dpe * drop.inv : 0.f;
-        s[i] = pv * (dpe - dlt);  // dS^T
-      }
-#pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
-        const bf16x8 dsf = acc_frag(s, ss);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) dqacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.tr_frag(kimg, db, kb, ss), dsf, dqacc[db], 0, 0, 0);
-      }
+      dq_block<DROP>(rd, kimg, kimg + IMG_BYTES, kb, qf, dof, c, nlse, dlt, dqacc, drop, bh_base, qrow, t * TILE_ROWS + kb * 32, lane >> 5, N);
     }
   }
   store_lane_rows(dqacc, scale, dq + off, sn, qrow, valid, lane);   // dq has q's strides
   if constexpr (PEEL && !(XVIT_PEEL_DEBUG & 1)) {
     if (wave_active) {   // once per wave, after the loop: the CLS query (q0, dO0 in every column) against key block cls_kb of its own tile -> a partial of dQ0
-      const XVIT_LDS char* kimg = smem + ord.stage_of(cls_g, BWD_NST) * 2 * IMG_BYTES;
+      const XVIT_LDS char* kimg = ring.at(ord.stage_of(cls_g, BWD_NST));
       bf16x8 q0f[4], do0f[4];
       lds_row_bcast(q0f, row0, lane);
       lds_row_bcast(do0f, row0 + ROW0_BYTES, lane);
       f32x16 dq0[2] = {ZERO16, ZERO16};
-      dq_block(rd, kimg, kimg + IMG_BYTES, cls_kb, q0f, do0f, c, nlse0, dlt0, dq0);
-      store_col0(dq0, pdq + ((((int64_t)b * H + head) * (NK / 32)) + cls_g) * 64, lane);
+      dq_block<false>(rd, kimg, kimg + IMG_BYTES, cls_kb, q0f, do0f, c, nlse0, dlt0, dq0);
+      store_col0(dq0, pdq + peel_slot((int64_t)b * H + head, NK, cls_g) * 64, lane);
     }
   }
 }
@@ -737,17 +739,21 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DQ_PEEL_WAVES : 2) void attn_bwd_d
 // ------------------------------------------------------------------------------------------
 // backward, dK/dV: one wave = 32 keys, streams Q and dO tiles (+ lse, delta)
 // ------------------------------------------------------------------------------------------
-constexpr int DKV_STAGE = 2 * IMG_BYTES + 512;  // Q image | dO image | nlse[64] | delta[64]  (all four arrive by LDS-DMA)
-
 // (198 VGPRs: two blocks per CU; bounding it to 168 for a third spills and measured 7 % slower; keeping the query-block loop
 // rolled gives 162 VGPRs without spills and three blocks per CU: 552 vs 563 us at B = 126, N = 513, but 50.4 vs 47.0 us at B = 8
 // and 1466 vs 1439 us at N = 4097 — not kept)
 // one 32-query block of the dK/dV recomputation (keys on the lanes; or, for the CLS key, k0 / v0 repeated in every column):
-// S = Q K^T, dP = dO V^T -> P, dS -> dV^T += dO^T P, dK^T += Q^T dS.  st_lse / st_dlt: the tile's 64 query statistics in LDS
+// S = Q K^T, dP = dO V^T -> P, dS -> dV^T += dO^T P, dK^T += Q^T dS.  st_lse / st_dlt: the tile's 64 query statistics in LDS.
+// DROP only: the mask of (b, head) bh_base, the tile's queries query0 + 0 .. 63, this lane's key
+// (`lane`, not its half h: with h handed in, hipcc keeps one more address register live across the tile loop, 199 VGPRs for 198)
+template <bool DROP>
 __device__ __forceinline__ void dkv_block(const ImgReader& rd, const XVIT_LDS char* qimg, const XVIT_LDS char* doimg, const XVIT_LDS float* st_lse,
-                                          const XVIT_LDS float* st_dlt, int qb, const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], float c, int h,
-                                          f32x16 (&dkacc)[2], f32x16 (&dvacc)[2]) {
+                                          const XVIT_LDS float* st_dlt, int qb, const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], float c, int lane,
+                                          f32x16 (&dkacc)[2], f32x16 (&dvacc)[2], const DropArgs& drop = DropArgs{}, uint64_t bh_base = 0,
+                                          int query0 = 0, int key = 0, int N = 0) {
+  const int h = lane >> 5;
   f32x16 s, dp, pr;
+  // S[query][key] = Q K^T ; dP[query][key] = dO V^T   (key on the lane)
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(qimg, qb, ks), kf[ks], ks == 0 ? ZERO16 : s, 0, 0, 0);
 #pragma unroll
@@ -759,8 +765,14 @@ __device__ __forceinline__ void dkv_block(const ImgReader& rd, const XVIT_LDS ch
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float pv = __builtin_amdgcn_exp2f(fmaf(s[g * 4 + e], c, nl[e]));
-      pr[g * 4 + e] = pv;
-      s[g * 4 + e] = pv * (dp[g * 4 + e] - dl[e]);  // dS
+      if constexpr (DROP) {   // dV uses P_drop = mask/(1-p) P; dP = mask/(1-p) (dO V^T)
+        const bool keep = drop_keep(drop, bh_base, query0 + qb * 32 + 8 * g + 4 * h + e, key, N);
+        pr[g * 4 + e] = keep ? pv * drop.inv : 0.f;
+        s[g * 4 + e] = pv * ((keep ? dp[g * 4 + e] * drop.inv : 0.f) - dl[e]);  // dS
+      } else {
+        pr[g * 4 + e] = pv;
+        s[g * 4 + e] = pv * (dp[g * 4 + e] - dl[e]);  // dS
+      }
     }
   }
 #pragma unroll
@@ -805,25 +817,24 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DKV_PEEL_WAVES : 2) void attn_bwd_
   // delta), so the loop contains NO ordinary global load whose compiler-inserted vmcnt(0) would drain the tile DMAs.
   // Rows past N read as 0 (buffer bounds): nlse = 0 gives P = 1 there, harmless because dO = 0 and delta = 0.
   const __amdgpu_buffer_rsrc_t rstat = make_rsrc(((wave & 1) == 0 ? nlse_ws : delta) + stat0, clamp_bytes((int64_t)NK * 4));
-  auto stage_stats = [&](XVIT_LDS char* st, int tile) {   // waves 2, 3 repeat waves 0, 1 (same bytes): every wave issues 5 DMAs per tile
-    glds4(rstat, st + 2 * IMG_BYTES + (wave & 1) * 256, (uint32_t)(lane * 4), (uint32_t)(tile * TILE_ROWS * 4));
-  };
   TileOrder ord;
   ord.init(PEEL, bc.x, ntiles);
-  XVIT_LDS char* row0 = smem + BWD_NST * DKV_STAGE;   // PEEL: [k0 | v0] (2 ROW0_BYTES)
+  XVIT_LDS char* row0 = smem + dkv_lds_bytes(false);   // PEEL: [k0 | v0]
   if constexpr (PEEL) {
     if (wave == 0) {
       stage_row0(row0, k + off0, lane);
       stage_row0(row0 + ROW0_BYTES, v + off0, lane);
     }
   }
-#pragma unroll
-  for (int st = 0; st < BWD_NST - 1; ++st)
-    if (st < ntiles) {
-      lq.issue(smem + st * DKV_STAGE, wave, ord.tile(st));
-      ldo.issue(smem + st * DKV_STAGE + IMG_BYTES, wave, ord.tile(st));
-      stage_stats(smem + st * DKV_STAGE, ord.tile(st));
-    }
+  constexpr int PT = 5;   // DMAs per wave and tile: 2 Q + 2 dO + 1 statistics (waves 2, 3 repeat waves 0, 1: the same bytes)
+  const auto issue = [&](XVIT_LDS char* st, int it) {
+    const int tile = ord.tile(it);
+    lq.issue(st, wave, tile);
+    ldo.issue(st + IMG_BYTES, wave, tile);
+    glds4(rstat, st + 2 * IMG_BYTES + (wave & 1) * 256, (uint32_t)(lane * 4), (uint32_t)(tile * TILE_ROWS * 4));
+  };
+  TileRing<BWD_NST, DKV_STAGE, PT> ring;
+  ring.prologue(smem, ntiles, issue);
 
   bf16x8 kf[4], vf[4];
   load_lane_operand(kf, k + off, sn, k0, NK, lane);
@@ -832,7 +843,6 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DKV_PEEL_WAVES : 2) void attn_bwd_
   settle(vf);
   ImgReader rd;
   rd.init(lane);
-  const int h = lane >> 5;
   const float c = scale * LOG2E;
   const bool wave_active = k0 < NK;   // wave-uniform
 
@@ -864,68 +874,24 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DKV_PEEL_WAVES : 2) void attn_bwd_
 #ifdef XVIT_DEBUG_ATTN_TIMES
   const uint64_t wc_loop = wall_clock64();
 #endif
-  int stage = 0;
   for (int t = 0; t < ntiles; ++t) {
 #ifdef XVIT_DEBUG_ATTN_TIMES
     if (t == 3) tk[0] = __builtin_readcyclecounter();
     if (t == 4) tk[2] = __builtin_readcyclecounter();
 #endif
-    ring_wait<BWD_NST, 5>(t, ntiles);
-    __builtin_amdgcn_s_barrier();   // every wave's pieces of tile t are in LDS; every wave is done with tile t-1
+    ring.wait(t, ntiles);
 #ifdef XVIT_DEBUG_ATTN_TIMES
     if (t == 3) tk[1] = __builtin_readcyclecounter();
 #endif
-    if (t + BWD_NST - 1 < ntiles) {
-      int ns = stage + BWD_NST - 1;
-      if (ns >= BWD_NST) ns -= BWD_NST;
-      XVIT_LDS char* nxt = smem + ns * DKV_STAGE;
-      lq.issue(nxt, wave, ord.tile(t + BWD_NST - 1));
-      ldo.issue(nxt + IMG_BYTES, wave, ord.tile(t + BWD_NST - 1));
-      stage_stats(nxt, ord.tile(t + BWD_NST - 1));
-    }
-    const XVIT_LDS char* qimg = smem + stage * DKV_STAGE;
-    stage = stage + 1 == BWD_NST ? 0 : stage + 1;
-    const XVIT_LDS char* doimg = qimg + IMG_BYTES;
+    const XVIT_LDS char* qimg = ring.advance(t, ntiles, issue);
     const XVIT_LDS float* st_lse = (const XVIT_LDS float*)(qimg + 2 * IMG_BYTES);
-    const XVIT_LDS float* st_dlt = st_lse + 64;
     if (!wave_active) continue;
     const int nqb = PEEL || (N - t * TILE_ROWS) > 32 ? 2 : 1;   // a tail tile with <= 32 queries needs one query block only (PEEL: no tail)
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
       if (qb >= nqb) break;
-      f32x16 s, dp;
-      // S[query][key] = Q K^T ; dP[query][key] = dO V^T   (key on the lane)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(qimg, qb, ks), kf[ks], ks == 0 ? ZERO16 : s, 0, 0, 0);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.row_frag(doimg, qb, ks), vf[ks], ks == 0 ? ZERO16 : dp, 0, 0, 0);
-      f32x16 pr;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 nl = *(const XVIT_LDS f32x4*)(st_lse + qb * 32 + 8 * g + 4 * h);
-        const f32x4 dl = *(const XVIT_LDS f32x4*)(st_dlt + qb * 32 + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float pv = __builtin_amdgcn_exp2f(fmaf(s[g * 4 + e], c, nl[e]));
-          if constexpr (DROP) {   // dV uses P_drop = mask/(1-p) P; dP = mask/(1-p) (dO V^T)
-            const bool keep = drop_keep(drop, (uint64_t)stat0 * (uint64_t)N, t * TILE_ROWS + qb * 32 + 8 * g + 4 * h + e, k0 + (lane & 31), N);
-            pr[g * 4 + e] = keep ? pv * drop.inv : 0.f;
-            s[g * 4 + e] = pv * ((keep ? dp[g * 4 + e] * drop.inv : 0.f) - dl[e]);  // dS
-          } else {
-            pr[g * 4 + e] = pv;
-            s[g * 4 + e] = pv * (dp[g * 4 + e] - dl[e]);  // dS
-          }
-        }
-      }
-#pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
-        const bf16x8 pf = acc_frag(pr, ss), dsf = acc_frag(s, ss);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          dvacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.tr_frag(doimg, db, qb, ss), pf, dvacc[db], 0, 0, 0);
-          dkacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd.tr_frag(qimg, db, qb, ss), dsf, dkacc[db], 0, 0, 0);
-        }
-      }
+      dkv_block<DROP>(rd, qimg, qimg + IMG_BYTES, st_lse, st_lse + 64, qb, kf, vf, c, lane, dkacc, dvacc, drop, (uint64_t)stat0 * (uint64_t)N, t * TILE_ROWS,
+                      k0 + (lane & 31), N);
     }
   }
 #ifdef XVIT_DEBUG_ATTN_TIMES
@@ -945,14 +911,14 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DKV_PEEL_WAVES : 2) void attn_bwd_
   store_lane_rows(dvacc, 1.0f, dv + off, sn, krow, valid, lane);
   if constexpr (PEEL && !(XVIT_PEEL_DEBUG & 1)) {
     if (wave_active) {   // once per wave, after the loop: the CLS key (k0, v0 in every column) against query block cls_qb of its own tile -> partials of dK0, dV0
-      const XVIT_LDS char* qimg = smem + ord.stage_of(cls_g, BWD_NST) * DKV_STAGE;
+      const XVIT_LDS char* qimg = ring.at(ord.stage_of(cls_g, BWD_NST));
       const XVIT_LDS float* st_lse = (const XVIT_LDS float*)(qimg + 2 * IMG_BYTES);
       bf16x8 k0f[4], v0f[4];
       lds_row_bcast(k0f, row0, lane);
       lds_row_bcast(v0f, row0 + ROW0_BYTES, lane);
       f32x16 dk0[2] = {ZERO16, ZERO16}, dv0[2] = {ZERO16, ZERO16};
-      dkv_block(rd, qimg, qimg + IMG_BYTES, st_lse, st_lse + 64, cls_qb, k0f, v0f, c, h, dk0, dv0);
-      const int64_t slot = ((((int64_t)b * H + head) * (NK / 32)) + cls_g) * 64;
+      dkv_block<false>(rd, qimg, qimg + IMG_BYTES, st_lse, st_lse + 64, cls_qb, k0f, v0f, c, lane, dk0, dv0);
+      const int64_t slot = peel_slot((int64_t)b * H + head, NK, cls_g) * 64;
       store_col0(dk0, pdk + slot, lane);
       store_col0(dv0, pdv + slot, lane);
     }
@@ -970,7 +936,7 @@ __global__ __launch_bounds__(256) void attn_cls_fwd_merge_kernel(const bf16* __r
   const int b = bh / H, head = bh - b * H, G = (N - 1) / 32;
   const int64_t off0 = (int64_t)b * sb + head * DH;
   const float c = scale * LOG2E;
-  const float* ws = cls_ws + (int64_t)bh * G * CLS_SLOT;
+  const float* ws = cls_ws + peel_slot(bh, N - 1, 0) * CLS_SLOT;
   // the (CLS, CLS) score, raw like the partial maxima, is the starting state; the partials follow in slot order, eight loads deep
   float m = wave_sum(bf2f(q[off0 + lane]) * bf2f(k[off0 + lane]));
   float acc = bf2f(v[off0 + lane]), l = 1.f;
@@ -1008,7 +974,7 @@ __global__ __launch_bounds__(256) void attn_cls_bwd_merge_kernel(const bf16* __r
   const float c = scale * LOG2E;
   const float q0 = bf2f(q[off0 + lane]), k0 = bf2f(k[off0 + lane]), v0 = bf2f(v[off0 + lane]), o0 = bf2f(o[ooff0 + lane]), g0 = bf2f(d_o[ooff0 + lane]);
   float sq = 0.f, sk = 0.f, sv = 0.f;
-  const int64_t base = (int64_t)bh * G * 64 + lane;
+  const int64_t base = peel_slot(bh, N - 1, 0) * 64 + lane;
   for (int gg = 0; gg < G; gg += 8) {   // slot order, eight slots (24 loads) in flight
     float a[8], bb[8], cc[8];
 #pragma unroll
@@ -1198,11 +1164,54 @@ static bool peel_shape(int B, int H, int N, float dropout_p) {
 
 extern "C" int64_t xvit_attn_fwd_workspace_bytes(int B, int H, int N) {
   if (B <= 0 || H <= 0 || !peel_shape(B, H, N, 0.f)) return 0;
-  return (int64_t)B * H * ((N - 1) / 32) * CLS_SLOT * 4;
+  return fwd_workspace_floats(B, H, N) * 4;
 }
 extern "C" int64_t xvit_attn_bwd_workspace_bytes(int B, int H, int N) {
   if (B <= 0 || H <= 0 || N <= 0) return 0;
-  return ((int64_t)2 * B * H * N + (peel_shape(B, H, N, 0.f) ? (int64_t)3 * B * H * ((N - 1) / 32) * 64 : 0)) * 4;
+  return BwdWorkspace(B, H, N, peel_shape(B, H, N, 0.f)).total * 4;
+}
+
+// One 256-thread launch of KERNEL with LDS bytes of dynamic LDS.  Rings deeper than 3 stages need more than the default 64 KiB:
+// every launched instantiation opts in once.
+template <auto KERNEL, int LDS, class... Args>
+static void launch_lds(dim3 grid, hipStream_t s, Args... args) {
+  static const hipError_t opt_in = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  (void)opt_in;
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), LDS, s, args...);
+}
+// the extern "C" functions pick the instantiation: go(std::bool_constant<DROP>, std::bool_constant<PEEL>) holds the one argument list
+template <class Go>
+static void dispatch_form(bool peel, float dropout_p, const Go& go) {
+  if (peel) go(std::false_type{}, std::true_type{});
+  else if (dropout_p > 0.f) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{});
+}
+
+// QB = 1 (32 queries per wave).  QB = 2 was measured: identical throughput at N = 512..4097 (the loop is bound by
+// softmax VALU issue, 12.4 VALU per MFMA at d_h = 64 — not by LDS reads or per-wave ILP) and worse at small batch.
+template <bool DROP, bool PEEL>
+static void launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, int64_t sb, int64_t sn, bf16* o, int64_t osb, int64_t osn, float* lse, float* cls_ws,
+                            int B, int H, int N, float scale, DropArgs da, hipStream_t s) {
+  const int NK = PEEL ? N - 1 : N;   // PEEL: token 0 off the tile grid (see "CLS peel" above)
+  launch_lds<attn_fwd_kernel<1, DROP, PEEL>, fwd_lds_bytes(PEEL)>(dim3((NK + 127) / 128, H, B), s, q, k, v, sb, sn, o, osb, osn, lse, H, N, scale, da, cls_ws);
+  if (PEEL)
+    hipLaunchKernelGGL(attn_cls_fwd_merge_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, q, k, v, sb, o, osb, lse, (const float*)cls_ws, B * H, H, N, scale);
+}
+
+template <bool DROP, bool PEEL>
+static void launch_attn_bwd(const bf16* q, const bf16* k, const bf16* v, int64_t sb, int64_t sn, const bf16* o, const bf16* d_o, int64_t osb, int64_t osn,
+                            const float* lse, float* ws, bf16* dq, bf16* dk, bf16* dv, int B, int H, int N, float scale, DropArgs da, hipStream_t s) {
+  const BwdWorkspace w(B, H, N, PEEL);
+  const int NK = PEEL ? N - 1 : N;
+  const dim3 grid((NK + 127) / 128, H, B);
+  // the dQ kernel first: it also leaves delta and -lse log2(e) of every query row in the workspace for the dK/dV kernel
+  launch_lds<attn_bwd_dq_kernel<DROP, PEEL>, dq_lds_bytes(PEEL)>(grid, s, q, k, v, sb, sn, o, d_o, osb, osn, lse, ws + w.nlse, ws + w.delta, dq, H, N, scale, da,
+                                                                 ws + w.pdq);
+  launch_lds<attn_bwd_dkv_kernel<DROP, PEEL>, dkv_lds_bytes(PEEL)>(grid, s, q, k, v, sb, sn, o, d_o, osb, osn, lse, ws + w.nlse, ws + w.delta, dk, dv, H, N, scale,
+                                                                   da, ws + w.pdk, ws + w.pdv);
+  if (PEEL)
+    hipLaunchKernelGGL(attn_cls_bwd_merge_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, q, k, v, sb, o, d_o, osb, lse, ws + w.pdq, ws + w.pdk, ws + w.pdv,
+                       dq, dk, dv, B * H, H, N, scale);
 }
 
 extern "C" int xvit_attn_fwd(const void* q, const void* k, const void* v, int64_t sb, int64_t sn, void* o, int64_t osb, int64_t osn, float* lse,
@@ -1211,50 +1220,16 @@ extern "C" int xvit_attn_fwd(const void* q, const void* k, const void* v, int64_
   XVIT_REQUIRE(q && k && v && o && lse, "xvit_attn_fwd: null pointer");
   XVIT_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "xvit_attn_fwd: dropout_p must be in [0, 1)");
   if (int e = attn_check("xvit_attn_fwd", B, H, N, dh, sb, sn, osb, osn)) return e;
-  // QB = 1 (32 queries per wave).  QB = 2 was measured: identical throughput at N = 512..4097 (the loop is bound by
-  // softmax VALU issue, 12.4 VALU per MFMA at d_h = 64 — not by LDS reads or per-wave ILP) and worse at small batch.
-  const dim3 block(256);
-  const DropArgs da = drop_args(dropout_p, dropout_seed);
-  hipStream_t s = (hipStream_t)stream;
-  if (workspace && peel_shape(B, H, N, dropout_p)) {   // token 0 off the tile grid (see "CLS peel" above); without a workspace: the general kernel
-    XVIT_REQUIRE(workspace_bytes >= xvit_attn_fwd_workspace_bytes(B, H, N) && ((uintptr_t)workspace & 15) == 0,
+  const bool peel = workspace && peel_shape(B, H, N, dropout_p);   // without a workspace: the general kernel
+  if (peel)
+    XVIT_REQUIRE(workspace_bytes >= fwd_workspace_floats(B, H, N) * 4 && ((uintptr_t)workspace & 15) == 0,
                  "xvit_attn_fwd: workspace of %lld bytes, need %lld (xvit_attn_fwd_workspace_bytes), 16-byte aligned", (long long)workspace_bytes,
-                 (long long)xvit_attn_fwd_workspace_bytes(B, H, N));
-    const dim3 grid((N - 1 + 127) / 128, H, B);
-    hipLaunchKernelGGL((attn_fwd_kernel<1, false, true>), grid, block, FWD_NST * 2 * IMG_BYTES + ROW0_BYTES, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn,
-                       (bf16*)o, osb, osn, lse, H, N, scale, da, workspace);
-    hipLaunchKernelGGL(attn_cls_fwd_merge_kernel, dim3((B * H + 3) / 4), block, 0, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, (bf16*)o, osb, lse,
-                       (const float*)workspace, B * H, H, N, scale);
-    return check_launch("xvit_attn_fwd");
-  }
-  const dim3 grid((N + 127) / 128, H, B);
-  if (dropout_p > 0.f)
-    hipLaunchKernelGGL((attn_fwd_kernel<1, true, false>), grid, block, FWD_NST * 2 * IMG_BYTES, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn,
-                       (bf16*)o, osb, osn, lse, H, N, scale, da, (float*)nullptr);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<1, false, false>), grid, block, FWD_NST * 2 * IMG_BYTES, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn,
-                       (bf16*)o, osb, osn, lse, H, N, scale, da, (float*)nullptr);
+                 (long long)fwd_workspace_floats(B, H, N) * 4);
+  dispatch_form(peel, dropout_p, [&](auto drop, auto pl) {
+    launch_attn_fwd<decltype(drop)::value, decltype(pl)::value>((const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn, (bf16*)o, osb, osn, lse, workspace, B, H, N,
+                                                                 scale, drop_args(dropout_p, dropout_seed), (hipStream_t)stream);
+  });
   return check_launch("xvit_attn_fwd");
-}
-
-template <bool DROP, bool PEEL>
-static void launch_attn_bwd(const void* q, const void* k, const void* v, int64_t sb, int64_t sn, const void* o, const void* d_o, int64_t osb, int64_t osn,
-                            const float* lse, float* ws, void* dq, void* dk, void* dv, int B, int H, int N, float scale, DropArgs da, hipStream_t s) {
-  const int64_t total = (int64_t)B * H * N;
-  float* delta = ws;            // workspace = [2][B,H,N]: delta | -lse*log2e, then (PEEL) the dQ0 | dK0 | dV0 partials, [B,H,(N-1)/32,64] each
-  float* nlse = ws + total;
-  const int64_t slots = PEEL ? (int64_t)B * H * ((N - 1) / 32) * 64 : 0;
-  float *pdq = ws + 2 * total, *pdk = pdq + slots, *pdv = pdk + slots;
-  const int NK = PEEL ? N - 1 : N;
-  const dim3 grid((NK + 127) / 128, H, B), block(256);
-  // the dQ kernel first: it also leaves delta and -lse log2(e) of every query row in the workspace for the dK/dV kernel
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<DROP, PEEL>), grid, block, BWD_NST * 2 * IMG_BYTES + (PEEL ? 2 * ROW0_BYTES : 0), s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn,
-                     (const bf16*)o, (const bf16*)d_o, osb, osn, lse, nlse, delta, (bf16*)dq, H, N, scale, da, pdq);
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DROP, PEEL>), grid, block, BWD_NST * DKV_STAGE + (PEEL ? 2 * ROW0_BYTES : 0), s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn,
-                     (const bf16*)o, (const bf16*)d_o, osb, osn, lse, nlse, delta, (bf16*)dk, (bf16*)dv, H, N, scale, da, pdk, pdv);
-  if (PEEL)
-    hipLaunchKernelGGL(attn_cls_bwd_merge_kernel, dim3((B * H + 3) / 4), block, 0, s, (const bf16*)q, (const bf16*)k, (const bf16*)v, sb, (const bf16*)o,
-                       (const bf16*)d_o, osb, lse, pdq, pdk, pdv, (bf16*)dq, (bf16*)dk, (bf16*)dv, B * H, H, N, scale);
 }
 
 extern "C" int xvit_attn_bwd(const void* q, const void* k, const void* v, int64_t sb, int64_t sn, const void* o, const void* d_o, int64_t osb,
@@ -1264,46 +1239,38 @@ extern "C" int xvit_attn_bwd(const void* q, const void* k, const void* v, int64_
   XVIT_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "xvit_attn_bwd: dropout_p must be in [0, 1)");
   if (int e = attn_check("xvit_attn_bwd", B, H, N, dh, sb, sn, osb, osn)) return e;
   const bool peel = peel_shape(B, H, N, dropout_p);
-  const int64_t need = peel ? xvit_attn_bwd_workspace_bytes(B, H, N) : (int64_t)2 * B * H * N * 4;
+  const int64_t need = BwdWorkspace(B, H, N, peel).total * 4;
   XVIT_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, "xvit_attn_bwd: workspace of %lld bytes, need %lld (xvit_attn_bwd_workspace_bytes), 16-byte aligned",
                (long long)workspace_bytes, (long long)need);
-  hipStream_t s = (hipStream_t)stream;
-  static const bool lds_opt_in = [] {   // rings deeper than 3 stages need more than the default 64 KiB of dynamic LDS
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_NST * DKV_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_NST * DKV_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_NST * DKV_STAGE + 2 * ROW0_BYTES);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_NST * 2 * IMG_BYTES);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_NST * 2 * IMG_BYTES);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_NST * 2 * IMG_BYTES + 2 * ROW0_BYTES);
-    return true;
-  }();
-  (void)lds_opt_in;
-  const DropArgs da = drop_args(dropout_p, dropout_seed);
-  if (peel) launch_attn_bwd<false, true>(q, k, v, sb, sn, o, d_o, osb, osn, lse, workspace, dq, dk, dv, B, H, N, scale, da, s);
-  else if (dropout_p > 0.f) launch_attn_bwd<true, false>(q, k, v, sb, sn, o, d_o, osb, osn, lse, workspace, dq, dk, dv, B, H, N, scale, da, s);
-  else launch_attn_bwd<false, false>(q, k, v, sb, sn, o, d_o, osb, osn, lse, workspace, dq, dk, dv, B, H, N, scale, da, s);
+  dispatch_form(peel, dropout_p, [&](auto drop, auto pl) {
+    launch_attn_bwd<decltype(drop)::value, decltype(pl)::value>((const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn, (const bf16*)o, (const bf16*)d_o, osb, osn, lse,
+                                                                 workspace, (bf16*)dq, (bf16*)dk, (bf16*)dv, B, H, N, scale, drop_args(dropout_p, dropout_seed),
+                                                                 (hipStream_t)stream);
+  });
   return check_launch("xvit_attn_bwd");
+}
+
+// rollout (REL = false: v, d_o unused) and relevance steps
+template <bool REL>
+static int launch_rollout(const char* who, const void* q, const void* k, const void* v, int64_t sb, int64_t sn, const float* lse, const void* d_o, int64_t sbo,
+                          int64_t sno, const float* r_in, float* r_out, int B, int H, int N, int dh, float scale, xvit_stream_t stream) {
+  if (int e = attn_check(who, B, H, N, dh, sb, sn, sbo, sno)) return e;
+  const uintptr_t a = (uintptr_t)r_in, o = (uintptr_t)r_out, bytes = (uintptr_t)B * (uintptr_t)N * 4;
+  XVIT_REQUIRE(a + bytes <= o || o + bytes <= a, "%s: r_in and r_out must not alias", who);
+  hipLaunchKernelGGL(attn_rollout_kernel<REL>, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k,
+                     (const bf16*)v, sb, sn, lse, (const bf16*)d_o, REL ? sbo : 0, REL ? sno : 0, r_in, r_out, H, N, scale);
+  return check_launch(who);
 }
 
 extern "C" int xvit_attn_rollout_step(const void* q, const void* k, int64_t sb, int64_t sn, const float* lse, const float* r_in, float* r_out,
                                       int B, int H, int N, int dh, float scale, xvit_stream_t stream) {
   XVIT_REQUIRE(q && k && lse && r_in && r_out, "xvit_attn_rollout_step: null pointer");
-  if (int e = attn_check("xvit_attn_rollout_step", B, H, N, dh, sb, sn, sb, sn)) return e;
-  const uintptr_t a = (uintptr_t)r_in, o = (uintptr_t)r_out, bytes = (uintptr_t)B * (uintptr_t)N * 4;
-  XVIT_REQUIRE(a + bytes <= o || o + bytes <= a, "xvit_attn_rollout_step: r_in and r_out must not alias");
-  hipLaunchKernelGGL(attn_rollout_kernel<false>, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k,
-                     nullptr, sb, sn, lse, nullptr, 0, 0, r_in, r_out, H, N, scale);
-  return check_launch("xvit_attn_rollout_step");
+  return launch_rollout<false>("xvit_attn_rollout_step", q, k, nullptr, sb, sn, lse, nullptr, sb, sn, r_in, r_out, B, H, N, dh, scale, stream);
 }
 
 extern "C" int xvit_attn_relevance_step(const void* q, const void* k, const void* v, int64_t sb, int64_t sn, const float* lse, const void* d_o,
                                         int64_t sbo, int64_t sno, const float* r_in, float* r_out, int B, int H, int N, int dh, float scale,
                                         xvit_stream_t stream) {
   XVIT_REQUIRE(q && k && v && lse && d_o && r_in && r_out, "xvit_attn_relevance_step: null pointer");
-  if (int e = attn_check("xvit_attn_relevance_step", B, H, N, dh, sb, sn, sbo, sno)) return e;
-  const uintptr_t a = (uintptr_t)r_in, o = (uintptr_t)r_out, bytes = (uintptr_t)B * (uintptr_t)N * 4;
-  XVIT_REQUIRE(a + bytes <= o || o + bytes <= a, "xvit_attn_relevance_step: r_in and r_out must not alias");
-  hipLaunchKernelGGL(attn_rollout_kernel<true>, dim3((N + 63) / 64, 1, B), dim3(RO_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k,
-                     (const bf16*)v, sb, sn, lse, (const bf16*)d_o, sbo, sno, r_in, r_out, H, N, scale);
-  return check_launch("xvit_attn_relevance_step");
+  return launch_rollout<true>("xvit_attn_relevance_step", q, k, v, sb, sn, lse, d_o, sbo, sno, r_in, r_out, B, H, N, dh, scale, stream);
 }

@@ -27,10 +27,7 @@ constexpr int DH = 64, TILE = 64;
 constexpr int K_IMG = TILE * DH;          // 4 KiB: [64 keys][64 B]
 constexpr int STAGE = 2 * K_IMG;          // K image | V^T image ([64 d][64 B of keys])
 constexpr int NST = 2;
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int P_SCALE = 119;              // e8m0 of 2^-8
-
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 // e8m0 byte b with amax / 2^(b - 127) <= 448 (0 for an all-zero block: its products vanish anyway)
 __device__ __forceinline__ int block_scale(float amax, float& inv) {
@@ -115,20 +112,6 @@ __global__ void quant_vt_kernel(const bf16* __restrict__ v, int64_t sb, int64_t 
   vs[(((int64_t)b * H + head) * DH + d) * nkb + kb] = (uint8_t)sbyte;
 }
 
-struct BlockCoord { int x, head, b; };
-__device__ __forceinline__ BlockCoord xcd_block_coord() {   // as attention.hip: the query blocks of one (b, h) share an XCD's L2
-  const int nx = gridDim.x, nh = gridDim.y, total = nx * nh * gridDim.z;
-  const int lin = blockIdx.x + nx * (blockIdx.y + nh * blockIdx.z);
-  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (lin >> 3);
-  BlockCoord c;
-  c.x = logical % nx;
-  const int rest = logical / nx;
-  c.head = rest % nh;
-  c.b = rest / nh;
-  return c;
-}
-
 // [64 rows][64 B] images: 16-byte chunk c of row r sits at chunk position c ^ ((r >> 2) & 3): the 16 rows one ds_read_b128
 // lane group touches then spread over all 64 banks
 __device__ __forceinline__ int swz(int row) { return (row >> 2) & 3; }
@@ -154,9 +137,6 @@ __device__ __forceinline__ i32x8 pack_p(const f32x16& p0, const f32x16& p1) {
   }
   return b;
 }
-
-template <int N_>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
 
 __global__ __launch_bounds__(256, 4) void attn_fwd_fp8_kernel(const uint8_t* __restrict__ q8, const uint8_t* __restrict__ k8, const uint8_t* __restrict__ v8t,
                                                               const uint8_t* __restrict__ qs, const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vs,

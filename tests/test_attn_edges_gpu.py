@@ -79,7 +79,7 @@ def _element_case(B, H, N, mode, scale, *, p=0.0, seed=0, expect_peel=None, qkv=
 GRID_N = [1, 2, 31, 32, 33, 63, 64, 65, 96, 97, 127, 128, 129, 160, 161, 191, 192, 193, 255, 256, 257, 320, 321, 449, 513]
 GRID_CASES = [(2, 3, n) for n in GRID_N] + [(1, 2, n) for n in (1000, 1025, 3376, 4097)] + [(1, 16, 129)]
 PEEL_N = [64 * m + 1 for m in (1, 2, 3, 4, 5, 7, 8, 16, 64)]
-PEEL_CASES = [(2, 3, n) for n in PEEL_N[:-1]] + [(1, 2, PEEL_N[-1])]
+PEEL_CASES = [(2, 3, n) for n in PEEL_N[:-1]] + [(1, 2, PEEL_N[-1])] + [(5, 3, 193)]   # odd B H: 2 B H N is no multiple of 4 floats
 
 
 @pytest.mark.parametrize("B,H,N", GRID_CASES)
@@ -192,13 +192,18 @@ def _padding_ok(t, N, w, fill):
     return torch.equal(_bits(t)[pad], _bits(ref)[pad])
 
 
-@pytest.mark.parametrize("form,N", [("grid", 65), ("grid", 129), ("grid", 200), ("peel", 65), ("peel", 129), ("dropout", 65), ("dropout", 200)])
-def test_raw_entry_points_poisoned_layout(N, form):
-    """N = 65, 129: no tail in the peel form, a 1-key tail on the grid; N = 200: an 8-key tail."""
+POISON_CASES = [(f, n, 2, f"{f}-{n}") for f, n in (("grid", 65), ("grid", 129), ("grid", 200), ("peel", 65), ("peel", 129), ("dropout", 65), ("dropout", 200))]
+POISON_CASES.append(("peel", 193, 5, "peel-193-B5"))
+
+
+@pytest.mark.parametrize("form,N,B", [c[:3] for c in POISON_CASES], ids=[c[3] for c in POISON_CASES])
+def test_raw_entry_points_poisoned_layout(N, form, B):
+    """N = 65, 129: no tail in the peel form, a 1-key tail on the grid; N = 200: an 8-key tail.  B = 5 (odd B H, odd N): the peel
+    partials of the backward workspace start on a padded, 16-byte aligned offset."""
     from xvit import _lib
     ops = _ops()
     lib = _lib.load()
-    B, H, scale = 2, 3, 0.125
+    H, scale = 3, 0.125
     d = H * 64
     sn, osn = d + 24, d + 8
     p, seed = (0.1, 77) if form == "dropout" else (0.0, 0)
