@@ -1171,14 +1171,7 @@ extern "C" int64_t xvit_attn_bwd_workspace_bytes(int B, int H, int N) {
   return BwdWorkspace(B, H, N, peel_shape(B, H, N, 0.f)).total * 4;
 }
 
-// One 256-thread launch of KERNEL with LDS bytes of dynamic LDS.  Rings deeper than 3 stages need more than the default 64 KiB:
-// every launched instantiation opts in once.
-template <auto KERNEL, int LDS, class... Args>
-static void launch_lds(dim3 grid, hipStream_t s, Args... args) {
-  static const hipError_t opt_in = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  (void)opt_in;
-  hipLaunchKernelGGL(KERNEL, grid, dim3(256), LDS, s, args...);
-}
+// launches: launch_lds (xvit_common.h), 256 threads; rings deeper than 3 stages need more than the default 64 KiB of dynamic LDS
 // the extern "C" functions pick the instantiation: go(std::bool_constant<DROP>, std::bool_constant<PEEL>) holds the one argument list
 template <class Go>
 static void dispatch_form(bool peel, float dropout_p, const Go& go) {
@@ -1193,7 +1186,7 @@ template <bool DROP, bool PEEL>
 static void launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, int64_t sb, int64_t sn, bf16* o, int64_t osb, int64_t osn, float* lse, float* cls_ws,
                             int B, int H, int N, float scale, DropArgs da, hipStream_t s) {
   const int NK = PEEL ? N - 1 : N;   // PEEL: token 0 off the tile grid (see "CLS peel" above)
-  launch_lds<attn_fwd_kernel<1, DROP, PEEL>, fwd_lds_bytes(PEEL)>(dim3((NK + 127) / 128, H, B), s, q, k, v, sb, sn, o, osb, osn, lse, H, N, scale, da, cls_ws);
+  launch_lds<attn_fwd_kernel<1, DROP, PEEL>, fwd_lds_bytes(PEEL), 256>(dim3((NK + 127) / 128, H, B), s, q, k, v, sb, sn, o, osb, osn, lse, H, N, scale, da, cls_ws);
   if (PEEL)
     hipLaunchKernelGGL(attn_cls_fwd_merge_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, q, k, v, sb, o, osb, lse, (const float*)cls_ws, B * H, H, N, scale);
 }
@@ -1205,9 +1198,9 @@ static void launch_attn_bwd(const bf16* q, const bf16* k, const bf16* v, int64_t
   const int NK = PEEL ? N - 1 : N;
   const dim3 grid((NK + 127) / 128, H, B);
   // the dQ kernel first: it also leaves delta and -lse log2(e) of every query row in the workspace for the dK/dV kernel
-  launch_lds<attn_bwd_dq_kernel<DROP, PEEL>, dq_lds_bytes(PEEL)>(grid, s, q, k, v, sb, sn, o, d_o, osb, osn, lse, ws + w.nlse, ws + w.delta, dq, H, N, scale, da,
+  launch_lds<attn_bwd_dq_kernel<DROP, PEEL>, dq_lds_bytes(PEEL), 256>(grid, s, q, k, v, sb, sn, o, d_o, osb, osn, lse, ws + w.nlse, ws + w.delta, dq, H, N, scale, da,
                                                                  ws + w.pdq);
-  launch_lds<attn_bwd_dkv_kernel<DROP, PEEL>, dkv_lds_bytes(PEEL)>(grid, s, q, k, v, sb, sn, o, d_o, osb, osn, lse, ws + w.nlse, ws + w.delta, dk, dv, H, N, scale,
+  launch_lds<attn_bwd_dkv_kernel<DROP, PEEL>, dkv_lds_bytes(PEEL), 256>(grid, s, q, k, v, sb, sn, o, d_o, osb, osn, lse, ws + w.nlse, ws + w.delta, dk, dv, H, N, scale,
                                                                    da, ws + w.pdk, ws + w.pdv);
   if (PEEL)
     hipLaunchKernelGGL(attn_cls_bwd_merge_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, q, k, v, sb, o, d_o, osb, lse, ws + w.pdq, ws + w.pdk, ws + w.pdv,

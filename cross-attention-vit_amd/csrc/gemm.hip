@@ -1,43 +1,49 @@
 // bf16 MFMA GEMM with fused epilogue for gfx950 (MI355X).
 //
-// Tile 128x128x64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 tiles of
-// v_mfma_f32_16x16x32_bf16.  Operands go HBM -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds,
-// 1 KiB per wave-instruction, out-of-range -> 0), double buffered, one barrier per K-step.
-// An operand is either K-CONTIGUOUS (tile image [128 rows][64 k], 128-B rows, fragments by
-// ds_read_b128) or K-STRIDED (tile image [64 k][128 cols], 256-B rows, fragments by
-// ds_read_b64_tr_b16), so NT / NN / TN all run without a transpose pass over HBM.
+// Two tile kernels on v_mfma_f32_16x16x32_bf16, both with a 64-deep K-step:
+//   gemm_kernel      128x128 tile, 256 threads = 4 waves (2x2) of 64x64; small grids (use_big_tile)
+//   gemm_big_kernel  256x256 tile, 512 threads = 8 waves (2x4) of 128x64; the production kernel, also with patch rows
+//                    gathered from / scattered to the volume (GATHER 1..4, xvit_patch_embed_*)
+// Operands go HBM -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave-instruction,
+// out-of-range -> 0), double buffered, one barrier per K-step (TileLoader).
+// An operand is either K-CONTIGUOUS (tile image [W rows][64 k], 128-B rows, fragments by
+// ds_read_b128) or K-STRIDED (tile image [64 k][W cols], 2 W-byte rows, fragments by
+// ds_read_b64_tr_b16), so NT / NN / TN all run without a transpose pass over HBM (TileFrag).
 // LDS-DMA writes lane-linear, so both images are XOR-swizzled on the per-lane SOURCE address
 // and un-swizzled on the read (bank-conflict-free for both read kinds).
-// Epilogue: accumulators -> wave-private LDS slab -> row-contiguous 16-B accesses.
+// Epilogues: accumulators -> wave-private LDS slab -> row-contiguous accesses.  Four families share the
+// element-level math (act4, dropout4, colsum_flush): epilogue_apply (128x128 kernel and the split-K reduce
+// kernel, 4 columns per lane, pointers), wave_tile_epilogue (256x256, 4 columns per lane, any output form),
+// wave_tile_epilogue_wide (256x256, 8 columns per lane, plain bf16 outputs) and scatter_epilogue (GATHER 4).
 #include "xvit_common.h"
 
 #include <atomic>
-#include <mutex>
 #include <algorithm>
 #include <string>
 
 namespace xvit {
 
 struct GemmParams {
-  const bf16* A; const bf16* B; void* C; const float* bias; const float* res; bf16* aux;
-  int64_t lda, ldb, ldc, ldr, ldaux;
-  int64_t sA, sB, sC, sBias, sR, sAux;
-  int M, N, K, k_per_split, split_k, ntm, ntn;
-  int c_f32, act, accumulate;
-  int res_row_mod, res_row_off, seg_rows, seg_skip, row_off;
-  float* slab;          // split-K partial sums [split][batch][M][N], else nullptr
-  float* colsum;        // optional [N] fp32: += column sums of the stored C
-  float drop_p, drop_inv; uint64_t drop_seed;   // dropout after the activation, before the residual (p == 0: off)
-  const uint64_t* drop_epoch;                   // device-side epoch added to the seed at run time (captured steps), or nullptr
-  int aux_deriv;                 // aux holds GELU'(z) instead of z: ACT_GELU writes the derivative, ACT_DGELU multiplies by it
-  int narrow_epi;                // force the 8-byte-per-lane epilogue (A/B measurements)
-  int ncg;                       // gemm_big_kernel: column tiles per super-column of the tile walk
+  // default state: one unsplit, unbatched product with a bf16 C and a plain epilogue; every entry point sets what differs
+  const bf16* A = nullptr; const bf16* B = nullptr; void* C = nullptr; const float* bias = nullptr; const float* res = nullptr; bf16* aux = nullptr;
+  int64_t lda = 0, ldb = 0, ldc = 0, ldr = 0, ldaux = 0;
+  int64_t sA = 0, sB = 0, sC = 0, sBias = 0, sR = 0, sAux = 0;
+  int M = 0, N = 0, K = 0, k_per_split = 0, split_k = 1, ntm = 0, ntn = 0;
+  int c_f32 = 0, act = XVIT_ACT_NONE, accumulate = 0;
+  int res_row_mod = 0, res_row_off = 0, seg_rows = 0, seg_skip = 0, row_off = 0;
+  float* slab = nullptr;          // split-K partial sums [split][batch][M][N], else nullptr
+  float* colsum = nullptr;        // optional [N] fp32: += column sums of the stored C
+  float drop_p = 0.f, drop_inv = 1.f; uint64_t drop_seed = 0;   // dropout after the activation, before the residual (p == 0: off)
+  const uint64_t* drop_epoch = nullptr;         // device-side epoch added to the seed at run time (captured steps), or nullptr
+  int aux_deriv = 0;             // aux holds GELU'(z) instead of z: ACT_GELU writes the derivative, ACT_DGELU multiplies by it
+  int narrow_epi = 0;            // force the 8-byte-per-lane epilogue (A/B measurements)
+  int ncg = 1;                   // gemm_big_kernel: column tiles per super-column of the tile walk
   // Patch rows gathered straight from the volume (xvit_patch_embed_*; reference model_cross.py:193, the einops rearrange
   // 'b c (d p1) (h p2) (w p3) -> b (h w d) (p1 p2 p3 c)' in front of patch_to_embedding): the [rows, dp hp wp] patch matrix is
   // never stored.  mode 1: the A rows of the forward NT product; mode 2: the weight gradient (TN), whose contraction runs over
   // the patch rows in token order with the CLS rows skipped, so both operands take their K-step offset from (sample, 64-token group).
   struct PatchGather {
-    int mode;
+    int mode = 0;
     int dp, hp, wp;        // patch extents along the volume's first / middle / contiguous axis
     int Dn, Wn;            // patches along the first and the contiguous axis: token t = (h Wn + w) Dn + d
     int Sy, Sz;            // element strides of the middle and the first axis (W, H W)
@@ -51,7 +57,14 @@ struct GemmParams {
 };
 
 // ---- patch-gather address arithmetic (elements; every volume stays below 2 GiB, so byte offsets fit 31 bits) -------------
-constexpr uint32_t GATHER_OOB = 0x80000000u;   // + any K-step offset < 2^31 neither wraps nor falls below num_records
+// Two out-of-range buffer offsets ("this lane fetches zeros / stores nothing"), because two things are added to them:
+// GATHER_OOB is a loader's voffset, to which the hardware adds a K-step soffset < 2^31: the sum must neither wrap around nor fall
+// below num_records (<= 2^31 - 1).  OOB is an epilogue offset used with soffset 0 and 16-byte accesses: any value above every
+// descriptor's size (<= 0x7FFFFFF0) will do, and the largest 16-byte aligned one is taken.
+constexpr uint32_t GATHER_OOB = 0x80000000u;
+constexpr uint32_t OOB = 0xFFFFFFF0u;
+typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned u32x2_t;
+typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
 __device__ __forceinline__ uint32_t gather_elem_off(const GemmParams::PatchGather& g, int e) {   // feature f = (p1 hp + p2) wp + p3
   const int hw = g.hp * g.wp, p1 = e / hw, r = e - p1 * hw, p2 = r / g.wp, p3 = r - p2 * g.wp;
   return (uint32_t)(p1 * g.Sz + p2 * g.Sy + p3);
@@ -93,7 +106,48 @@ __device__ __forceinline__ GatherTok gather_token(const GemmParams::PatchGather&
 constexpr int ACT_GELU_D = 3;    // C = gelu(z), aux <- gelu'(z)
 constexpr int ACT_MULAUX = 4;    // C = acc * aux
 
-// ---- the fused epilogue, shared by both tile kernels and the split-K reduce kernel -------------
+// ---- element-level epilogue math on 4 consecutive columns of one row, shared by every epilogue -------------
+// The activation step.  GELU / GELU_D: v <- gelu(v), d <- gelu'(v) (one exponential for both; dead code where the caller drops d);
+// DGELU: v *= gelu'(z), z = the stored pre-activation; MULAUX: v *= z, z = the stored derivative.
+template <int ACT>
+__device__ __forceinline__ void act4(f32x4& v, f32x4& d, const bf16x4 z) {
+  if (ACT == XVIT_ACT_GELU || ACT == ACT_GELU_D) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { float a_, d_; gelu_and_grad(v[c], a_, d_); v[c] = a_; d[c] = d_; }
+  } else if (ACT == XVIT_ACT_DGELU) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] *= dgelu_f(bf2f(z[c]));
+  } else if (ACT == ACT_MULAUX) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] *= bf2f(z[c]);
+  }
+}
+// Dropout mask keyed by (seed, batch-local element index idx .. idx + 3): regenerated in the backward, never stored.
+__device__ __forceinline__ void dropout4(const GemmParams& p, f32x4& v, uint64_t idx) {
+  const uint32_t thr = (uint32_t)(p.drop_p * 16777216.0f);
+  const uint64_t seed = drop_seed_at(p.drop_seed, p.drop_epoch);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) v[c] = (hash32(seed, idx + c) & 0xFFFFFFu) >= thr ? v[c] * p.drop_inv : 0.f;
+}
+// Column sums of the stored values: a lane's 4 columns are the same in every row it visits, so they are summed in registers,
+// then over the lanes that share the columns (l, l + GROUP, l + 2 GROUP, ...: GROUP lanes cover one row), and reach memory as ONE
+// atomic per column and wave (per-element atomics made a 4104 x 3072 GELU' dgrad take 476 us instead of 34).
+template <int GROUP>
+__device__ __forceinline__ void colsum_flush(float* dst, f32x4 cs, bool col_ok) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float t = cs[c];
+#pragma unroll
+    for (int o = GROUP; o < 64; o <<= 1) t += __shfl_xor(t, o);
+    cs[c] = t;
+  }
+  if ((threadIdx.x & 63) < GROUP && col_ok) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) unsafeAtomicAdd(dst + c, cs[c]);
+  }
+}
+
+// ---- the fused epilogue of the 128x128 kernel and the split-K reduce kernel -------------
 // v: 4 consecutive output columns of one row (fp32 accumulators).  Returns the value stored.
 template <int ACT, bool DROP = false>
 __device__ __forceinline__ f32x4 epilogue_apply(const GemmParams& p, f32x4 v, int row, int col, int64_t cb, const float* bias, const float* res,
@@ -102,8 +156,7 @@ __device__ __forceinline__ f32x4 epilogue_apply(const GemmParams& p, f32x4 v, in
   if (ACT == XVIT_ACT_GELU) {
     f32x4 d;
     const f32x4 zv = v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { float a_, d_; gelu_and_grad(zv[e], a_, d_); v[e] = a_; d[e] = d_; }
+    act4<XVIT_ACT_GELU>(v, d, bf16x4{});
     if (aux) {   // the pre-activation, or (aux_mode 1) the derivative the backward will multiply by
       const f32x4 s = p.aux_deriv ? d : zv;
       bf16x4 z = {f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
@@ -111,21 +164,11 @@ __device__ __forceinline__ f32x4 epilogue_apply(const GemmParams& p, f32x4 v, in
     }
   } else if (ACT == XVIT_ACT_DGELU) {
     const bf16x4 z = *(const bf16x4*)(aux + (int64_t)row * p.ldaux + col);
-    if (p.aux_deriv) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= bf2f(z[e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= dgelu_f(bf2f(z[e]));
-    }
+    f32x4 d;
+    if (p.aux_deriv) act4<ACT_MULAUX>(v, d, z);
+    else act4<XVIT_ACT_DGELU>(v, d, z);
   }
-  if (DROP) {   // mask keyed by (seed, batch-local element index): regenerated, never stored
-    const uint32_t thr = (uint32_t)(p.drop_p * 16777216.0f);
-    const uint64_t idx = (uint64_t)(cb / (p.sC ? p.sC : 1)) * ((uint64_t)p.M * p.N) + (uint64_t)row * p.N + col;
-    const uint64_t seed = drop_seed_at(p.drop_seed, p.drop_epoch);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (hash32(seed, idx + e) & 0xFFFFFFu) >= thr ? v[e] * p.drop_inv : 0.f;
-  }
+  if (DROP) dropout4(p, v, (uint64_t)(cb / (p.sC ? p.sC : 1)) * ((uint64_t)p.M * p.N) + (uint64_t)row * p.N + col);
   if (res) {
     const int rr = p.res_row_mod > 0 ? p.res_row_off + (row % p.res_row_mod) : row;
     v += *(const f32x4*)(res + (int64_t)rr * p.ldr + col);
@@ -164,62 +207,154 @@ __device__ __forceinline__ int swz_ks(int krow) { return ((krow & 3) << 2) | ((k
 // swizzle of the 16-B chunk index inside a 128-B row of a K-contiguous image (serves b128 reads)
 __device__ __forceinline__ int swz_kc(int row) { return (row >> 1) & 7; }
 
+// Weight-gradient K-step: LDS k-row kr of both operands holds token gather_krow_token(kr) of the 64-token group (the
+// contraction order is free as long as dx and the volume agree).  One LDS-DMA instruction fills two k-rows; pairing the
+// tokens (w, d) and (w + 1, d) puts their 16-voxel runs side by side: 64 contiguous bytes per (p1, p2) instead of two
+// 32-byte pieces 512 KiB apart.
+__device__ __forceinline__ int gather_krow_token(const GemmParams::PatchGather& g, int kr) {
+  const int nw = 64 / g.Dn;
+  if (nw & 1) return kr;
+  const int a = kr >> 1, b = kr & 1, wa = a / g.Dn, d = a - wa * g.Dn;
+  return d + g.Dn * (2 * wa + b);
+}
+
+// One LDS-DMA instruction moves a 1 KiB piece of a tile image (64 lanes x 16 B, lane-linear in LDS).  The image row this lane
+// fills in piece `piece` and the 16-byte chunk of the SOURCE row it fetches for it (the swizzle sits on the source side).
+// K-strided image [64 k][W cols], 2 W-byte rows: a piece is 4 (W = 128) or 2 (W = 256) k-rows; K-contiguous image [W rows][64 k],
+// 128-byte rows: a piece is 8 rows.
+struct PieceLane { int row, chunk; };
+template <bool KS, int W>
+__device__ __forceinline__ PieceLane piece_lane(int piece, int lane) {
+  constexpr int SH = W == 128 ? 4 : 5;   // log2 of the 16-byte chunks per K-strided row
+  PieceLane o;
+  if (KS) {
+    o.row = piece * (64 >> SH) + (lane >> SH);
+    o.chunk = (lane & ((1 << SH) - 1)) ^ swz_ks(o.row);
+  } else {
+    o.row = piece * 8 + (lane >> 3);
+    o.chunk = (lane & 7) ^ swz_kc(o.row);
+  }
+  return o;
+}
+
+// Base and byte extent (for the buffer resource: reads past it return 0) of the operand tile whose first row / column is row0 of
+// rows_total, K range [k_begin, k_end).  KS: stored [K, rows]; else stored [rows, K].  ld in elements.
+struct OperandTile { const bf16* base; int64_t bytes; };
 template <bool KS>
-struct OperandLoader {
+__device__ __forceinline__ OperandTile operand_tile(const bf16* ptr, int64_t ld, int row0, int rows_total, int k_begin, int k_end) {
+  if (KS) return {ptr + (int64_t)k_begin * ld + row0, ((int64_t)(k_end - 1 - k_begin) * ld + (rows_total - row0)) * 2};
+  return {ptr + (int64_t)row0 * ld + k_begin, ((int64_t)(rows_total - 1 - row0) * ld + (k_end - k_begin)) * 2};
+}
+
+// LDS-DMA loader of one operand of a W-wide tile (W = 128: 16 KiB image, 4 waves; W = 256: 32 KiB, 8 waves): wave w moves
+// the 1 KiB pieces 4 w .. 4 w + 3.  The init_gather_* / place_tokens forms (patch embedding) exist for the 256-wide tile only.
+template <bool KS, int W>
+struct TileLoader {
   __amdgpu_buffer_rsrc_t rsrc;
   uint32_t voff[4];
   uint32_t kstep;  // soffset increment per K-tile, bytes
-  // ld in elements; `wave` handles pieces 4*wave .. 4*wave+3 of the 16 KiB image
-  __device__ __forceinline__ void init(const bf16* tile_base, int64_t bytes_avail, int64_t ld, int wave, int lane) {
-    rsrc = make_rsrc(tile_base, clamp_bytes(bytes_avail));
+  // perm != nullptr (weight gradient of the gathered patch embedding): LDS k-row kr is source row gather_krow_token(kr)
+  __device__ __forceinline__ void init(const OperandTile& t, int64_t ld, int wave, int lane, const GemmParams::PatchGather* perm = nullptr) {
+    rsrc = make_rsrc(t.base, clamp_bytes(t.bytes));
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int piece = wave * 4 + j;
-      if (KS) {
-        const int krow = piece * 4 + (lane >> 4);
-        const int chunk = (lane & 15) ^ swz_ks(krow);
-        voff[j] = (uint32_t)(krow * ld * 2 + chunk * 16);
-      } else {
-        const int row = piece * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ swz_kc(row);
-        voff[j] = (uint32_t)(row * ld * 2 + chunk * 16);
-      }
+      const PieceLane pl = piece_lane<KS, W>(wave * 4 + j, lane);
+      const int srow = KS && perm ? gather_krow_token(*perm, pl.row) : pl.row;
+      voff[j] = (uint32_t)(srow * ld * 2 + pl.chunk * 16);
     }
     kstep = KS ? (uint32_t)(BK * ld * 2) : (uint32_t)(BK * 2);
   }
-  __device__ __forceinline__ void issue(XVIT_LDS char* image, int wave, int kt) const {
-    const uint32_t soff = (uint32_t)kt * kstep;
+  // mode 1 (KS = false): row m0 + r of the token matrix = patch (sample, token) or a CLS / out-of-range row (zeros)
+  __device__ __forceinline__ void init_gather_rows(const GemmParams::PatchGather& g, const bf16* vol, int m0, int M, int wave, int lane) {
+    static_assert(W == 256 && !KS, "gathered patch rows: 256-wide K-contiguous operand");
+    rsrc = make_rsrc(vol, g.vol_bytes);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      // LDS row rl = 32 wave + 8 j + ii holds tile row 32 wave + (ii % 4) 8 + 2 j + ii / 4: the 8 rows of one DMA instruction are
+      // two groups of 4 tokens that are neighbours along W, so each of its 4 x 2 runs covers a whole 128-byte line (4 x 32 B)
+      // instead of 32 lines of 32 bytes; the epilogue un-permutes in its LDS transpose (wave_tile_epilogue<PERM>)
+      const PieceLane pl = piece_lane<false, W>(wave * 4 + j, lane);   // pl.row = rl
+      const int ii = lane >> 3, row = m0 + wave * 32 + (ii & 3) * 8 + 2 * j + (ii >> 2);
+      const int smp = row / g.ntok, n = row - smp * g.ntok;
+      voff[j] = (row < M && n >= g.cls) ? 2u * (gather_sample_origin(g, smp) + gather_patch_origin(g, n - g.cls) + gather_elem_off(g, pl.chunk * 8)) : GATHER_OOB;
+    }
+    kstep = 0;
+  }
+  // mode 2 (KS = true): k-row = token (64 consecutive tokens of one sample per K-step), column = feature n0 + c
+  __device__ __forceinline__ void init_gather_ks(const GemmParams::PatchGather& g, const bf16* vol, int n0, int N, int wave, int lane) {
+    static_assert(W == 256 && KS, "gathered patch columns: 256-wide K-strided operand");
+    rsrc = make_rsrc(vol, g.vol_bytes);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const PieceLane pl = piece_lane<true, W>(wave * 4 + j, lane);
+      const int e = n0 + (pl.chunk << 3);
+      const int tok = gather_krow_token(g, pl.row);
+      voff[j] = e < N ? 2u * ((uint32_t)((tok % g.Dn) * g.dp * g.Sz + (tok / g.Dn) * g.wp) + gather_elem_off(g, e)) : GATHER_OOB;
+    }
+    kstep = 0;
+  }
+  // mode 3: k-row kr of K-step ktg is patch token T = 64 ktg + kr.  KS operand A = dx (row = token row, this lane's 16-byte column chunk),
+  // KS operand B = the volume (this lane's feature chunk of the token's patch).  `fixed` = the lane's part that does not move:
+  // init_token_fixed sets it once (byte offset of the chunk that starts at column / feature c0 + 8 chunk of `cols`), place_tokens adds the token per K-step.
+  __device__ __forceinline__ void init_token_fixed(const GemmParams::PatchGather& g, int c0, int cols, bool volume, uint32_t (&fixed)[4], int wave, int lane) const {
+    static_assert(W == 256 && KS, "per-K-step token placement: 256-wide K-strided operand");
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int chunk = piece_lane<true, W>(wave * 4 + j, lane).chunk, e = c0 + chunk * 8;
+      fixed[j] = e < cols ? (volume ? 2u * gather_elem_off(g, e) : (uint32_t)(chunk * 16)) : GATHER_OOB;
+    }
+  }
+  __device__ __forceinline__ void place_tokens(const GemmParams::PatchGather& g, int ktg, uint32_t total, int64_t ld, bool volume, const uint32_t (&fixed)[4], int wave, int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int krow = piece_lane<true, W>(wave * 4 + j, lane).row;
+      const GatherTok t = gather_token(g, (uint32_t)ktg * 64u + (uint32_t)krow, total);
+      voff[j] = !t.ok || fixed[j] == GATHER_OOB ? GATHER_OOB : (volume ? 2u * t.vol + fixed[j] : t.row * (uint32_t)(ld * 2) + fixed[j]);
+    }
+  }
+  __device__ __forceinline__ void issue_at(XVIT_LDS char* image, int wave, uint32_t soff) const {
 #pragma unroll
     for (int j = 0; j < 4; ++j) glds16(rsrc, image + (wave * 4 + j) * 1024, voff[j], soff);
   }
+  __device__ __forceinline__ void issue(XVIT_LDS char* image, int wave, int kt) const { issue_at(image, wave, (uint32_t)kt * kstep); }
 };
 
-// Fragment addressing.  `sub` = this wave's 64-wide slice (0/1) of the tile's 128 rows/cols.
-template <bool KS>
-struct FragReader {
-  uint32_t off[KS ? 8 : 2];
-  __device__ __forceinline__ void init(int sub, int lane) {
+// Fragment addressing in the image of a W-wide tile.  NT_ = number of 16-wide tiles this wave reads from the image;
+// `first` = index of the wave's first 16-wide tile inside it.
+template <bool KS, int W, int NT_>
+struct TileFrag {
+  static constexpr int PITCH = 2 * W;   // bytes per k-row of the K-strided image
+  uint32_t off[KS ? 2 * NT_ : 2];
+  __device__ __forceinline__ void init(int first, int lane) {
     if (KS) {
       const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < NT_; ++t)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const int krow = 8 * g + 4 * s + q;
-          const int ch = sub * 8 + t * 2 + (p >> 1);
-          off[t * 2 + s] = (uint32_t)(256 * krow + 16 * (ch ^ swz_ks(krow)) + 8 * (p & 1));
+          const int ch = (first + t) * 2 + (p >> 1);
+          off[t * 2 + s] = (uint32_t)(PITCH * krow + 16 * (ch ^ swz_ks(krow)) + 8 * (p & 1));
         }
     } else {
-      const int row = sub * 64 + (lane & 15);
+      const int row = first * 16 + (lane & 15);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) off[kk] = (uint32_t)(row * 128 + (((kk * 4 + (lane >> 4)) ^ swz_kc(row)) << 4));
     }
   }
-  // fragment for 16-wide tile t (0..3), k-step kk (0..1) of the staged 64-deep K tile
+  // fragment for 16-wide tile t (0 .. NT_ - 1), k-step kk (0..1) of the staged 64-deep K tile
   __device__ __forceinline__ bf16x8 read(const XVIT_LDS char* image, int t, int kk) const {
+#ifdef XVIT_DEBUG_NO_LDSREAD   // energy decomposition (256x256 kernel): MFMAs on register-resident pseudo-random operands, no fragment reads
+    if constexpr (W == 256) {
+      u32x4_t v = {off[0] * 2654435761u, off[0] * 40503u + 12345u, (uint32_t)t * 0x9E3779B9u ^ off[0], 0x3F803F80u ^ (off[0] << 3)};
+      v &= 0xBFFFBFFFu;            // keep the bf16 exponents below 2^1: finite products
+      asm volatile("" : "+v"(v));
+      return __builtin_bit_cast(bf16x8, v);
+    }
+#endif
     if (KS) {
-      const s16x4 lo = lds_read_tr16(image + off[t * 2 + 0] + kk * 32 * 256);
-      const s16x4 hi = lds_read_tr16(image + off[t * 2 + 1] + kk * 32 * 256);
+      const s16x4 lo = lds_read_tr16(image + off[t * 2 + 0] + kk * 32 * PITCH);
+      const s16x4 hi = lds_read_tr16(image + off[t * 2 + 1] + kk * 32 * PITCH);
       s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       return __builtin_bit_cast(bf16x8, v);
     } else {
@@ -237,39 +372,21 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 
   // XCD-aware bijective remap: blocks b, b+8, ... share an XCD (its L2); give each XCD a contiguous
   // run of tiles, n fastest, so an A row-panel is fetched by one XCD and B stays L2-resident.
-  const int nblk = gridDim.x, bid = blockIdx.x;
-  const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int logical = xcd_logical(blockIdx.x, gridDim.x);
   const int tm = logical / p.ntn, tn = logical - tm * p.ntn;
   const int m0 = tm * BM, n0 = tn * BN;
   const int batch = blockIdx.z / p.split_k, split = blockIdx.z - batch * p.split_k;
   const int k_begin = split * p.k_per_split;
   const int k_end = min(p.K, k_begin + p.k_per_split);
   const int nk = (k_end - k_begin + BK - 1) / BK;
-  OperandLoader<A_KS> la;   // nk may be 0 for a trailing split: it still writes its (zero) partial tile
-  OperandLoader<B_KS> lb;
-  {
-    const bf16* Ab = p.A + batch * p.sA;
-    if (A_KS) {  // stored [K, M]
-      const bf16* base = Ab + (int64_t)k_begin * p.lda + m0;
-      la.init(base, ((int64_t)(k_end - 1 - k_begin) * p.lda + (p.M - m0)) * 2, p.lda, wave, lane);
-    } else {  // stored [M, K]
-      const bf16* base = Ab + (int64_t)m0 * p.lda + k_begin;
-      la.init(base, ((int64_t)(p.M - 1 - m0) * p.lda + (k_end - k_begin)) * 2, p.lda, wave, lane);
-    }
-    const bf16* Bb = p.B + batch * p.sB;
-    if (B_KS) {  // stored [K, N]
-      const bf16* base = Bb + (int64_t)k_begin * p.ldb + n0;
-      lb.init(base, ((int64_t)(k_end - 1 - k_begin) * p.ldb + (p.N - n0)) * 2, p.ldb, wave, lane);
-    } else {  // stored [N, K]
-      const bf16* base = Bb + (int64_t)n0 * p.ldb + k_begin;
-      lb.init(base, ((int64_t)(p.N - 1 - n0) * p.ldb + (k_end - k_begin)) * 2, p.ldb, wave, lane);
-    }
-  }
-  FragReader<A_KS> fa;
-  FragReader<B_KS> fb;
-  fa.init(wr, lane);
-  fb.init(wc, lane);
+  TileLoader<A_KS, BM> la;   // nk may be 0 for a trailing split: it still writes its (zero) partial tile
+  TileLoader<B_KS, BN> lb;
+  la.init(operand_tile<A_KS>(p.A + batch * p.sA, p.lda, m0, p.M, k_begin, k_end), p.lda, wave, lane);
+  lb.init(operand_tile<B_KS>(p.B + batch * p.sB, p.ldb, n0, p.N, k_begin, k_end), p.ldb, wave, lane);
+  TileFrag<A_KS, BM, 4> fa;   // `wr` / `wc` = this wave's 64-wide slice (4 tiles of 16) of the tile's 128 rows / cols
+  TileFrag<B_KS, BN, 4> fb;
+  fa.init(wr * 4, lane);
+  fb.init(wc * 4, lane);
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -317,9 +434,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
   const int nbatch = gridDim.z / p.split_k;
   float* part = p.slab ? p.slab + ((int64_t)split * nbatch + batch) * (int64_t)p.M * p.N : nullptr;
 
-  // column sums of the stored values: a lane's 4 columns are the same in every row it visits, so they are summed in registers,
-  // then over the 4 lanes that share the columns, and reach memory as ONE atomic per column and wave (per-element atomics made a
-  // 4104 x 3072 GELU' dgrad take 476 us instead of 34)
   f32x4 cs4 = {0.f, 0.f, 0.f, 0.f};
   const int col = n0 + wc * 64 + (lane & 15) * 4;
 #pragma unroll
@@ -346,19 +460,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
       }
     }
   }
-  if (csum && !part) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float t = cs4[e];
-      t += __shfl_xor(t, 16);
-      t += __shfl_xor(t, 32);
-      cs4[e] = t;
-    }
-    if (lane < 16 && col < p.N) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) unsafeAtomicAdd(csum + col + e, cs4[e]);
-    }
-  }
+  if (csum && !part) colsum_flush<16>(csum + col, cs4, col < p.N);
 }
 
 // ==========================================================================================
@@ -376,86 +478,6 @@ constexpr int T_OPER = TBM * BK * 2;     // 32 KiB per operand per stage
 constexpr int T_STAGE = 2 * T_OPER;      // 64 KiB
 constexpr int T_LDS = 2 * T_STAGE;       // 128 KiB
 
-// Weight-gradient K-step: LDS k-row kr of both operands holds token gather_krow_token(kr) of the 64-token group (the
-// contraction order is free as long as dx and the volume agree).  One LDS-DMA instruction fills two k-rows; pairing the
-// tokens (w, d) and (w + 1, d) puts their 16-voxel runs side by side: 64 contiguous bytes per (p1, p2) instead of two
-// 32-byte pieces 512 KiB apart.
-__device__ __forceinline__ int gather_krow_token(const GemmParams::PatchGather& g, int kr) {
-  const int nw = 64 / g.Dn;
-  if (nw & 1) return kr;
-  const int a = kr >> 1, b = kr & 1, wa = a / g.Dn, d = a - wa * g.Dn;
-  return d + g.Dn * (2 * wa + b);
-}
-
-template <bool KS>
-struct BigLoader {
-  __amdgpu_buffer_rsrc_t rsrc;
-  uint32_t voff[4];
-  uint32_t kstep;
-  // 32 KiB image = 32 pieces of 1 KiB; wave w moves pieces 4w .. 4w+3
-  // perm != nullptr (weight gradient of the gathered patch embedding): LDS k-row kr is source row gather_krow_token(kr)
-  __device__ __forceinline__ void init(const bf16* tile_base, int64_t bytes_avail, int64_t ld, int wave, int lane, const GemmParams::PatchGather* perm = nullptr) {
-    rsrc = make_rsrc(tile_base, clamp_bytes(bytes_avail));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int piece = wave * 4 + j;
-      if (KS) {  // image [64 k][256 cols], 512-B rows: a piece is 2 k-rows
-        const int krow = piece * 2 + (lane >> 5);
-        const int chunk = (lane & 31) ^ swz_ks(krow);
-        const int srow = perm ? gather_krow_token(*perm, krow) : krow;
-        voff[j] = (uint32_t)(srow * ld * 2 + chunk * 16);
-      } else {   // image [256 rows][64 k], 128-B rows: a piece is 8 rows
-        const int row = piece * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ swz_kc(row);
-        voff[j] = (uint32_t)(row * ld * 2 + chunk * 16);
-      }
-    }
-    kstep = KS ? (uint32_t)(BK * ld * 2) : (uint32_t)(BK * 2);
-  }
-  // mode 1 (KS = false): row m0 + r of the token matrix = patch (sample, token) or a CLS / out-of-range row (zeros)
-  __device__ __forceinline__ void init_gather_rows(const GemmParams::PatchGather& g, const bf16* vol, int m0, int M, int wave, int lane) {
-    rsrc = make_rsrc(vol, g.vol_bytes);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      // LDS row rl = 32 wave + 8 j + ii holds tile row 32 wave + (ii % 4) 8 + 2 j + ii / 4: the 8 rows of one DMA instruction are
-      // two groups of 4 tokens that are neighbours along W, so each of its 4 x 2 runs covers a whole 128-byte line (4 x 32 B)
-      // instead of 32 lines of 32 bytes; the epilogue un-permutes in its LDS transpose (wave_tile_epilogue<PERM>)
-      const int ii = lane >> 3, rl = (wave * 4 + j) * 8 + ii, row = m0 + wave * 32 + (ii & 3) * 8 + 2 * j + (ii >> 2);
-      const int chunk = (lane & 7) ^ swz_kc(rl);
-      const int smp = row / g.ntok, n = row - smp * g.ntok;
-      voff[j] = (row < M && n >= g.cls) ? 2u * (gather_sample_origin(g, smp) + gather_patch_origin(g, n - g.cls) + gather_elem_off(g, chunk * 8)) : GATHER_OOB;
-    }
-    kstep = 0;
-  }
-  // mode 2 (KS = true): k-row = token (64 consecutive tokens of one sample per K-step), column = feature n0 + c
-  __device__ __forceinline__ void init_gather_ks(const GemmParams::PatchGather& g, const bf16* vol, int n0, int N, int wave, int lane) {
-    rsrc = make_rsrc(vol, g.vol_bytes);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int krow = (wave * 4 + j) * 2 + (lane >> 5);
-      const int e = n0 + (((lane & 31) ^ swz_ks(krow)) << 3);
-      const int tok = gather_krow_token(g, krow);
-      voff[j] = e < N ? 2u * ((uint32_t)((tok % g.Dn) * g.dp * g.Sz + (tok / g.Dn) * g.wp) + gather_elem_off(g, e)) : GATHER_OOB;
-    }
-    kstep = 0;
-  }
-  // mode 3: k-row kr of K-step ktg is patch token T = 64 ktg + kr.  KS operand A = dx (row = token row, this lane's 16-byte column chunk),
-  // KS operand B = the volume (this lane's feature chunk of the token's patch).  `fixed` = the lane's part that does not move.
-  __device__ __forceinline__ void place_tokens(const GemmParams::PatchGather& g, int ktg, uint32_t total, int64_t ld, bool volume, const uint32_t (&fixed)[4], int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int krow = (wave * 4 + j) * 2 + (lane >> 5);
-      const GatherTok t = gather_token(g, (uint32_t)ktg * 64u + (uint32_t)krow, total);
-      voff[j] = !t.ok || fixed[j] == GATHER_OOB ? GATHER_OOB : (volume ? 2u * t.vol + fixed[j] : t.row * (uint32_t)(ld * 2) + fixed[j]);
-    }
-  }
-  __device__ __forceinline__ void issue_at(XVIT_LDS char* image, int wave, uint32_t soff) const {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) glds16(rsrc, image + (wave * 4 + j) * 1024, voff[j], soff);
-  }
-  __device__ __forceinline__ void issue(XVIT_LDS char* image, int wave, int kt) const { issue_at(image, wave, (uint32_t)kt * kstep); }
-};
-
 // K-step offsets (bytes) of the gathered operands; ktg = K-step index counted from k = 0
 __device__ __forceinline__ uint32_t gather_soff_rows(const GemmParams::PatchGather& g, int ktg) { return 2u * gather_elem_off(g, ktg * 64); }
 struct GatherStep { uint32_t a, b; };
@@ -467,47 +489,6 @@ __device__ __forceinline__ GatherStep gather_soff_wgrad(const GemmParams::PatchG
   o.b = 2u * (gather_sample_origin(g, smp) + (uint32_t)(h * g.hp * g.Sy + wpart * g.wp));
   return o;
 }
-
-// NT = number of 16-wide tiles this wave reads from the image (8 along M, 4 along N);
-// `first` = index of the wave's first 16-wide tile inside the 256-wide image.
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_dbg;
-template <bool KS, int NT_>
-struct BigFrag {
-  uint32_t off[KS ? 2 * NT_ : 2];
-  __device__ __forceinline__ void init(int first, int lane) {
-    if (KS) {
-      const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-#pragma unroll
-      for (int t = 0; t < NT_; ++t)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const int krow = 8 * g + 4 * s + q;
-          const int ch = (first + t) * 2 + (p >> 1);
-          off[t * 2 + s] = (uint32_t)(512 * krow + 16 * (ch ^ swz_ks(krow)) + 8 * (p & 1));
-        }
-    } else {
-      const int row = first * 16 + (lane & 15);
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) off[kk] = (uint32_t)(row * 128 + (((kk * 4 + (lane >> 4)) ^ swz_kc(row)) << 4));
-    }
-  }
-  __device__ __forceinline__ bf16x8 read(const XVIT_LDS char* image, int t, int kk) const {
-#ifdef XVIT_DEBUG_NO_LDSREAD   // energy decomposition: MFMAs on register-resident pseudo-random operands, no fragment reads
-    u32x4_dbg v = {off[0] * 2654435761u, off[0] * 40503u + 12345u, (uint32_t)t * 0x9E3779B9u ^ off[0], 0x3F803F80u ^ (off[0] << 3)};
-    v &= 0xBFFFBFFFu;            // keep the bf16 exponents below 2^1: finite products
-    asm volatile("" : "+v"(v));
-    return __builtin_bit_cast(bf16x8, v);
-#endif
-    if (KS) {
-      const s16x4 lo = lds_read_tr16(image + off[t * 2 + 0] + kk * 32 * 512);
-      const s16x4 hi = lds_read_tr16(image + off[t * 2 + 1] + kk * 32 * 512);
-      s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      return __builtin_bit_cast(bf16x8, v);
-    } else {
-      return *(const XVIT_LDS bf16x8*)(image + off[kk] + t * 16 * 128);
-    }
-  }
-};
 
 // scheduling pattern of big_tile_mma: per step, the LDS reads issued in it, then its 4 MFMAs (the builtin wants literals)
 template <int S, int PF, int NA, int NB>
@@ -528,8 +509,8 @@ __device__ __forceinline__ void mma_sched_steps() {
 // stall the wave ~670 cycles in the in-order vector-memory issue queue before its first MFMA (same-box A/B: one
 // per step -3 % on the model's 15 GEMM shapes; two per step or every other step are both slower than that).
 template <bool A_KS, bool B_KS>
-__device__ __forceinline__ void big_tile_mma(const XVIT_LDS char* sa, const XVIT_LDS char* sb, const BigFrag<A_KS, 8>& fa, const BigFrag<B_KS, 4>& fb,
-                                             f32x4 (&acc)[8][4], const BigLoader<A_KS>& la, const BigLoader<B_KS>& lb, __amdgpu_buffer_rsrc_t ra,
+__device__ __forceinline__ void big_tile_mma(const XVIT_LDS char* sa, const XVIT_LDS char* sb, const TileFrag<A_KS, TBM, 8>& fa, const TileFrag<B_KS, TBN, 4>& fb,
+                                             f32x4 (&acc)[8][4], const TileLoader<A_KS, TBM>& la, const TileLoader<B_KS, TBN>& lb, __amdgpu_buffer_rsrc_t ra,
                                              __amdgpu_buffer_rsrc_t rb, XVIT_LDS char* nxt, int wave, uint32_t soff_a, uint32_t soff_b) {
   constexpr int PF = 2;                       // prefetch distance in steps
   constexpr int NA = A_KS ? 2 : 1, NB = B_KS ? 2 : 1;   // LDS instructions per fragment
@@ -580,9 +561,6 @@ __device__ __forceinline__ void big_tile_mma(const XVIT_LDS char* sa, const XVIT
 #ifndef XVIT_EPI_RES_AUX
 #define XVIT_EPI_RES_AUX 2
 #endif
-typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned u32x2_t;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
-constexpr uint32_t OOB = 0xFFFFFFF0u;
 constexpr int EPI_WAVE_BYTES = 64 * 256;   // 64 rows x 64 fp32
 
 struct BigEpi {
@@ -630,8 +608,7 @@ __device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32
     if (ACT == XVIT_ACT_GELU) {
       f32x4 d;
       const f32x4 zv = v;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { float a_, d_; gelu_and_grad(zv[c], a_, d_); v[c] = a_; d[c] = d_; }
+      act4<XVIT_ACT_GELU>(v, d, bf16x4{});
       if (e.has_aux) {
         const f32x4 sv = p.aux_deriv ? d : zv;
         bf16x4 z = {f2bf(sv[0]), f2bf(sv[1]), f2bf(sv[2]), f2bf(sv[3])};
@@ -639,20 +616,11 @@ __device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32
       }
     } else if (ACT == XVIT_ACT_DGELU) {
       const bf16x4 z = __builtin_bit_cast(bf16x4, auxv);
-      if (p.aux_deriv) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] *= bf2f(z[c]);
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] *= dgelu_f(bf2f(z[c]));
-      }
+      f32x4 d;
+      if (p.aux_deriv) act4<ACT_MULAUX>(v, d, z);
+      else act4<XVIT_ACT_DGELU>(v, d, z);
     }
-    if (DROP) {
-      const uint32_t thr = (uint32_t)(p.drop_p * 16777216.0f);
-      const uint64_t idx = e.drop_base + (uint64_t)e.row * p.N + e.col;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) v[c] = (hash32(drop_seed_at(p.drop_seed, p.drop_epoch), idx + c) & 0xFFFFFFu) >= thr ? v[c] * p.drop_inv : 0.f;
-    }
+    if (DROP) dropout4(p, v, e.drop_base + (uint64_t)e.row * p.N + e.col);
     if (e.has_res) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(e.rres, ok ? e.res : OOB, 0, XVIT_EPI_RES_AUX));
     if (p.c_f32) {
       const uint32_t off = ok ? e.c : OOB;
@@ -707,19 +675,7 @@ __device__ __forceinline__ void big_epilogue(const GemmParams& p, BigEpi& e, con
   EpiLoads first;
   if constexpr (ACT == XVIT_ACT_DGELU) big_epi_issue_aux(p, e, lc, first);
   big_epi_regions<ACT, DROP, 0, PERM>(p, e, lc, first, acc, slice, woff, roff);
-  if (p.colsum && !e.to_slab) {   // += column sums of the stored tile: lanes l, l+16, l+32, l+48 share their 4 columns
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float t = e.csum[c];
-      t += __shfl_xor(t, 16);
-      t += __shfl_xor(t, 32);
-      e.csum[c] = t;
-    }
-    if ((threadIdx.x & 63) < 16 && e.col_ok) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) unsafeAtomicAdd(e.colsum_dst + c, e.csum[c]);
-    }
-  }
+  if (p.colsum && !e.to_slab) colsum_flush<16>(e.colsum_dst, e.csum, e.col_ok);   // += column sums of the stored tile
 }
 
 // ---- wide epilogue for bf16 outputs: 16 bytes per lane -----------------------------------------------------------
@@ -730,6 +686,59 @@ __device__ __forceinline__ void big_epilogue(const GemmParams& p, BigEpi& e, con
 // tile needs 16 stores per bf16 tensor.  Same LDS transpose; the read-back takes two swizzled 16-byte chunks per lane
 // (conflict-free: the XOR keeps an aligned chunk pair together).  Used when C is bf16 with no residual / row remap /
 // split-K slab and N, ldc, ldaux are multiples of 8.
+// The epilogues' address arithmetic is loop-invariant: without this opaque dependency (placed AFTER the K loop) LLVM hoists
+// it above the MFMA loop and spills the accumulators.  Returns `lane`, as far as the compiler can tell a new value.
+__device__ __forceinline__ int pin_lane(int lane) {
+  int pin = 0;
+  asm volatile("" : "+v"(pin));
+  return lane + pin;
+}
+
+// The 8-columns-per-lane LDS transpose of a wave's 128 x 64 accumulator tile, 64 rows per pass (regions 0-3 and 4-7), shared by
+// the wide and the scatter epilogue.  Written in the accumulator layout (row r = lane & 15 of each 16-row tile, chunk 4 j + g),
+// read back with 8 lanes per row (row 8 it + rr, chunks 2 c and 2 c + 1), both with chunk ^= row & 15.
+struct Transpose8 {
+  uint32_t woff[4], roffw[2][2];
+  __device__ __forceinline__ void init(int wl) {
+    const int r = wl & 15, g = wl >> 4, c = wl & 7, rr = wl >> 3;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) woff[j] = (uint32_t)(r * 256 + (((j * 4 + g) ^ r) << 4));
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) roffw[par][k] = (uint32_t)(rr * 256 + (((2 * c + k) ^ ((par * 8 + rr) & 15)) << 4));
+  }
+  template <int PASS>
+  __device__ __forceinline__ void write(XVIT_LDS char* slice, const f32x4 (&acc)[8][4]) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) *(XVIT_LDS f32x4*)(slice + i * 4096 + woff[j]) = acc[PASS * 4 + i][j];
+  }
+  // the lane's 8 columns of row 8 it + rr of the pass (it = 0..7)
+  __device__ __forceinline__ void read(const XVIT_LDS char* slice, int it, f32x4& v0, f32x4& v1) const {
+    v0 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][0]);
+    v1 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][1]);
+  }
+};
+// Region R (0..7) = 2 bodies = rows 16 R .. 16 R + 15 of the wave tile (one scheduling window: with 4 bodies of 8 elements
+// in one window the allocator spills); regions 0-3 and 4-7 share one LDS transpose pass.  prefetch(nxt) issues the next region's
+// loads in front of this region's stores; body(v0, v1, cur, b) consumes body b of `cur`, the loads issued one region earlier.
+template <int R, class Loads, class Prefetch, class Body>
+__device__ __forceinline__ void transpose8_regions(const Transpose8& t, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, Loads& cur, const Prefetch& prefetch, const Body& body) {
+  if constexpr ((R & 3) == 0) t.write<(R >> 2)>(slice, acc);
+  Loads nxt;
+  if constexpr (R < 7) prefetch(nxt);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    f32x4 v0, v1;
+    t.read(slice, (R & 3) * 2 + b, v0, v1);   // 8-row group inside the 64-row pass
+    body(v0, v1, cur, b);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (R < 7) transpose8_regions<R + 1>(t, acc, slice, nxt, prefetch, body);
+}
+
 typedef __attribute__((ext_vector_type(8))) float f32x8;
 struct WideEpi {
   __amdgpu_buffer_rsrc_t rc, raux;
@@ -759,27 +768,13 @@ __device__ __forceinline__ u32x4_t pack_bf16x8(const f32x4& a, const f32x4& b) {
 // activation + dropout on 4 of the lane's 8 elements (columns col .. col + 3 of row `row`)
 template <int ACT, bool DROP>
 __device__ __forceinline__ void wide_half(const GemmParams& p, f32x4& v, const bf16x4 z, uint64_t idx, u32x2_t& dpack) {
-  if (ACT == XVIT_ACT_GELU) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = gelu_f(v[c]);
-  } else if (ACT == ACT_GELU_D) {   // gelu and, packed to bf16 at once (registers), its derivative for the aux tensor
-    f32x4 d;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { float a_, d_; gelu_and_grad(v[c], a_, d_); v[c] = a_; d[c] = d_; }
+  f32x4 d;
+  act4<ACT>(v, d, z);
+  if (ACT == ACT_GELU_D) {   // the derivative for the aux tensor, packed to bf16 at once (registers)
     const bf16x4 db = {f2bf(d[0]), f2bf(d[1]), f2bf(d[2]), f2bf(d[3])};
     dpack = __builtin_bit_cast(u32x2_t, db);
-  } else if (ACT == XVIT_ACT_DGELU) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] *= dgelu_f(bf2f(z[c]));
-  } else if (ACT == ACT_MULAUX) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] *= bf2f(z[c]);
   }
-  if (DROP) {
-    const uint32_t thr = (uint32_t)(p.drop_p * 16777216.0f);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = (hash32(drop_seed_at(p.drop_seed, p.drop_epoch), idx + c) & 0xFFFFFFu) >= thr ? v[c] * p.drop_inv : 0.f;
-  }
+  if (DROP) dropout4(p, v, idx);
 }
 
 template <int ACT, bool DROP>
@@ -802,49 +797,18 @@ __device__ __forceinline__ void wide_body(const GemmParams& p, WideEpi& e, f32x4
   e.row += 8; e.c += e.c_step; e.aux += e.aux_step;
 }
 
-// Region R (0..7) = 2 bodies = rows 16 R .. 16 R + 15 of the wave tile (one scheduling window: with 4 bodies of 8 elements
-// in one window the allocator spills); regions 0-3 and 4-7 share one LDS transpose pass.
-template <int ACT, bool DROP, int R>
-__device__ __forceinline__ void wide_regions(const GemmParams& p, WideEpi& e, WideCursor& lc, WideLoads& cur, const f32x4 (&acc)[8][4], XVIT_LDS char* slice,
-                                             const uint32_t (&woff)[4], const uint32_t (&roffw)[2][2]) {
-  if constexpr ((R & 3) == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(XVIT_LDS f32x4*)(slice + i * 4096 + woff[j]) = acc[(R >> 2) * 4 + i][j];
-  }
-  WideLoads nxt;
-  if constexpr ((ACT == XVIT_ACT_DGELU || ACT == ACT_MULAUX) && R < 7) wide_issue_aux(p, e, lc, nxt);
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int it = (R & 3) * 2 + b;   // 8-row group inside the 64-row pass
-    const f32x4 v0 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][0]);
-    const f32x4 v1 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][1]);
-    wide_body<ACT, DROP>(p, e, v0, v1, cur.aux[b]);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (R < 7) wide_regions<ACT, DROP, R + 1>(p, e, lc, nxt, acc, slice, woff, roffw);
-}
-
 template <int ACT, bool DROP>
-__device__ __forceinline__ void wide_epilogue(const GemmParams& p, WideEpi& e, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, const uint32_t (&woff)[4],
-                                              const uint32_t (&roffw)[2][2], float* colsum_dst) {
+__device__ __forceinline__ void wide_epilogue(const GemmParams& p, WideEpi& e, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, const Transpose8& t, float* colsum_dst) {
   WideCursor lc = {e.row, e.aux};
+  const auto prefetch = [&](WideLoads& L) {
+    if constexpr (ACT == XVIT_ACT_DGELU || ACT == ACT_MULAUX) wide_issue_aux(p, e, lc, L);
+  };
   WideLoads first;
-  if constexpr (ACT == XVIT_ACT_DGELU || ACT == ACT_MULAUX) wide_issue_aux(p, e, lc, first);
-  wide_regions<ACT, DROP, 0>(p, e, lc, first, acc, slice, woff, roffw);
+  prefetch(first);
+  transpose8_regions<0>(t, acc, slice, first, prefetch, [&](f32x4 v0, f32x4 v1, const WideLoads& cur, int b) { wide_body<ACT, DROP>(p, e, v0, v1, cur.aux[b]); });
   if (colsum_dst) {   // lanes l, l+8, ..., l+56 share their 8 columns
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float t0 = e.csum0[c], t1 = e.csum1[c];
-#pragma unroll
-      for (int o = 8; o < 64; o <<= 1) { t0 += __shfl_xor(t0, o); t1 += __shfl_xor(t1, o); }
-      e.csum0[c] = t0; e.csum1[c] = t1;
-    }
-    if ((threadIdx.x & 63) < 8 && e.col_ok) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { unsafeAtomicAdd(colsum_dst + c, e.csum0[c]); unsafeAtomicAdd(colsum_dst + 4 + c, e.csum1[c]); }
-    }
+    colsum_flush<8>(colsum_dst, e.csum0, e.col_ok);
+    colsum_flush<8>(colsum_dst + 4, e.csum1, e.col_ok);
   }
 }
 
@@ -857,19 +821,9 @@ __device__ __forceinline__ void wave_tile_epilogue_wide(const GemmParams& p, con
   const bool has_bias = p.bias != nullptr;
   e.raux = make_rsrc(e.has_aux ? (const void*)(p.aux + batch * p.sAux) : (const void*)p.C, e.has_aux ? 0x7FFFFFF0u : 0u);
   const __amdgpu_buffer_rsrc_t rbias = make_rsrc(has_bias ? (const void*)(p.bias + batch * p.sBias) : (const void*)p.C, has_bias ? (uint32_t)(p.N * 4) : 0u);
-  int pin = 0;                       // keep the address arithmetic below the K loop (see wave_tile_epilogue)
-  asm volatile("" : "+v"(pin));
-  const int wl = lane + pin;
-  uint32_t woff[4], roffw[2][2];
-  {
-    const int r = wl & 15, g = wl >> 4, c = wl & 7, rr = wl >> 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) woff[j] = (uint32_t)(r * 256 + (((j * 4 + g) ^ r) << 4));
-#pragma unroll
-    for (int par = 0; par < 2; ++par)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) roffw[par][k] = (uint32_t)(rr * 256 + (((2 * c + k) ^ ((par * 8 + rr) & 15)) << 4));
-  }
+  const int wl = pin_lane(lane);
+  Transpose8 t;
+  t.init(wl);
   XVIT_LDS char* slice = smem + wave * EPI_WAVE_BYTES;
   e.col = (uint32_t)(col0 + (wl & 7) * 8);
   e.col_ok = e.col < (uint32_t)p.N;
@@ -883,7 +837,7 @@ __device__ __forceinline__ void wave_tile_epilogue_wide(const GemmParams& p, con
   e.aux = e.row * (uint32_t)p.ldaux * 2u + e.col * 2u;
   e.c_step = 8u * (uint32_t)p.ldc * 2u;
   e.aux_step = 8u * (uint32_t)p.ldaux * 2u;
-  wide_epilogue<ACT, false>(p, e, acc, slice, woff, roffw, colsum_dst);
+  wide_epilogue<ACT, false>(p, e, acc, slice, t, colsum_dst);
 }
 
 // Epilogue of one wave's 128 x 64 accumulator tile whose first element is (row0, col0); shared by every tile kernel
@@ -902,11 +856,7 @@ __device__ __forceinline__ void wave_tile_epilogue(const GemmParams& p, const f3
   const __amdgpu_buffer_rsrc_t rbias = make_rsrc(has_bias ? (const void*)(p.bias + batch * p.sBias) : (const void*)p.C, has_bias ? (uint32_t)(p.N * 4) : 0u);
   e.rslab = make_rsrc(e.to_slab ? (const void*)(p.slab + ((int64_t)split * nbatch + batch) * (int64_t)p.M * p.N) : (const void*)p.C,
                       e.to_slab ? clamp_bytes((int64_t)p.M * p.N * 4) : 0u);
-  // the epilogue's address arithmetic is loop-invariant: without this opaque dependency (placed AFTER the K loop)
-  // LLVM hoists it above the MFMA loop and spills the accumulators
-  int pin = 0;
-  asm volatile("" : "+v"(pin));
-  const int wl = lane + pin;
+  const int wl = pin_lane(lane);
   // LDS slice offsets: accumulator layout (row r = lane & 15 of each 16-row tile, chunk 4 J + g) and read-back
   // layout (row 4 it + rr, chunk k), both with chunk ^= row & 15
   uint32_t woff[8], roff[4];
@@ -914,7 +864,7 @@ __device__ __forceinline__ void wave_tile_epilogue(const GemmParams& p, const f3
     const int r = wl & 15, g = wl >> 4, k = wl & 15, rr = wl >> 4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) woff[j] = woff[4 + j] = (uint32_t)(r * 256 + (((j * 4 + g) ^ r) << 4));
-    if constexpr (PERM) {   // LDS row 8 jj + ii of a 32-row group holds tile row (ii % 4) 8 + 2 jj + ii / 4 (BigLoader::init_gather_rows)
+    if constexpr (PERM) {   // LDS row 8 jj + ii of a 32-row group holds tile row (ii % 4) 8 + 2 jj + ii / 4 (TileLoader::init_gather_rows)
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const int l32 = 16 * half + r, jj = l32 >> 3, ii = l32 & 7, rho = (ii & 3) * 8 + 2 * jj + (ii >> 2);
@@ -1001,47 +951,18 @@ __device__ __forceinline__ void scatter_body(const GemmParams& p, ScatterEpi& e,
   }
 }
 
-template <int R>
-__device__ __forceinline__ void scatter_regions(const GemmParams& p, ScatterEpi& e, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, const uint32_t (&woff)[4],
-                                                const uint32_t (&roffw)[2][2]) {
-  if constexpr ((R & 3) == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(XVIT_LDS f32x4*)(slice + i * 4096 + woff[j]) = acc[(R >> 2) * 4 + i][j];
-  }
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int it = (R & 3) * 2 + b;
-    const f32x4 v0 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][0]);
-    const f32x4 v1 = *(const XVIT_LDS f32x4*)(slice + it * 2048 + roffw[it & 1][1]);
-    scatter_body(p, e, v0, v1);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (R < 7) scatter_regions<R + 1>(p, e, acc, slice, woff, roffw);
-}
-
 __device__ __forceinline__ void scatter_epilogue(const GemmParams& p, const f32x4 (&acc)[8][4], XVIT_LDS char* smem, int wave, int lane, int row0, int col0) {
-  int pin = 0;                       // keep the address arithmetic below the K loop (see wave_tile_epilogue)
-  asm volatile("" : "+v"(pin));
-  const int wl = lane + pin;
-  uint32_t woff[4], roffw[2][2];     // the layout of wave_tile_epilogue_wide
-  {
-    const int r = wl & 15, g = wl >> 4, c = wl & 7, rr = wl >> 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) woff[j] = (uint32_t)(r * 256 + (((j * 4 + g) ^ r) << 4));
-#pragma unroll
-    for (int par = 0; par < 2; ++par)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) roffw[par][k] = (uint32_t)(rr * 256 + (((2 * c + k) ^ ((par * 8 + rr) & 15)) << 4));
-  }
+  const int wl = pin_lane(lane);
+  Transpose8 t;
+  t.init(wl);
   ScatterEpi e;
   e.vol = (char*)p.C;
   const uint32_t col = (uint32_t)(col0 + (wl & 7) * 8);
   e.col_ok = col < (uint32_t)p.N;
   e.eoff = e.col_ok ? gather_elem_off(p.g, (int)col) : 0u;
   e.row = (uint32_t)(row0 + (wl >> 3));
-  scatter_regions<0>(p, e, acc, smem + wave * EPI_WAVE_BYTES, woff, roffw);
+  struct NoLoads {} none;
+  transpose8_regions<0>(t, acc, smem + wave * EPI_WAVE_BYTES, none, [](NoLoads&) {}, [&](f32x4 v0, f32x4 v1, const NoLoads&, int) { scatter_body(p, e, v0, v1); });
 }
 
 // WIDE_ACT >= 0: the 16-byte-per-lane bf16 epilogue with that activation and no dropout, as its own instantiation (with
@@ -1074,9 +995,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
   // one XCD.  Consecutive logical ids walk the tiles of ONE K-split (sharing its A and B panels through that
   // XCD's L2) before moving to the next split; with the tile index alone (36 tiles, not a multiple of 8) the
   // split-K wgrads fetched 2.3x their algorithmic bytes.
-  const int nblk = gridDim.x, total = nblk * gridDim.z, lin = blockIdx.x + nblk * blockIdx.z;
-  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (lin >> 3);
+  const int nblk = gridDim.x;
+  const int logical = xcd_logical(blockIdx.x + nblk * blockIdx.z, nblk * gridDim.z);
   const int zz = logical / nblk, tile = logical - zz * nblk;
   // Within one (batch, split) the tiles are walked super-column by super-column: p.ncg column tiles wide, row tiles outermost
   // inside it, columns fastest.  The ~32 tiles an XCD runs at one time then share a few A row-panels AND a W slice narrow
@@ -1092,33 +1012,25 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
   const int k_end = min(p.K, k_begin + p.k_per_split);
   const int nk = (k_end - k_begin + BK - 1) / BK;   // may be 0 for a trailing split: still writes its (zero) slab
 
-  BigLoader<A_KS> la;
-  BigLoader<B_KS> lb;
+  TileLoader<A_KS, TBM> la;
+  TileLoader<B_KS, TBN> lb;
   {
     const bf16* Ab = p.A + batch * p.sA;
     if constexpr (GATHER == 1) la.init_gather_rows(p.g, Ab, m0, p.M, wave, lane);
     else if constexpr (GATHER == 2 || GATHER == 3) {   // dY rows are re-indexed per K-step (CLS rows skipped): base = row 0, K-step offsets from gather_soff_wgrad
       const int64_t rows = (int64_t)(p.K / p.g.pcount) * p.g.ntok;
-      la.init(Ab + m0, ((rows - 1) * p.lda + (p.M - m0)) * 2, p.lda, wave, lane, GATHER == 2 ? &p.g : nullptr);
-    } else if (A_KS) la.init(Ab + (int64_t)k_begin * p.lda + m0, ((int64_t)(k_end - 1 - k_begin) * p.lda + (p.M - m0)) * 2, p.lda, wave, lane);
-    else la.init(Ab + (int64_t)m0 * p.lda + k_begin, ((int64_t)(p.M - 1 - m0) * p.lda + (k_end - k_begin)) * 2, p.lda, wave, lane);
+      la.init(OperandTile{Ab + m0, ((rows - 1) * p.lda + (p.M - m0)) * 2}, p.lda, wave, lane, GATHER == 2 ? &p.g : nullptr);
+    } else la.init(operand_tile<A_KS>(Ab, p.lda, m0, p.M, k_begin, k_end), p.lda, wave, lane);
     const bf16* Bb = p.B + batch * p.sB;
     if constexpr (GATHER == 2 || GATHER == 3) lb.init_gather_ks(p.g, Bb, n0, p.N, wave, lane);
-    else if (B_KS) lb.init(Bb + (int64_t)k_begin * p.ldb + n0, ((int64_t)(k_end - 1 - k_begin) * p.ldb + (p.N - n0)) * 2, p.ldb, wave, lane);
-    else lb.init(Bb + (int64_t)n0 * p.ldb + k_begin, ((int64_t)(p.N - 1 - n0) * p.ldb + (k_end - k_begin)) * 2, p.ldb, wave, lane);
+    else lb.init(operand_tile<B_KS>(Bb, p.ldb, n0, p.N, k_begin, k_end), p.ldb, wave, lane);
   }
   // byte offsets of K-step kt (relative to this split's first) for the two loaders
   const int ktg0 = k_begin / BK;
   uint32_t fix_a[4], fix_b[4];       // mode 3: the lanes' fixed parts (column chunk of dx, feature chunk of the patch); the token part is placed per K-step
   if constexpr (GATHER == 3) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int krow = (wave * 4 + j) * 2 + (lane >> 5);
-      const int chunk = (lane & 31) ^ swz_ks(krow);
-      fix_a[j] = m0 + chunk * 8 < p.M ? (uint32_t)(chunk * 16) : GATHER_OOB;
-      const int e = n0 + (chunk << 3);
-      fix_b[j] = e < p.N ? 2u * gather_elem_off(p.g, e) : GATHER_OOB;
-    }
+    la.init_token_fixed(p.g, m0, p.M, false, fix_a, wave, lane);
+    lb.init_token_fixed(p.g, n0, p.N, true, fix_b, wave, lane);
   }
   auto step_off = [&](int kt, uint32_t& oa, uint32_t& ob) {
     if constexpr (GATHER == 1) { oa = gather_soff_rows(p.g, ktg0 + kt); ob = (uint32_t)kt * lb.kstep; }
@@ -1130,8 +1042,8 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
     }
     else { oa = (uint32_t)kt * la.kstep; ob = (uint32_t)kt * lb.kstep; }
   };
-  BigFrag<A_KS, 8> fa;
-  BigFrag<B_KS, 4> fb;
+  TileFrag<A_KS, TBM, 8> fa;
+  TileFrag<B_KS, TBN, 4> fb;
   fa.init(wr * 8, lane);
   fb.init(wc * 4, lane);
 
@@ -1208,6 +1120,40 @@ static bool use_big_tile(const xvit_gemm_args* a) {
   return big_blocks > 128;
 }
 
+// ---- what every entry point does the same way -------------
+static int k_per_split(int K, int split_k) {   // whole K-steps; K need not be a multiple of 64 where an operand is K-strided
+  const int ktiles = (K + BK - 1) / BK;
+  return ((ktiles + split_k - 1) / split_k) * BK;
+}
+
+// Tile counts of `tile`-wide square tiles and, for the 256x256 kernel, the super-column width of its tile walk: all column tiles
+// unless `grouped`, which lets xvit_set_option("gemm_group") force a width and gives NT products (forward Linears) the measured one.
+static void set_tile_grid(GemmParams& p, int tile, int layout, bool grouped = true) {
+  p.ntm = (p.M + tile - 1) / tile; p.ntn = (p.N + tile - 1) / tile;
+  p.ncg = p.ntn;
+  if (grouped) {
+    // measured at M = 64638, K = 768 (tools/gemm_model_bench.py): forward Linears with >= 6 column tiles gain 4-14 % from
+    // super-columns of 3 (qkv 238 -> 204 us, kv 152 -> 141, FFN1 406 -> 391); dgrads / wgrads and narrow outputs do not
+    const int forced = g_gemm_group.load(std::memory_order_relaxed);
+    p.ncg = forced > 0 ? std::min(forced, p.ntn) : (layout == XVIT_GEMM_NT && p.ntn >= 6 ? 3 : p.ntn);
+  }
+}
+
+// One launch of a tile kernel over p's tile grid x grid_z (batch x split); each instantiation raises its dynamic-LDS limit at its first launch
+template <bool A_KS, bool B_KS, int WIDE_ACT, int GATHER = 0>
+static void launch_big(const GemmParams& p, int grid_z, hipStream_t s) {
+  launch_lds<gemm_big_kernel<A_KS, B_KS, WIDE_ACT, GATHER>, T_LDS, 512>(dim3(p.ntm * p.ntn, 1, grid_z), s, p);
+}
+template <bool A_KS, bool B_KS>
+static void launch_small(const GemmParams& p, int grid_z, hipStream_t s) {
+  launch_lds<gemm_kernel<A_KS, B_KS>, GEMM_LDS, 256>(dim3(p.ntm * p.ntn, 1, grid_z), s, p);
+}
+static void launch_splitk_reduce(const GemmParams& p, int nbatch, hipStream_t s) {
+  const int64_t work = (int64_t)nbatch * p.M * (p.N / 4);
+  const int g = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
+  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(g), dim3(256), 0, s, p, nbatch);
+}
+
 extern "C" int xvit_set_option(const char* name, int value) {
   XVIT_REQUIRE(name != nullptr, "xvit_set_option: null name");
   const std::string n(name);
@@ -1264,8 +1210,7 @@ extern "C" int xvit_gemm(const xvit_gemm_args* a, xvit_stream_t stream) {
   p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldaux = a->ldaux;
   p.sA = a->stride_a; p.sB = a->stride_b; p.sC = a->stride_c; p.sBias = a->stride_bias; p.sR = a->stride_r; p.sAux = a->stride_aux;
   p.M = a->M; p.N = a->N; p.K = a->K; p.split_k = a->split_k;
-  const int ktiles = (a->K + BK - 1) / BK;
-  p.k_per_split = ((ktiles + a->split_k - 1) / a->split_k) * BK;
+  p.k_per_split = k_per_split(a->K, a->split_k);
   p.c_f32 = a->c_dtype == XVIT_F32; p.act = a->act; p.accumulate = a->accumulate;
   p.res_row_mod = a->res_row_mod; p.res_row_off = a->res_row_off;
   p.seg_rows = a->out_seg_rows; p.seg_skip = a->out_seg_skip; p.row_off = a->out_row_off;
@@ -1276,61 +1221,33 @@ extern "C" int xvit_gemm(const xvit_gemm_args* a, xvit_stream_t stream) {
   p.drop_epoch = a->dropout_p > 0.f ? drop_epoch_ptr() : nullptr;
   p.narrow_epi = g_gemm_epi.load(std::memory_order_relaxed);
   p.aux_deriv = a->aux_mode;
-  p.ncg = 1;
-  p.g.mode = 0;
   hipStream_t s = (hipStream_t)stream;
+  const int gz = a->batch * a->split_k;
 
-  static std::once_flag attr_once;   // the library is re-entrant: concurrent first calls from several host threads
-  std::call_once(attr_once, [] {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, true, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<true, true, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, XVIT_ACT_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, XVIT_ACT_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, true, XVIT_ACT_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, true, XVIT_ACT_DGELU>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, ACT_GELU_D>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, true, ACT_MULAUX>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-  });
   if (big) {
-    p.ntm = (a->M + TBM - 1) / TBM; p.ntn = (a->N + TBN - 1) / TBN;
-    {
-      // measured at M = 64638, K = 768 (tools/gemm_model_bench.py): forward Linears with >= 6 column tiles gain 4-14 % from
-      // super-columns of 3 (qkv 238 -> 204 us, kv 152 -> 141, FFN1 406 -> 391); dgrads / wgrads and narrow outputs do not
-      const int forced = g_gemm_group.load(std::memory_order_relaxed);
-      p.ncg = forced > 0 ? std::min(forced, p.ntn) : (a->layout == XVIT_GEMM_NT && p.ntn >= 6 ? 3 : p.ntn);
-    }
-    const dim3 grid(p.ntm * p.ntn, 1, a->batch * a->split_k), block(512);
+    set_tile_grid(p, TBM, a->layout);
     // bf16 C with nothing but bias / activation / column sums behind it: the 16-byte-per-lane epilogue (forward Linears use
     // NONE or GELU, dgrads NONE or GELU'; wgrads store fp32; with dropout the narrow kernels run)
     const bool wide = !p.c_f32 && !p.slab && !p.res && p.seg_rows == 0 && !p.narrow_epi && p.drop_p == 0.f && a->layout != XVIT_GEMM_TN &&
                       ((p.N | (int)p.ldc | (int)p.ldaux) & 7) == 0 && (a->layout == XVIT_GEMM_NT ? p.act != XVIT_ACT_DGELU : p.act != XVIT_ACT_GELU);
-    if (wide && a->layout == XVIT_GEMM_NT && p.act == XVIT_ACT_NONE) hipLaunchKernelGGL((gemm_big_kernel<false, false, XVIT_ACT_NONE>), grid, block, T_LDS, s, p);
-    else if (wide && a->layout == XVIT_GEMM_NT && p.aux_deriv) hipLaunchKernelGGL((gemm_big_kernel<false, false, ACT_GELU_D>), grid, block, T_LDS, s, p);
-    else if (wide && a->layout == XVIT_GEMM_NT) hipLaunchKernelGGL((gemm_big_kernel<false, false, XVIT_ACT_GELU>), grid, block, T_LDS, s, p);
-    else if (wide && p.act == XVIT_ACT_NONE) hipLaunchKernelGGL((gemm_big_kernel<false, true, XVIT_ACT_NONE>), grid, block, T_LDS, s, p);
-    else if (wide && p.aux_deriv) hipLaunchKernelGGL((gemm_big_kernel<false, true, ACT_MULAUX>), grid, block, T_LDS, s, p);
-    else if (wide) hipLaunchKernelGGL((gemm_big_kernel<false, true, XVIT_ACT_DGELU>), grid, block, T_LDS, s, p);
-    else if (a->layout == XVIT_GEMM_NT) hipLaunchKernelGGL((gemm_big_kernel<false, false, -1>), grid, block, T_LDS, s, p);
-    else if (a->layout == XVIT_GEMM_NN) hipLaunchKernelGGL((gemm_big_kernel<false, true, -1>), grid, block, T_LDS, s, p);
-    else hipLaunchKernelGGL((gemm_big_kernel<true, true, -1>), grid, block, T_LDS, s, p);
+    if (wide && a->layout == XVIT_GEMM_NT && p.act == XVIT_ACT_NONE) launch_big<false, false, XVIT_ACT_NONE>(p, gz, s);
+    else if (wide && a->layout == XVIT_GEMM_NT && p.aux_deriv) launch_big<false, false, ACT_GELU_D>(p, gz, s);
+    else if (wide && a->layout == XVIT_GEMM_NT) launch_big<false, false, XVIT_ACT_GELU>(p, gz, s);
+    else if (wide && p.act == XVIT_ACT_NONE) launch_big<false, true, XVIT_ACT_NONE>(p, gz, s);
+    else if (wide && p.aux_deriv) launch_big<false, true, ACT_MULAUX>(p, gz, s);
+    else if (wide) launch_big<false, true, XVIT_ACT_DGELU>(p, gz, s);
+    else if (a->layout == XVIT_GEMM_NT) launch_big<false, false, -1>(p, gz, s);
+    else if (a->layout == XVIT_GEMM_NN) launch_big<false, true, -1>(p, gz, s);
+    else launch_big<true, true, -1>(p, gz, s);
   } else {
-    p.ntm = (a->M + BM - 1) / BM; p.ntn = (a->N + BN - 1) / BN;
-    const dim3 grid(p.ntm * p.ntn, 1, a->batch * a->split_k), block(256);
+    set_tile_grid(p, BM, a->layout, false);
     switch (a->layout) {
-      case XVIT_GEMM_NT: hipLaunchKernelGGL((gemm_kernel<false, false>), grid, block, GEMM_LDS, s, p); break;
-      case XVIT_GEMM_NN: hipLaunchKernelGGL((gemm_kernel<false, true>), grid, block, GEMM_LDS, s, p); break;
-      default: hipLaunchKernelGGL((gemm_kernel<true, true>), grid, block, GEMM_LDS, s, p); break;
+      case XVIT_GEMM_NT: launch_small<false, false>(p, gz, s); break;
+      case XVIT_GEMM_NN: launch_small<false, true>(p, gz, s); break;
+      default: launch_small<true, true>(p, gz, s); break;
     }
   }
-  if (p.slab) {
-    const int64_t work = (int64_t)a->batch * a->M * (a->N / 4);
-    const int g = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(g), dim3(256), 0, s, p, a->batch);
-  }
+  if (p.slab) launch_splitk_reduce(p, a->batch, s);
   return check_launch("xvit_gemm");
 }
 
@@ -1343,9 +1260,13 @@ static int64_t pe_rows(const xvit_patch_geom* g) {
   return (int64_t)g->M * g->B * (g->cls_rows + (int64_t)(g->D / g->dp) * (g->H / g->hp) * (g->W / g->wp));
 }
 
+static bool pe_geom_ok(const xvit_patch_geom* g) {   // a volume that splits into whole patches
+  if (!g || g->B <= 0 || g->M <= 0 || g->dp <= 0 || g->hp <= 0 || g->wp <= 0 || (g->cls_rows != 0 && g->cls_rows != 1)) return false;
+  return !(g->D % g->dp || g->H % g->hp || g->W % g->wp);
+}
+
 extern "C" int xvit_patch_embed_supported(const xvit_patch_geom* g, int d) {
-  if (!g || g->B <= 0 || g->M <= 0 || g->dp <= 0 || g->hp <= 0 || g->wp <= 0 || (g->cls_rows != 0 && g->cls_rows != 1)) return 0;
-  if (g->D % g->dp || g->H % g->hp || g->W % g->wp) return 0;
+  if (!pe_geom_ok(g)) return 0;
   const int Dn = g->D / g->dp, Hn = g->H / g->hp, Wn = g->W / g->wp;
   const int64_t pd = (int64_t)g->dp * g->hp * g->wp, pcount = (int64_t)Dn * Hn * Wn;
   if (g->wp % 8 || 64 % g->wp || (g->hp * g->wp) % 64) return 0;          // a K-step = whole runs of one (p1) slab
@@ -1379,23 +1300,8 @@ static void pe_fill(GemmParams& p, const xvit_patch_geom* g, int mode) {
   p.g.m_pcount = magic(p.g.pcount); p.g.m_dn = magic(p.g.Dn); p.g.m_wn = magic(p.g.Wn); p.g.m_nb = magic(p.g.nb); p.g.m_ntok = magic(p.g.ntok);
 }
 
-static void pe_defaults(GemmParams& p) {
-  p.bias = nullptr; p.res = nullptr; p.aux = nullptr; p.slab = nullptr; p.colsum = nullptr;
-  p.lda = p.ldb = p.ldc = p.ldr = p.ldaux = 0;
-  p.sA = p.sB = p.sC = p.sBias = p.sR = p.sAux = 0;
-  p.c_f32 = 1; p.act = XVIT_ACT_NONE; p.accumulate = 0;
-  p.res_row_mod = 0; p.res_row_off = 0; p.seg_rows = 0; p.seg_skip = 0; p.row_off = 0;
-  p.drop_p = 0.f; p.drop_inv = 1.f; p.drop_seed = 0; p.drop_epoch = nullptr; p.narrow_epi = 1; p.split_k = 1; p.aux_deriv = 0;
-}
-
-static void pe_attrs() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, false, -1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<true, true, -1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<true, true, -1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_big_kernel<false, true, -1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-  });
+static void pe_defaults(GemmParams& p) {   // fp32 output through the narrow epilogue
+  p.c_f32 = 1; p.narrow_epi = 1;
 }
 
 extern "C" int xvit_patch_embed_fwd(const void* img, const xvit_patch_geom* g, const void* W, int64_t ldw, const float* bias, const float* pos, int64_t ldpos,
@@ -1413,9 +1319,8 @@ extern "C" int xvit_patch_embed_fwd(const void* img, const xvit_patch_geom* g, c
   p.M = (int)pe_rows(g); p.N = d; p.K = (int)pd;
   p.k_per_split = p.K;
   if (pos) { p.res_row_mod = p.g.ntok; p.res_row_off = 0; }   // x row (s, n) += pos[n]  (model_cross.py:197)
-  p.ntm = (p.M + TBM - 1) / TBM; p.ntn = (p.N + TBN - 1) / TBN; p.ncg = p.ntn;
-  pe_attrs();
-  hipLaunchKernelGGL((gemm_big_kernel<false, false, -1, 1>), dim3(p.ntm * p.ntn, 1, 1), dim3(512), T_LDS, (hipStream_t)stream, p);
+  set_tile_grid(p, TBM, XVIT_GEMM_NT, false);
+  launch_big<false, false, -1, 1>(p, 1, (hipStream_t)stream);
   return check_launch("xvit_patch_embed_fwd");
 }
 
@@ -1455,19 +1360,13 @@ extern "C" int xvit_patch_embed_wgrad(const void* img, const xvit_patch_geom* g,
   p.M = d; p.N = (int)pd;
   p.K = (int)((int64_t)g->M * g->B * p.g.pcount);          // contraction over the patch rows; CLS rows carry no patch
   p.split_k = pe_wgrad_split(g, d);
-  const int ktiles = (p.K + BK - 1) / BK;                     // mode 3: K need not be a multiple of 64 (tokens past it are zero rows)
-  p.k_per_split = ((ktiles + p.split_k - 1) / p.split_k) * BK;
+  p.k_per_split = k_per_split(p.K, p.split_k);               // mode 3: K need not be a multiple of 64 (tokens past it are zero rows)
   p.slab = need > 0 ? (float*)workspace : nullptr;
-  p.ntm = (p.M + TBM - 1) / TBM; p.ntn = (p.N + TBN - 1) / TBN; p.ncg = p.ntn;
-  pe_attrs();
+  set_tile_grid(p, TBM, XVIT_GEMM_TN, false);
   hipStream_t s = (hipStream_t)stream;
-  if (aligned) hipLaunchKernelGGL((gemm_big_kernel<true, true, -1, 2>), dim3(p.ntm * p.ntn, 1, p.split_k), dim3(512), T_LDS, s, p);
-  else hipLaunchKernelGGL((gemm_big_kernel<true, true, -1, 3>), dim3(p.ntm * p.ntn, 1, p.split_k), dim3(512), T_LDS, s, p);
-  if (p.slab) {
-    const int64_t work = (int64_t)p.M * (p.N / 4);
-    const int gsz = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(gsz), dim3(256), 0, s, p, 1);
-  }
+  if (aligned) launch_big<true, true, -1, 2>(p, p.split_k, s);
+  else launch_big<true, true, -1, 3>(p, p.split_k, s);
+  if (p.slab) launch_splitk_reduce(p, 1, s);
   return check_launch("xvit_patch_embed_wgrad");
 }
 
@@ -1477,8 +1376,7 @@ extern "C" int xvit_patch_embed_wgrad(const void* img, const xvit_patch_geom* g,
 // each (token row, feature) to its voxel, so the [rows, pd] patch-gradient matrix never reaches HBM.  No split-K: deterministic.
 // ------------------------------------------------------------------------------------------------------------------
 extern "C" int xvit_patch_embed_dgrad_supported(const xvit_patch_geom* g, int d) {
-  if (!g || g->B <= 0 || g->M <= 0 || g->dp <= 0 || g->hp <= 0 || g->wp <= 0 || (g->cls_rows != 0 && g->cls_rows != 1)) return 0;
-  if (g->D % g->dp || g->H % g->hp || g->W % g->wp) return 0;
+  if (!pe_geom_ok(g)) return 0;
   if (g->wp % 8) return 0;                                                 // a lane's 8 features = 8 voxels of one run: whole 16-byte stores
   if (d % 64 || d < 64) return 0;                                          // the contraction runs in 64-deep K-steps of k-contiguous rows
   const int64_t rows = pe_rows(g);
@@ -1506,13 +1404,8 @@ extern "C" int xvit_patch_embed_dgrad(const void* dx, int64_t lddx, const void* 
   p.M = (int)pe_rows(g); p.N = (int)pd; p.K = d;
   p.k_per_split = p.K;
   p.c_f32 = dimg_dtype == XVIT_F32;
-  p.ntm = (p.M + TBM - 1) / TBM; p.ntn = (p.N + TBN - 1) / TBN;
-  {
-    const int forced = g_gemm_group.load(std::memory_order_relaxed);
-    p.ncg = forced > 0 ? std::min(forced, p.ntn) : p.ntn;
-  }
-  pe_attrs();
-  hipLaunchKernelGGL((gemm_big_kernel<false, true, -1, 4>), dim3(p.ntm * p.ntn, 1, 1), dim3(512), T_LDS, (hipStream_t)stream, p);
+  set_tile_grid(p, TBM, XVIT_GEMM_NN);   // the one patch-embedding product whose tile walk honours gemm_group
+  launch_big<false, true, -1, 4>(p, 1, (hipStream_t)stream);
   return check_launch("xvit_patch_embed_dgrad");
 }
 

@@ -28,6 +28,15 @@ int check_launch(const char* what);
 const uint64_t* drop_epoch_ptr();   // xvit_set_dropout_epoch: device address of the dropout epoch counter, or nullptr (core.hip)
 void set_attn_peel(int v);   // xvit_set_option("attn_peel") -> attention.hip
 
+// One BLOCK-thread launch of KERNEL with LDS bytes of dynamic LDS.  More than the default 64 KiB has to be opted into per kernel:
+// every launched instantiation does so at its first launch (a function-local static: thread-safe, the library is re-entrant).
+template <auto KERNEL, int LDS, int BLOCK, class... Args>
+static void launch_lds(dim3 grid, hipStream_t s, Args... args) {
+  static const hipError_t opt_in = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  (void)opt_in;
+  hipLaunchKernelGGL(KERNEL, grid, dim3(BLOCK), LDS, s, args...);
+}
+
 #define XVIT_REQUIRE(cond, ...)            \
   do {                                     \
     if (!(cond)) {                         \
@@ -169,12 +178,16 @@ __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >
 // Remap the linear id so that a contiguous range of LOGICAL ids runs on one XCD: the query (or key) blocks of
 // one (batch, head) then share an L2 and its K/V (Q/dO) tiles are fetched from HBM once, not once per XCD
 // (measured before the remap: 350-390 MB fetched per launch against ~100 MB of q/k/v).
+// The remap itself, bijective on [0, total): XCD x = lin % 8 gets the logical ids [x total / 8, (x + 1) total / 8), the first
+// total % 8 XCDs one more.  What a kernel counts as `lin` and `total` decides which workgroups share an L2.
+__device__ __forceinline__ int xcd_logical(int lin, int total) {
+  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (lin >> 3);
+}
 struct BlockCoord { int x, head, b; };
 __device__ __forceinline__ BlockCoord xcd_block_coord() {
-  const int nx = gridDim.x, nh = gridDim.y, total = nx * nh * gridDim.z;
-  const int lin = blockIdx.x + nx * (blockIdx.y + nh * blockIdx.z);
-  const int q8 = total >> 3, r8 = total & 7, xcd = lin & 7;
-  const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (lin >> 3);
+  const int nx = gridDim.x, nh = gridDim.y;
+  const int logical = xcd_logical(blockIdx.x + nx * (blockIdx.y + nh * blockIdx.z), nx * nh * gridDim.z);
   BlockCoord c;
   c.x = logical % nx;
   const int rest = logical / nx;

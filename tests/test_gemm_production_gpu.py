@@ -126,8 +126,8 @@ def _launched_in_xvit_gemm():
     body = src[src.index('extern "C" int xvit_gemm('):]
     body = body[:body.index('return check_launch("xvit_gemm")')]
     found = {"gemm_big_kernel<%s>" % ", ".join(a.strip() for a in m.split(","))
-             for m in re.findall(r"hipLaunchKernelGGL\(\(gemm_big_kernel<([^>]*)>\)", body)}
-    if re.search(r"hipLaunchKernelGGL\(splitk_epilogue_kernel\b", body):
+             for m in re.findall(r"\blaunch_big<([^>]*)>\(", body)}
+    if re.search(r"\blaunch_splitk_reduce\(", body):
         found.add("splitk_epilogue_kernel")
     return found
 
