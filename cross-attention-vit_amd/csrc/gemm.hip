@@ -239,10 +239,13 @@ __device__ __forceinline__ PieceLane piece_lane(int piece, int lane) {
 
 // Base and byte extent (for the buffer resource: reads past it return 0) of the operand tile whose first row / column is row0 of
 // rows_total, K range [k_begin, k_end).  KS: stored [K, rows]; else stored [rows, K].  ld in elements.
+// The buffer range check works on whole dwords: an extent that ends on an odd element would zero the last element of the last
+// k-row (a TN product with an odd M lost a[K - 1][M - 1]), so a K-strided extent is rounded up to an even element count.  The
+// element behind an odd row's end lies inside the row (ld >= rows, ld % 8 == 0) and only feeds an output row that is never stored.
 struct OperandTile { const bf16* base; int64_t bytes; };
 template <bool KS>
 __device__ __forceinline__ OperandTile operand_tile(const bf16* ptr, int64_t ld, int row0, int rows_total, int k_begin, int k_end) {
-  if (KS) return {ptr + (int64_t)k_begin * ld + row0, ((int64_t)(k_end - 1 - k_begin) * ld + (rows_total - row0)) * 2};
+  if (KS) return {ptr + (int64_t)k_begin * ld + row0, ((int64_t)(k_end - 1 - k_begin) * ld + ((rows_total - row0 + 1) & ~1)) * 2};
   return {ptr + (int64_t)row0 * ld + k_begin, ((int64_t)(rows_total - 1 - row0) * ld + (k_end - k_begin)) * 2};
 }
 

@@ -108,11 +108,19 @@ def _rows2d(t):
     return t.stride(0)
 
 
+def gemm_workspace_bytes(layout, M, N, K, split_k, batch=1):
+    """Bytes of fp32 workspace ops.gemm(..., split_k=split_k, workspace=...) needs for this product (0 when split_k <= 1)."""
+    a = GemmArgs()
+    a.layout, a.M, a.N, a.K, a.split_k, a.batch = layout, M, N, K, split_k, batch
+    return _lib.load().xvit_gemm_workspace_bytes(C.byref(a))
+
+
 def gemm(layout, A, B, C_out, *, bias=None, residual=None, aux=None, act=ACT_NONE, accumulate=False,
-         split_k=1, res_row_mod=0, res_row_off=0, out_seg=(0, 0, 0), M=None, N=None, K=None, colsum=None, dropout=None, aux_mode=0):
+         split_k=1, res_row_mod=0, res_row_off=0, out_seg=(0, 0, 0), M=None, N=None, K=None, colsum=None, dropout=None, aux_mode=0, workspace=None):
     """C = op(A) op(B) with the fused epilogue of include/xvit.h.  2-D tensors, or 3-D
     [batch, rows, cols] for a strided batch (all of A, B, C and optional bias 2-D / residual /
-    aux 3-D then carry the batch in dim 0)."""
+    aux 3-D then carry the batch in dim 0).  workspace: an fp32 tensor for the partial tiles of split_k > 1
+    (gemm_workspace_bytes), else one is allocated per call."""
     a = GemmArgs()
     batched = A.dim() == 3
     A2, B2, C2 = (A[0], B[0], C_out[0]) if batched else (A, B, C_out)
@@ -159,7 +167,9 @@ def gemm(layout, A, B, C_out, *, bias=None, residual=None, aux=None, act=ACT_NON
     if split_k > 1:
         need = _lib.load().xvit_gemm_workspace_bytes(C.byref(a))
         if need:
-            ws = torch.empty(need // 4, dtype=torch.float32, device=C_out.device)
+            ws = workspace if workspace is not None else torch.empty(need // 4, dtype=torch.float32, device=C_out.device)
+            if not (ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() * 4 >= need):
+                raise RuntimeError(f"xvit: gemm workspace must be a contiguous fp32 tensor of at least {need} bytes")
             a.workspace, a.workspace_bytes = _ptr(ws), need
     # one family per kernel symbol: gemm_big_kernel<..> (M, N >= 256) vs gemm_kernel<..>; "+splitk" brackets also
     # contain the splitk_epilogue_kernel launch that follows

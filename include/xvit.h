@@ -83,7 +83,10 @@ typedef struct xvit_gemm_args {
   const float* bias;     /* [N] fp32 or NULL */
   const float* residual; /* fp32 [*, N] or NULL */
   void* aux;             /* bf16 [M, N] or NULL (see act) */
-  int64_t lda, ldb, ldc, ldr, ldaux;                                  /* leading dims, elements */
+  int64_t lda, ldb, ldc, ldr, ldaux;                                  /* leading dims, elements; lda, ldb: multiples of 8, >= the row
+                                                                         length.  TN with an odd M: the kernel reads one element
+                                                                         past a[k][M - 1] of every k-row (inside the row, as lda > M),
+                                                                         so the LAST row must be readable up to an even count too */
   int64_t stride_a, stride_b, stride_c, stride_bias, stride_r, stride_aux; /* per-batch strides */
   void* workspace;         /* caller-owned scratch for split_k > 1 (fp32 partial tiles), else NULL */
   int64_t workspace_bytes;

@@ -69,9 +69,18 @@ def bf16_ulp(x):
     return torch.where(x == 0, torch.zeros_like(x), torch.ldexp(torch.ones_like(x), e - 8))
 
 
-def gemm_coords(shape, flat):
+def gemm_coords(shape, flat, tile=256):
     """Where element `flat` of a GEMM output of `shape` ([..., M, N], or [N]) sits in the 256x256 kernel: batch, (row, col), its
-    256x256 tile, the 128x64 sub-tile of the wave (2 x 4 waves) and the 16x16 MFMA fragment inside that sub-tile."""
+    256x256 tile, the 128x64 sub-tile of the wave (2 x 4 waves) and the 16x16 MFMA fragment inside that sub-tile.  tile=128: in the
+    128x128 kernel instead (gemm_kernel): its 128x128 tile, the 64x64 sub-tile of the wave (2 x 2 waves) and the 16x16 fragment."""
+    if tile == 128 and len(shape) == 1:
+        return f"(col {flat}): 128x128 tile column {flat // 128}, wave sub-tile column {(flat % 128) // 64}, 16x16 fragment column {(flat % 64) // 16}"
+    if tile == 128:
+        M, N = shape[-2], shape[-1]
+        b, rc = divmod(flat, M * N)
+        r, c = divmod(rc, N)
+        return (f"{'batch %d, ' % b if len(shape) > 2 else ''}(row {r}, col {c}): 128x128 tile ({r // 128}, {c // 128}), "
+                f"wave sub-tile ({(r % 128) // 64}, {(c % 128) // 64}), 16x16 fragment ({(r % 64) // 16}, {(c % 64) // 16})")
     if len(shape) == 1:   # a row vector (column sums)
         return f"(col {flat}): 256x256 tile column {flat // 256}, wave sub-tile column {(flat % 256) // 64}, 16x16 fragment column {(flat % 64) // 16}"
     M, N = shape[-2], shape[-1]
@@ -81,10 +90,11 @@ def gemm_coords(shape, flat):
             f"wave sub-tile ({(r % 256) // 128}, {(c % 256) // 64}), 16x16 fragment ({(r % 128) // 16}, {(c % 64) // 16})")
 
 
-def assert_exact(out, ref, what="", tol=None):
+def assert_exact(out, ref, what="", tol=None, tile=256):
     """out (any device, fp32 / bf16) against the CPU reference: bit-equal to ref rounded to out's dtype, or (tol given: a
     tensor or scalar) |out - ref| <= tol element-wise.  NaN anywhere in out fails, so prefill outputs with NaN: an element
-    that is never written fails too.  The message names the number of wrong elements and where the first one sits."""
+    that is never written fails too.  The message names the number of wrong elements and where the first one sits (tile: in which
+    kernel's terms, see gemm_coords).  Returns the number of wrong elements it counted (0, or it would have raised)."""
     o = out.detach().cpu()
     assert o.shape == ref.shape, f"{what}: shape {tuple(o.shape)} != {tuple(ref.shape)}"
     if tol is None:
@@ -95,5 +105,6 @@ def assert_exact(out, ref, what="", tol=None):
     if n:
         flat = int(bad.reshape(-1).nonzero()[0])
         got, want = float(o.reshape(-1)[flat]), float(ref.reshape(-1)[flat])
-        raise AssertionError(f"{what}: {n} of {o.numel()} elements wrong; first at {gemm_coords(tuple(o.shape), flat)}: "
+        raise AssertionError(f"{what}: {n} of {o.numel()} elements wrong; first at {gemm_coords(tuple(o.shape), flat, tile)}: "
                              f"{got!r} != {want!r} ({o.dtype})")
+    return n

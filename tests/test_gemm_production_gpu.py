@@ -9,35 +9,22 @@ SITES mirrors the GEMMs of functional.block_forward / block_backward and of the 
 pass and the split their rules pick; test_sites_cover_every_big_kernel_launch (no GPU needed) checks that each gemm_big_kernel
 launch of xvit_gemm is reached by at least one site, so a new instantiation without a test fails before any GPU run.
 """
-import math
 import os
 import re
-from contextlib import contextmanager
-from dataclasses import dataclass
+from dataclasses import asdict, dataclass
 
 import pytest
 import torch
 
 import xvit.functional as XF
-from _util import assert_exact, bf16_ulp, dev, exact_grid, exact_operands
+from _gemm_check import TN_EDGES, Spec, _operands, _options, check_site
+from _util import assert_exact, dev, exact_grid
 
 GEMM_HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cross-attention-vit_amd", "csrc", "gemm.hip")
 
 D, F = 768, 3072                 # configs[1]: width, FFN width
 TOK = 513                        # tokens per sample (512 patches + CLS)
 B126, B8 = 126 * TOK, 8 * TOK    # rows at the bench batch (64638) and at the reference's batch (4104)
-DROP_P, DROP_SEED = 0.5, 987654321   # p = 0.5: the kept values are scaled by exactly 2
-# |error| allowed on top of one bf16 ulp where the epilogue evaluates GELU / GELU' (csrc/xvit_common.h gelu_parts): the
-# erf approximation is good to 1.5e-7 absolute, which for |z| < 3 stays below 2^-21 in both gelu = z cdf and gelu' = cdf + z pdf
-ACT_ABS = 2.0 ** -21
-# column sums: the epilogue adds the fp32 values it is about to round and store, in fp32, along a chain of ~600 additions per
-# column at M = 64638 (32 rows per lane, 2 shuffles, one atomic per 128-row wave tile): 600 * 2^-24 of the column's sum of |values|
-COLSUM_REL = 4e-5
-
-
-def _ops():
-    from xvit import ops
-    return ops
 
 
 @dataclass(frozen=True)
@@ -144,133 +131,16 @@ def test_sites_cover_every_big_kernel_launch():
     assert not claimed - launched, f"the mirror of xvit_gemm's dispatch is out of date: {sorted(claimed - launched)}"
 
 
-# ---- the GPU side -------------------------------------------------------------------------------------------------------
-def _gelu(x):
-    return 0.5 * x * (1 + torch.erf(x / math.sqrt(2)))
-
-
-def _dgelu(x):
-    return 0.5 * (1 + torch.erf(x / math.sqrt(2))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2 * math.pi)
-
-
-def _rowwise(fn, x, rows=8192):
-    """fn of fp64 x, chunk by chunk (the outputs here reach 2e8 elements)."""
-    out = torch.empty(x.shape, dtype=torch.float64)
-    for r in range(0, x.shape[0], rows):
-        out[r:r + rows] = fn(x[r:r + rows].double())
-    return out
-
-
-def _mask(shape, p, seed):
-    """The dropout epilogue's mask as ops.dropout draws it for the same (seed, element index): values 0 or 1 / (1 - p)."""
-    ops = _ops()
-    return ops.dropout(torch.ones(*shape, device=dev()), p, seed).cpu()
-
-
-def _operands(layout, M, N, K, seed, sa, sb, batch=()):
-    shp_a = {"NT": (M, K), "NN": (M, K), "TN": (K, M)}[layout]
-    shp_b = {"NT": (N, K), "NN": (K, N), "TN": (K, N)}[layout]
-    a, b = exact_operands(batch + shp_a, seed, sa), exact_operands(batch + shp_b, seed + 1, sb)
-    eq = {"NT": "...mk,...nk->...mn", "NN": "...mk,...kn->...mn", "TN": "...km,...kn->...mn"}[layout]
-    return a, b, torch.einsum(eq, a, b)
-
-
-def _check_colsum(cs, start, pre, what):
-    """cs = start + column sums of `pre`, the epilogue's values before their bf16 rounding (fp64 sum of the reference)."""
-    v = pre.double()
-    assert_exact(cs, start + v.sum(0), what, tol=COLSUM_REL * v.abs().sum(0) + 1e-6)
-
-
+# ---- the GPU side: tests/_gemm_check.py builds the reference, runs the call and compares -------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("site", SITES, ids=[s.name for s in SITES])
 def test_production_site(site):
-    """One production GEMM under the automatic tile choice (the 256x256 kernel), every output checked element by element."""
-    ops = _ops()
-    lay = {"NT": ops.NT, "NN": ops.NN, "TN": ops.TN}[site.layout]
-    M, N, K = site.M, site.N, site.K
-    sa = sb = 4                    # unit 2^-8: at K = 768 the pre-activation has std 0.43, inside the erf's accurate range
-    unit = 2.0 ** -(sa + sb)
-    a, b, acc = _operands(site.layout, M, N, K, 11, sa, sb)
-    ad, bd = a.to(dev(), torch.bfloat16), b.to(dev(), torch.bfloat16)
-    out_dt = torch.float32 if site.f32 else torch.bfloat16
-    C = torch.full((M, N), float("nan"), dtype=out_dt, device=dev())
-    kw = dict(split_k=site.split)
-    z = acc
-    if site.bias:
-        bias = exact_grid((N,), 21, unit, 32)
-        kw["bias"] = bias.to(dev())
-        z = acc + bias
-    if site.res:
-        res = exact_grid((M, N), 22, unit, 256)
-        kw["residual"] = res.to(dev())
-    if site.drop:
-        kw["dropout"] = (DROP_P, DROP_SEED)
-    aux = None
-    if site.act == "gelu":
-        aux = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev())
-        kw.update(act=ops.ACT_GELU, aux=aux, aux_mode=site.aux_mode)
-    elif site.act == "dgelu":
-        zin = exact_grid((M, N), 23, 2.0 ** -5, 96)                     # a pre-activation in [-3, 3]
-        aux_cpu = _rowwise(_dgelu, zin).to(torch.bfloat16) if site.aux_mode else zin.to(torch.bfloat16)
-        aux = aux_cpu.to(dev())
-        kw.update(act=ops.ACT_DGELU, aux=aux, aux_mode=site.aux_mode)
-    cs = None
-    if site.colsum:
-        cs = torch.full((N,), 0.25, device=dev())                       # the epilogue accumulates onto what is there
-        kw["colsum"] = cs
-    ops.gemm(lay, ad, bd, C, **kw)
-    torch.cuda.synchronize()
-    mask = _mask((M, N), DROP_P, DROP_SEED) if site.drop else None
-    tag = f"{site.name} {site.layout} {M}x{N}x{K} split {site.split}"
-
-    if site.act == "gelu":             # aux: gelu'(z) (aux_mode 1) or z itself; C: gelu(z) [* mask]
-        if site.aux_mode:
-            d = _rowwise(_dgelu, z)
-            assert_exact(aux, d, f"{tag}: saved gelu'", tol=bf16_ulp(d) + ACT_ABS)
-        else:
-            assert_exact(aux, z, f"{tag}: saved pre-activation")
-        g = _rowwise(_gelu, z)
-        if mask is not None:
-            g *= mask
-        assert_exact(C, g, f"{tag}: gelu", tol=bf16_ulp(g) + ACT_ABS * (mask if mask is not None else 1.0))
-    elif site.act == "dgelu":          # C = acc * gelu'(z) [* mask]: exact when the derivative is the saved bf16 operand
-        if site.aux_mode:
-            v = acc * aux_cpu.float()          # <= 21 significant bits: exact in fp32
-            if mask is not None:
-                v *= mask
-            assert_exact(C, v, f"{tag}: dgrad x saved gelu'")
-        else:
-            v = acc.double() * _rowwise(_dgelu, aux_cpu.float())
-            if mask is not None:
-                v *= mask
-            assert_exact(C, v, f"{tag}: dgrad x gelu'(z)", tol=bf16_ulp(v) + ACT_ABS * acc.abs().double() * (mask if mask is not None else 1.0))
-    else:                              # exact: (acc + bias) [* mask] [+ residual]
-        v = z if mask is None else z * mask
-        if site.res:
-            v = v + res
-        assert_exact(C, v, tag)
-    if cs is not None:
-        _check_colsum(cs, 0.25, v, f"{tag}: colsum")
-    if site.layout == "TN":            # once more on top of known values (beta = 1)
-        P = exact_grid((M, N), 24, unit, 1024)
-        C.copy_(P.to(dev()))
-        ops.gemm(lay, ad, bd, C, accumulate=True, **kw)
-        assert_exact(C, P + acc, f"{tag}: accumulate")
+    """One production GEMM under the automatic tile choice (the 256x256 kernel), every output checked element by element
+    (TN, fp32: once more with accumulate on known values)."""
+    check_site(Spec(**asdict(site), split=site.split, accumulate="again" if site.layout == "TN" else ""))
 
 
 # ---- edges at moderate size, forced onto the 256x256 kernel ------------------------------------------------------------
-@contextmanager
-def _options(**opts):
-    ops = _ops()
-    try:
-        for k, v in opts.items():
-            ops.set_option(k, v)
-        yield ops
-    finally:
-        for k in opts:
-            ops.set_option(k, 0)
-
-
 def _exact_case(layout, M, N, K, *, f32=False, split=1, batch=(), bias=False, res=False, group=0, what=""):
     """One GEMM on the 256x256 kernel with exact operands; TN (fp32) also once more with accumulate on known values."""
     sa = sb = 2
@@ -305,15 +175,6 @@ def test_ring_prologue_and_drain(layout, f32, nk):
     """nk K-steps through the two-stage LDS ring: prologue only, one steady step, ... (ragged last row and column tile)."""
     M, N, K = 296, 520, 64 * nk
     _exact_case(layout, M, N, K, f32=f32, what=f"{layout} {M}x{N}x{K} ({nk} K-steps)")
-
-
-# (K, split): k_per_split = ceil(ceil(K / 64) / split) K-steps; a split starting at or beyond K gets nk = 0 or (C division) < 0
-TN_EDGES = [(65, 1), (127, 1), (769, 1), (831, 1),      # K = 64 n + 1 and 64 n + 63
-            (320, 4),                                    # splits of 2, 2, 1, 0 K-steps
-            (257, 4),                                    # 2, 2, 1 (one row), then k_begin = 384 > K: nk = -1
-            (769, 6),                                    # 3, 3, 3, 3, 1, then k_begin = 960: nk = -2
-            (641, 3),                                    # 4, 4, 3 (the last one ragged)
-            (4104, 7)]                                   # 6 x 10, then 5 (ragged)
 
 
 @pytest.mark.gpu
