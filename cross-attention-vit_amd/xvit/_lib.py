@@ -36,6 +36,17 @@ class GradSegment(C.Structure):
 GRAD_PACK_MAX_SEGMENTS = 32   # XVIT_GRAD_PACK_MAX_SEGMENTS
 
 
+class AugmentConfig(C.Structure):
+    """struct xvit_augment_config (include/xvit.h)."""
+    _fields_ = [("flip_prob", f32 * 3), ("rotate_prob", f32), ("rotate_range", f32 * 3), ("zoom_prob", f32), ("zoom_range", f32 * 2),
+                ("translate_prob", f32), ("translate_range", f32 * 3), ("scale_prob", f32), ("scale_range", f32 * 2),
+                ("shift_prob", f32), ("shift_range", f32 * 2), ("noise_prob", f32), ("noise_std", f32),
+                ("intensity_scale", f32), ("intensity_shift", f32)]
+
+
+AUG_NPARAM = 32   # XVIT_AUG_NPARAM
+
+
 # name -> argtypes; every function returns int except the two noted below
 SIGNATURES = {
     "xvit_gemm": [C.POINTER(GemmArgs), vp],
@@ -76,6 +87,8 @@ SIGNATURES = {
     "xvit_binary_metrics_step": [vp, i64, vp, i32, i32, vp, vp],
     "xvit_mean_ce": [vp, vp, f32, vp, vp, vp, i32, i32, i32, vp],
     "xvit_resize_pad_crop_i16": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "xvit_augment_draw": [C.POINTER(AugmentConfig), vp, i32, i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp],
+    "xvit_augment_apply": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_set_option": [C.c_char_p, i32],
     "xvit_set_dropout_epoch": [C.c_void_p],
     "xvit_adam_step": [vp, vp, i32, f32, f32, f32, f32, f32, i32, f32, vp],

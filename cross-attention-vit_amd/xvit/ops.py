@@ -736,3 +736,37 @@ def resize_pad_crop_i16(vol, img_size, pad_value=-1.0):
          lambda: _lib.load().xvit_resize_pad_crop_i16(_ptr(vol), _ptr(out), B * M, Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
          "xvit_resize_pad_crop_i16")
     return out
+
+
+I16 = 2   # XVIT_I16: source volumes of augment_apply only
+
+
+def augment_draw(config, params, vol_shape, img_size, seed, counter=None, advance=False):
+    """xvit_augment_draw (include/xvit.h): fill params [B, M, 32] (fp32) with one augmentation record per volume drawn from `config`
+    (_lib.AugmentConfig) and `seed`; vol_shape / img_size are the source and destination (D, H, W).  counter: optional one-element int64
+    device tensor mixed into the seed at kernel run time, advanced by one after it is read when advance is set."""
+    assert params.dtype == torch.float32 and params.dim() == 3 and params.shape[2] == _lib.AUG_NPARAM and params.is_contiguous()
+    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
+        raise RuntimeError("augment_draw: the counter is a one-element int64 GPU tensor (or None)")
+    B, M = params.shape[:2]
+    (Ds, Hs, Ws), (D, H, W) = vol_shape, img_size
+    _run("augment_draw", params.numel() * 4.0, "byte",
+         lambda: _lib.load().xvit_augment_draw(C.byref(config), _ptr(params), B, M, Ds, Hs, Ws, D, H, W, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter),
+                                               int(bool(advance)), _stream()),
+         "xvit_augment_draw")
+    return params
+
+
+def augment_apply(src, params, img_size, pad_value=-1.0, out_dtype=torch.bfloat16):
+    """xvit_augment_apply (include/xvit.h): src [B, M, Ds, Hs, Ws] (int16, bf16 or fp32) through the records params [B, M, 32] ->
+    [B, M, 1, D, H, W] in out_dtype (bf16 or fp32): pad / crop, affine resample (or the exact copy), a v + b, noise, one rounding."""
+    assert src.dim() == 5 and src.is_contiguous() and params.dtype == torch.float32 and params.is_contiguous()
+    B, M, Ds, Hs, Ws = src.shape
+    assert tuple(params.shape) == (B, M, _lib.AUG_NPARAM), f"params {tuple(params.shape)} do not match {B} x {M} volumes"
+    D, H, W = img_size
+    out = torch.empty(B, M, 1, D, H, W, dtype=out_dtype, device=src.device)
+    sdt = I16 if src.dtype == torch.int16 else _dt(src)
+    _run("augment_apply", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
+         lambda: _lib.load().xvit_augment_apply(_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params), B * M, Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
+         "xvit_augment_apply")
+    return out

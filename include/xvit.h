@@ -26,10 +26,10 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 308 /* 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 309 /* 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
-enum { XVIT_BF16 = 0, XVIT_F32 = 1 };
+enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply only */ };
 
 typedef void* xvit_stream_t; /* hipStream_t */
 
@@ -318,6 +318,66 @@ int xvit_patch_embed_dgrad(const void* dx_bf16, int64_t lddx, const void* W_bf16
  * ---------------------------------------------------------------------------------------- */
 int xvit_resize_pad_crop_i16(const void* src_i16, void* dst_bf16, int nvol, int Ds, int Hs, int Ws, int D, int H, int W,
                              float pad_value, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Augmenting input stage (stands where dataset_ucsf.py:94-113 runs MONAI's random transforms on five CPU loader workers): pad / crop to
+ * img_size, one random affine resample and one random intensity transform, straight from the raw volume on the device into the
+ * [B, M, 1, D, H, W] tensor xvit_patch_embed_fwd reads.  The source is read once and the destination written once.  The transform set and
+ * its ranges are this project's own; parity with MONAI's random stream is NOT claimed (the position dropout takes).
+ *
+ * Two kernels with a table between them.  xvit_augment_draw turns (config, seed) into params[B, M, XVIT_AUG_NPARAM] (fp32, one record
+ * per volume) that can be read back; xvit_augment_apply is a pure function of (src, params).
+ *
+ * Record (fp32 slots):
+ *    0..11  A | t, row-major 3 x 4: source voxel index p = A (z, y, x) + t for the destination voxel index (z, y, x)
+ *    12, 13 intensity: v = a v + b                       14  noise sigma (0: no noise)
+ *    15     noise seed, a uint32 bit pattern             16  flags (integer-valued): bit 0 = exact path: A is a diagonal of +-1 and t is integral
+ *    17..19 flips (1 = the axis is reversed)             20..22 rotation angles, radians (0 when not drawn)
+ *    23..25 zooms (1 when not drawn)                     26..28 translation in voxels (0 when not drawn)        29..31 zero
+ * Slots 17..28 record what was drawn; xvit_augment_apply reads slots 0..16 only.
+ *
+ * xvit_augment_draw.  Uniform numbers are u(i) = (hash32(seed', i) & 0xFFFFFF) / 2^24 with the dropout hash (xvit_dropout), seed' = seed +
+ * *counter * 0xD1B54A32D192ED03 when a device counter is given (read at run time; advance != 0: one thread stores counter + 1 after every
+ * thread has read it, so a replayed graph draws anew at every replay), else seed.  Spatial draws of sample b use i = 64 b + k: k = 0..2
+ * flip z, y, x (u < flip_prob); 3 rotate (u < rotate_prob), 4..6 the angles about z, y, x, uniform in [-rotate_range, rotate_range];
+ * 7 zoom, 8..10 the zooms, uniform in zoom_range; 11 translate, 12..14 the translation, uniform in [-translate_range, translate_range].
+ * They never depend on the modality: the M volumes of a sample are co-registered scans and move together.  Intensity draws of volume
+ * (b, m) use i = 64 (b M + m) + 32 + k: 0 scale?, 1 the factor s in scale_range, 2 shift?, 3 the shift h in shift_range, 4 noise?,
+ * 5 sigma = noise_std (1 + draw) / 2^24 (never 0), 6 the noise seed (all 32 bits of the hash).  a = s intensity_scale,
+ * b = s intensity_shift + h: the fixed affine (normalisation) comes first.
+ * Matrix, composed in double and rounded once: with c = ((D, H, W) - 1) / 2 the destination centre and o the per-axis offset of
+ * xvit_resize_pad_crop_i16 (source index = destination index + o),
+ *    L = F Rz Ry Rx diag(1 / zoom),   F = diag(+-1),   Rz = [[1, 0, 0], [0, cz, -sz], [0, sz, cz]] (turns the y-x plane about z),
+ *    Ry = [[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]],   Rx = [[cx, -sx, 0], [sx, cx, 0], [0, 0, 1]]   (axes in index order z, y, x),
+ *    A = L,   t = c + o + translation - L c.
+ * All probabilities 0: A = I, t = o, exact.  config is a HOST struct, read during the call.  params 16-byte, counter 8-byte aligned.
+ *
+ * xvit_augment_apply.  src [nvol, Ds, Hs, Ws] int16 / bf16 / fp32 -> dst [nvol, D, H, W] bf16 / fp32, both contiguous; a volume has fewer than
+ * 2^31 voxels on either side.  General path: trilinear interpolation at p (fp32), source voxels outside the volume counting as pad_value
+ * (borders blend with it); exact path (flag bit 0): the source voxel at the integer index is copied (a flip is a reversed run).  Then
+ * v = a v + b; sigma > 0: v += sigma n with n = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((hash32(noise_seed, 2 i) & 0xFFFFFF) + 1) / 2^24,
+ * u2 = (hash32(noise_seed, 2 i + 1) & 0xFFFFFF) / 2^24 for voxel i = (z H + y) W + x of its volume; one rounding to the destination dtype.
+ * With a = 1, b = 0, sigma = 0, int16 -> bf16 the exact path reproduces xvit_resize_pad_crop_i16 bit for bit.  A workgroup owns one
+ * destination brick, every lane 8 consecutive voxels along W (16-byte stores where the address allows, any W); no atomics: bit-reproducible.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_AUG_NPARAM 32
+enum { XVIT_AUG_MATRIX = 0, XVIT_AUG_SCALE = 12, XVIT_AUG_SHIFT = 13, XVIT_AUG_SIGMA = 14, XVIT_AUG_NOISE_SEED = 15, XVIT_AUG_FLAGS = 16,
+       XVIT_AUG_FLIPS = 17, XVIT_AUG_ANGLES = 20, XVIT_AUG_ZOOMS = 23, XVIT_AUG_TRANSLATION = 26 };
+enum { XVIT_AUG_FLAG_EXACT = 1 };
+typedef struct xvit_augment_config {
+  float flip_prob[3];                          /* per axis z, y, x */
+  float rotate_prob, rotate_range[3];          /* radians, about z, y, x */
+  float zoom_prob, zoom_range[2];              /* lo <= hi, lo > 0; one draw per axis */
+  float translate_prob, translate_range[3];    /* voxels, >= 0 */
+  float scale_prob, scale_range[2];            /* multiplicative factor, lo <= hi */
+  float shift_prob, shift_range[2];            /* lo <= hi */
+  float noise_prob, noise_std;                 /* noise_std >= 0 */
+  float intensity_scale, intensity_shift;      /* the fixed affine folded into a, b */
+} xvit_augment_config;
+int xvit_augment_draw(const xvit_augment_config* config, float* params, int B, int M, int Ds, int Hs, int Ws, int D, int H, int W, uint64_t seed,
+                      uint64_t* counter, int advance, xvit_stream_t stream);
+int xvit_augment_apply(const void* src, int src_dtype, void* dst, int dst_dtype, const float* params, int nvol, int Ds, int Hs, int Ws, int D, int H,
+                       int W, float pad_value, xvit_stream_t stream);
 
 /* x[m, b, 0, :] = cls + pos[0]  (model_cross.py:195-197, the CLS row); x fp32 [M*B, N, d] */
 int xvit_cls_row_fwd(const float* cls, const float* pos, float* x, int MB, int N, int d, xvit_stream_t stream);

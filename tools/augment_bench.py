@@ -1,0 +1,99 @@
+"""Time the augmenting input stage at the reference's input shape: B = 8, M = 2, 240 x 240 x 155 int16 -> 128^3 bf16.
+
+    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE]
+
+Arms, interleaved inside every repeat (so that drift hits them alike): xvit_resize_pad_crop_i16 (twice: two identical arms), the exact
+path as identity, the exact path with all three flips, the general path (every random transform on) and the draw kernel.  Times are
+device-event times per launch (median over the repeats); GB/s counts the source bytes the destination maps to, read once, plus the
+destination bytes.  The identity arm is held against xvit_resize_pad_crop_i16: it may be slower by no more than the spread, which is the
+largest max - min over the repeats of the two identical arms.  Exit status 1 when it is.  The other arms are reported, not gated."""
+from __future__ import annotations
+
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cross-attention-vit_amd"))
+
+B, M, SRC, DST = 8, 2, (240, 240, 155), (128, 128, 128)
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("augment_bench: needs a GPU; a CPU run measures nothing")
+    from xvit import ops
+    from xvit.augment import AugmentParams, VolumeAugment
+
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    src = torch.randint(0, 3000, (B, M) + SRC, generator=g, dtype=torch.int16).to(dev)
+    off = dict(flip_prob=(0, 0, 0), rotate_prob=0, zoom_prob=0, translate_prob=0, scale_intensity_prob=0, shift_intensity_prob=0, noise_prob=0)
+    ident = VolumeAugment(DST, **off)
+    t_ident = ident.draw(B, M, SRC, dev)
+    t_flip = VolumeAugment(DST, **dict(off, flip_prob=(1, 1, 1))).draw(B, M, SRC, dev)
+    full = VolumeAugment(DST, flip_prob=(1, 1, 1), rotate_prob=1, zoom_prob=1, translate_prob=1, scale_intensity_prob=1, shift_intensity_prob=1, noise_prob=0,
+                         intensity_scale=1e-3)
+    t_full = full.draw(B, M, SRC, dev)
+    assert bool(t_ident.exact.all()) and bool(t_flip.exact.all()) and not bool(t_full.exact.any())
+    assert torch.equal(ident.apply(src, t_ident).view(torch.int16), ops.resize_pad_crop_i16(src, DST, -1.0).view(torch.int16))
+    table = AugmentParams(torch.empty(B, M, 32, dtype=torch.float32, device=dev))
+
+    arms = [
+        ("xvit_resize_pad_crop_i16", lambda: ops.resize_pad_crop_i16(src, DST, -1.0)),
+        ("exact path, identity", lambda: ident.apply(src, t_ident)),
+        ("exact path, three flips", lambda: ident.apply(src, t_flip)),
+        ("general path", lambda: ident.apply(src, t_full)),
+        ("draw kernel", lambda: ops.augment_draw(full.config, table.table, SRC, DST, 1)),
+        ("xvit_resize_pad_crop_i16 (again)", lambda: ops.resize_pad_crop_i16(src, DST, -1.0)),
+    ]
+    for _, fn in arms:          # warm-up: code objects, allocator
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in arms}
+    for _ in range(a.reps):
+        for name, fn in arms:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(a.inner):
+                fn()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / a.inner)      # us per launch
+    nvol = B * M
+    src_elems = nvol * min(SRC[0], DST[0]) * min(SRC[1], DST[1]) * min(SRC[2], DST[2])
+    nbytes = src_elems * 2 + nvol * DST[0] * DST[1] * DST[2] * 2
+    lines = [f"augment_bench: B={B} M={M} {SRC} int16 -> {DST} bf16, {a.reps} repeats x {a.inner} launches per arm, interleaved; "
+             f"{nbytes / 1e6:.1f} MB per launch (source region read once + destination)"]
+    med = {}
+    for name, _ in arms:
+        t = times[name]
+        med[name] = statistics.median(t)
+        rate = "" if name == "draw kernel" else f"  {nbytes / med[name] / 1e3:8.1f} GB/s"
+        lines.append(f"  {name:34s} median {med[name]:8.2f} us  (min {min(t):8.2f}, max {max(t):8.2f}){rate}")
+    same = ("xvit_resize_pad_crop_i16", "xvit_resize_pad_crop_i16 (again)")
+    spread = max(max(times[n]) - min(times[n]) for n in same)
+    ref = min(med[n] for n in same)
+    delta = med["exact path, identity"] - ref
+    ok = delta <= spread
+    lines.append(f"  identity vs xvit_resize_pad_crop_i16: {delta:+.2f} us ({med['exact path, identity'] / ref:.3f} x); spread between the identical arms' repeats "
+                 f"{spread:.2f} us; the two identical arms' medians differ by {abs(med[same[0]] - med[same[1]]):.2f} us -> {'OK' if ok else 'SLOWER THAN THE SPREAD ALLOWS'}")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
