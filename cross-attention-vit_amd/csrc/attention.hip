@@ -305,10 +305,8 @@ __device__ __forceinline__ void store_col0(const f32x16 (&acc)[2], float* dst, i
 // kept iff hash32(seed, ((b H + h) N + query) N + key) >= p 2^24 — the mask xvit_dropout applies to a contiguous [B, H, N, N]
 // tensor with the same seed — and scaled by 1/(1-p).  The row sums (softmax normaliser) use the probabilities BEFORE the
 // mask; the backward kernels regenerate the mask (nothing is stored) and, with O = P_drop V, delta = rowsum(dO O) is unchanged.
-struct DropArgs { uint32_t thr; float inv; uint64_t seed; const uint64_t* epoch; };   // epoch: xvit_common.h drop_seed_at (captured steps), or nullptr
-__device__ __forceinline__ DropArgs drop_at_run_time(DropArgs d) { d.seed = drop_seed_at(d.seed, d.epoch); return d; }
-__device__ __forceinline__ bool drop_keep(const DropArgs& d, uint64_t bh_base, int query, int key, int N) {
-  return (hash32(d.seed, bh_base + (uint64_t)query * (uint64_t)N + (uint64_t)key) & 0xFFFFFFu) >= d.thr;
+__device__ __forceinline__ bool drop_keep(const Dropout& d, uint64_t bh_base, int query, int key, int N) {
+  return d.keep(bh_base + (uint64_t)query * (uint64_t)N + (uint64_t)key);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -329,8 +327,8 @@ constexpr int FWD_KS = 4, FWD_SS = 2;
 template <int QB, bool DROP, bool PEEL>
 __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
                                                           int64_t sb, int64_t sn, bf16* __restrict__ o, int64_t osb, int64_t osn,
-                                                          float* __restrict__ lse, int H, int N, float scale, const DropArgs drop_in, float* __restrict__ cls_ws) {
-  const DropArgs drop = DROP ? drop_at_run_time(drop_in) : drop_in;   // captured steps: seed + device-side epoch
+                                                          float* __restrict__ lse, int H, int N, float scale, const Dropout drop_in, float* __restrict__ cls_ws) {
+  const Dropout drop = DROP ? drop_in.at_run_time() : drop_in;   // captured steps: seed + device-side epoch
   static_assert(!PEEL || (QB == 1 && !DROP), "the CLS peel is built for 32 queries per wave, no probability dropout");
 #ifdef XVIT_DEBUG_ATTN_TIMES
   const uint64_t wc_entry = wall_clock64();
@@ -580,7 +578,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 4 : 2) void attn_fwd_kernel(const bf
 // mask of (b, head) bh_base, this lane's query, the keys key0 + acc_row(i, h)
 template <bool DROP>
 __device__ __forceinline__ void dq_block(const ImgReader& rd, const XVIT_LDS char* kimg, const XVIT_LDS char* vimg, int kb, const bf16x8 (&qf)[4],
-                                         const bf16x8 (&dof)[4], float c, float nlse, float dlt, f32x16 (&dqacc)[2], const DropArgs& drop = DropArgs{},
+                                         const bf16x8 (&dof)[4], float c, float nlse, float dlt, f32x16 (&dqacc)[2], const Dropout& drop = Dropout{},
                                          uint64_t bh_base = 0, int query = 0, int key0 = 0, int h = 0, int N = 0) {
   f32x16 s, dp;
 #pragma unroll
@@ -614,9 +612,9 @@ template <bool DROP, bool PEEL>
 __global__ __launch_bounds__(256, PEEL ? XVIT_DQ_PEEL_WAVES : 2) void attn_bwd_dq_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
                                                              int64_t sb, int64_t sn, const bf16* __restrict__ o, const bf16* __restrict__ d_o, int64_t osb,
                                                              int64_t osn, const float* __restrict__ lse, float* __restrict__ nlse_ws,
-                                                             float* __restrict__ delta, bf16* __restrict__ dq, int H, int N, float scale, const DropArgs drop_in,
+                                                             float* __restrict__ delta, bf16* __restrict__ dq, int H, int N, float scale, const Dropout drop_in,
                                                              float* __restrict__ pdq) {
-  const DropArgs drop = DROP ? drop_at_run_time(drop_in) : drop_in;   // captured steps: seed + device-side epoch
+  const Dropout drop = DROP ? drop_in.at_run_time() : drop_in;   // captured steps: seed + device-side epoch
   static_assert(!PEEL || !DROP, "the CLS peel is built without probability dropout");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   XVIT_LDS char* smem = (XVIT_LDS char*)smem_raw;
@@ -749,7 +747,7 @@ __global__ __launch_bounds__(256, PEEL ? XVIT_DQ_PEEL_WAVES : 2) void attn_bwd_d
 template <bool DROP>
 __device__ __forceinline__ void dkv_block(const ImgReader& rd, const XVIT_LDS char* qimg, const XVIT_LDS char* doimg, const XVIT_LDS float* st_lse,
                                           const XVIT_LDS float* st_dlt, int qb, const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], float c, int lane,
-                                          f32x16 (&dkacc)[2], f32x16 (&dvacc)[2], const DropArgs& drop = DropArgs{}, uint64_t bh_base = 0,
+                                          f32x16 (&dkacc)[2], f32x16 (&dvacc)[2], const Dropout& drop = Dropout{}, uint64_t bh_base = 0,
                                           int query0 = 0, int key = 0, int N = 0) {
   const int h = lane >> 5;
   f32x16 s, dp, pr;
@@ -790,9 +788,9 @@ template <bool DROP, bool PEEL>
 __global__ __launch_bounds__(256, PEEL ? XVIT_DKV_PEEL_WAVES : 2) void attn_bwd_dkv_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
                                                               int64_t sb, int64_t sn, const bf16* __restrict__ o, const bf16* __restrict__ d_o, int64_t osb, int64_t osn,
                                                               const float* __restrict__ lse, const float* __restrict__ nlse_ws, const float* __restrict__ delta,
-                                                              bf16* __restrict__ dk, bf16* __restrict__ dv, int H, int N, float scale, const DropArgs drop_in,
+                                                              bf16* __restrict__ dk, bf16* __restrict__ dv, int H, int N, float scale, const Dropout drop_in,
                                                               float* __restrict__ pdk, float* __restrict__ pdv) {
-  const DropArgs drop = DROP ? drop_at_run_time(drop_in) : drop_in;   // captured steps: seed + device-side epoch
+  const Dropout drop = DROP ? drop_in.at_run_time() : drop_in;   // captured steps: seed + device-side epoch
   static_assert(!PEEL || !DROP, "the CLS peel is built without probability dropout");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   XVIT_LDS char* smem = (XVIT_LDS char*)smem_raw;
@@ -1145,8 +1143,6 @@ static int attn_check(const char* who, int B, int H, int N, int dh, int64_t sb, 
   return XVIT_OK;
 }
 
-static DropArgs drop_args(float p, uint64_t seed) { return DropArgs{(uint32_t)(p * 16777216.0f), 1.0f / (1.0f - p), seed, p > 0.f ? drop_epoch_ptr() : nullptr}; }
-
 // xvit_set_option("attn_peel"): 0 = never; 2 = token 0 off the tile grid whenever N = 64 m + 1 and no probability dropout; 1 (default) = that,
 // on grids of >= 768 workgroups only.  On a grid the chip holds in a single round a launch takes as long as its slowest workgroup,
 // and the peeled workgroup (8 tiles + token-0 prologue and post-loop block, then the merge launch) is not shorter than the grid
@@ -1184,7 +1180,7 @@ static void dispatch_form(bool peel, float dropout_p, const Go& go) {
 // softmax VALU issue, 12.4 VALU per MFMA at d_h = 64 — not by LDS reads or per-wave ILP) and worse at small batch.
 template <bool DROP, bool PEEL>
 static void launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, int64_t sb, int64_t sn, bf16* o, int64_t osb, int64_t osn, float* lse, float* cls_ws,
-                            int B, int H, int N, float scale, DropArgs da, hipStream_t s) {
+                            int B, int H, int N, float scale, Dropout da, hipStream_t s) {
   const int NK = PEEL ? N - 1 : N;   // PEEL: token 0 off the tile grid (see "CLS peel" above)
   launch_lds<attn_fwd_kernel<1, DROP, PEEL>, fwd_lds_bytes(PEEL), 256>(dim3((NK + 127) / 128, H, B), s, q, k, v, sb, sn, o, osb, osn, lse, H, N, scale, da, cls_ws);
   if (PEEL)
@@ -1193,7 +1189,7 @@ static void launch_attn_fwd(const bf16* q, const bf16* k, const bf16* v, int64_t
 
 template <bool DROP, bool PEEL>
 static void launch_attn_bwd(const bf16* q, const bf16* k, const bf16* v, int64_t sb, int64_t sn, const bf16* o, const bf16* d_o, int64_t osb, int64_t osn,
-                            const float* lse, float* ws, bf16* dq, bf16* dk, bf16* dv, int B, int H, int N, float scale, DropArgs da, hipStream_t s) {
+                            const float* lse, float* ws, bf16* dq, bf16* dk, bf16* dv, int B, int H, int N, float scale, Dropout da, hipStream_t s) {
   const BwdWorkspace w(B, H, N, PEEL);
   const int NK = PEEL ? N - 1 : N;
   const dim3 grid((NK + 127) / 128, H, B);
@@ -1220,7 +1216,7 @@ extern "C" int xvit_attn_fwd(const void* q, const void* k, const void* v, int64_
                  (long long)fwd_workspace_floats(B, H, N) * 4);
   dispatch_form(peel, dropout_p, [&](auto drop, auto pl) {
     launch_attn_fwd<decltype(drop)::value, decltype(pl)::value>((const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn, (bf16*)o, osb, osn, lse, workspace, B, H, N,
-                                                                 scale, drop_args(dropout_p, dropout_seed), (hipStream_t)stream);
+                                                                 scale, Dropout(dropout_p, dropout_seed), (hipStream_t)stream);
   });
   return check_launch("xvit_attn_fwd");
 }
@@ -1237,7 +1233,7 @@ extern "C" int xvit_attn_bwd(const void* q, const void* k, const void* v, int64_
                (long long)workspace_bytes, (long long)need);
   dispatch_form(peel, dropout_p, [&](auto drop, auto pl) {
     launch_attn_bwd<decltype(drop)::value, decltype(pl)::value>((const bf16*)q, (const bf16*)k, (const bf16*)v, sb, sn, (const bf16*)o, (const bf16*)d_o, osb, osn, lse,
-                                                                 workspace, (bf16*)dq, (bf16*)dk, (bf16*)dv, B, H, N, scale, drop_args(dropout_p, dropout_seed),
+                                                                 workspace, (bf16*)dq, (bf16*)dk, (bf16*)dv, B, H, N, scale, Dropout(dropout_p, dropout_seed),
                                                                  (hipStream_t)stream);
   });
   return check_launch("xvit_attn_bwd");

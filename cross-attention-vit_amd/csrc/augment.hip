@@ -8,9 +8,8 @@
 namespace xvit {
 
 constexpr uint64_t kCounterStride = 0xD1B54A32D192ED03ull;   // the odd constant of drop_seed_at
-constexpr float kInv24 = 1.0f / 16777216.0f;
+constexpr float kInv24 = 1.0f / kTwo24;
 
-__device__ __forceinline__ uint32_t draw24(uint64_t seed, uint64_t idx) { return hash32(seed, idx) & 0xFFFFFFu; }
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) { return (float)draw24(seed, idx) * kInv24; }   // [0, 1), exact
 
 struct AugGeom {

@@ -9,16 +9,7 @@ namespace xvit {
 constexpr int XA_THREADS = 256;
 constexpr int XA_DH = 64;
 
-__device__ __forceinline__ float block_reduce(float v, bool is_max, float* red /*[4]*/) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-#pragma unroll
-  for (int w = 1; w < XA_THREADS / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
+constexpr int XA_WAVES = XA_THREADS / 64;
 
 // dot of this thread's 8 dims of a (loaded once) with the 8 dims of row n of mat; 8 lanes per row
 __device__ __forceinline__ float row_dot8(const float (&a)[8], const bf16* mat, int64_t stride_n, int n, int part) {
@@ -37,9 +28,8 @@ __device__ __forceinline__ float row_dot8(const float (&a)[8], const bf16* mat, 
 __global__ __launch_bounds__(XA_THREADS) void cls_xattn_fwd_kernel(const bf16* __restrict__ q, int64_t ldq, const float* __restrict__ q_f32, int64_t ldqf,
                                                                    const bf16* __restrict__ k, const bf16* __restrict__ v, int64_t sb, int64_t sn,
                                                                    bf16* __restrict__ o, int64_t ldo, float* __restrict__ o_f32, int64_t ldof,
-                                                                   float* __restrict__ p, int H, int N, float scale, float drop_p,
-                                                                   uint64_t drop_seed_in, const uint64_t* __restrict__ drop_epoch) {
-  const uint64_t drop_seed = drop_seed_at(drop_seed_in, drop_epoch);
+                                                                   float* __restrict__ p, int H, int N, float scale, const Dropout drop_in) {
+  const Dropout drop = drop_in.at_run_time();
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* sc = (float*)smem_raw;            // [N] scores -> probabilities
   float* red = sc + ((N + 3) & ~3);        // [4] + [32][64] partial outputs
@@ -65,24 +55,21 @@ __global__ __launch_bounds__(XA_THREADS) void cls_xattn_fwd_kernel(const bf16* _
     if (part == 0) sc[n] = s;
     mx = fmaxf(mx, s);
   }
-  mx = block_reduce(mx, true, red);
+  mx = block_reduce<XA_WAVES>(mx, MaxOp{}, red);
   float sum = 0.f;
   for (int n = tid; n < N; n += XA_THREADS) {
     const float e = __expf(sc[n] - mx);
     sc[n] = e;
     sum += e;
   }
-  sum = block_reduce(sum, false, red);
+  sum = block_reduce<XA_WAVES>(sum, SumOp{}, red);
   const float inv = 1.0f / sum;
   float* prow = p + ((int64_t)b * H + head) * N;
-  const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
-  const float dinv = 1.0f / (1.0f - drop_p);
   const uint64_t pidx = ((uint64_t)b * H + head) * N;
   for (int n = tid; n < N; n += XA_THREADS) {
     const float pr = sc[n] * inv;
     prow[n] = pr;                                   // saved pre-dropout (backward regenerates the mask)
-    const bool keep = drop_p <= 0.f || (hash32(drop_seed, pidx + n) & 0xFFFFFFu) >= thr;
-    sc[n] = keep ? pr * (drop_p > 0.f ? dinv : 1.0f) : 0.f;
+    sc[n] = !drop.on() || drop.keep(pidx + n) ? pr * drop.inv : 0.f;    // off: inv = 1
   }
   __syncthreads();
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -109,8 +96,8 @@ __global__ __launch_bounds__(XA_THREADS) void cls_xattn_bwd_kernel(const bf16* _
                                                                    const float* __restrict__ p, const bf16* __restrict__ d_o, int64_t lddo,
                                                                    float* __restrict__ dq, int64_t lddq, bf16* __restrict__ dk,
                                                                    bf16* __restrict__ dv, float* __restrict__ coef, int H, int N, float scale,
-                                                                   float drop_p, uint64_t drop_seed_in, const uint64_t* __restrict__ drop_epoch) {
-  const uint64_t drop_seed = drop_seed_at(drop_seed_in, drop_epoch);
+                                                                   const Dropout drop_in) {
+  const Dropout drop = drop_in.at_run_time();
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* ds = (float*)smem_raw;            // [N] dp -> ds
   float* red = ds + ((N + 3) & ~3);
@@ -128,20 +115,19 @@ __global__ __launch_bounds__(XA_THREADS) void cls_xattn_bwd_kernel(const bf16* _
     for (int e = 0; e < 8; ++e) { qv[e] = bf2f(t[e]); gov[e] = bf2f(g[e]); }
   }
   // p' = mask * p / (1-pd);  dp[n] = mask/(1-pd) * (do . v[n]);   dsum = sum_n p[n] dp[n]
-  const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
-  const float dinv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
   const uint64_t pidx = ((uint64_t)b * H + head) * N;
+  auto mask = [&](int n) { return !drop.on() || drop.keep(pidx + n) ? drop.inv : 0.f; };   // off: inv = 1
   float dsum = 0.f;
   for (int n = slice; n < N; n += 32) {
-    const float mk = (drop_p <= 0.f || (hash32(drop_seed, pidx + n) & 0xFFFFFFu) >= thr) ? dinv : 0.f;
+    const float mk = mask(n);
     const float dp = row_dot8(gov, v + boff, sn, n, part) * mk;
     if (part == 0) { ds[n] = dp; dsum += prow[n] * dp; }
   }
-  dsum = block_reduce(dsum, false, red);
+  dsum = block_reduce<XA_WAVES>(dsum, SumOp{}, red);
   // ds[n] = p (dp - dsum);  dq += scale * ds[n] k[n];  dk[n] = scale * ds[n] q;  dv[n] = p[n] do
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int n = slice; n < N; n += 32) {
-    const float mk = (drop_p <= 0.f || (hash32(drop_seed, pidx + n) & 0xFFFFFFu) >= thr) ? dinv : 0.f;
+    const float mk = mask(n);
     const float pr0 = prow[n];
     const float pr = pr0 * mk;                       // dropped probability feeds dv
     const float dsn = pr0 * (ds[n] - dsum) * scale;
@@ -222,8 +208,7 @@ __global__ __launch_bounds__(256) void xattn_kv_dgrad_kernel(const float* __rest
           const f32x4 cf = *(const f32x4*)(cl + rr * J2 + j4);   // same address on every lane: an LDS broadcast
           o += cf[0] * r[j4] + cf[1] * r[j4 + 1] + cf[2] * r[j4 + 2] + cf[3] * r[j4 + 3];
         }
-        const bf16x4 ob = {f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
-        *(bf16x4*)(dhn + ((int64_t)b * N + nb + rr) * lddh + c0) = ob;
+        *(bf16x4*)(dhn + ((int64_t)b * N + nb + rr) * lddh + c0) = to_bf16x4(o);
       }
     }
   }
@@ -244,15 +229,10 @@ extern "C" int xvit_cls_xattn_fwd(const void* q, int64_t ldq, const float* q_f32
   XVIT_REQUIRE(B > 0 && H > 0 && N > 0 && B <= 65535, "xvit_cls_xattn_fwd: bad B/H/N");
   XVIT_REQUIRE((!q || ldq % 8 == 0) && sb % 8 == 0 && sn % 8 == 0, "xvit_cls_xattn_fwd: strides must be multiples of 8 elements");
   XVIT_REQUIRE(xa_lds(N) <= 160 * 1024, "xvit_cls_xattn_fwd: N=%d too long for the LDS score row", N);
-  const size_t lds = xa_lds(N);
-  static size_t attr = 0;
-  if (lds > 64 * 1024 && lds > attr) {
-    (void)hipFuncSetAttribute((const void*)cls_xattn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = lds;
-  }
-  hipLaunchKernelGGL(cls_xattn_fwd_kernel, dim3(H, B), dim3(XA_THREADS), lds, (hipStream_t)stream, (const bf16*)q, ldq, q_f32, ldqf, (const bf16*)k,
-                     (const bf16*)v, sb, sn, (bf16*)o, ldo, o_f32, ldof, p, H, N, scale, drop_p, drop_seed,
-                     drop_p > 0.f ? drop_epoch_ptr() : nullptr);
+  const hipError_t e = launch_dyn_lds<cls_xattn_fwd_kernel>(dim3(H, B), dim3(XA_THREADS), xa_lds(N), (hipStream_t)stream, (const bf16*)q, ldq, q_f32, ldqf, (const bf16*)k,
+                                                            (const bf16*)v, sb, sn, (bf16*)o, ldo, o_f32, ldof, p, H, N, scale, Dropout(drop_p, drop_seed));
+  XVIT_REQUIRE(e == hipSuccess, "xvit_cls_xattn_fwd: N=%d needs %lld bytes of LDS and the kernel's limit could not be raised (%s)", N, (long long)xa_lds(N),
+               hipGetErrorString(e));
   return check_launch("xvit_cls_xattn_fwd");
 }
 
@@ -265,15 +245,10 @@ extern "C" int xvit_cls_xattn_bwd(const void* q, int64_t ldq, const void* k, con
   XVIT_REQUIRE(B > 0 && H > 0 && N > 0 && B <= 65535, "xvit_cls_xattn_bwd: bad B/H/N");
   XVIT_REQUIRE(ldq % 8 == 0 && lddo % 8 == 0 && sb % 8 == 0 && sn % 8 == 0, "xvit_cls_xattn_bwd: strides must be multiples of 8 elements");
   XVIT_REQUIRE(xa_lds(N) <= 160 * 1024, "xvit_cls_xattn_bwd: N=%d too long for the LDS score row", N);
-  const size_t lds = xa_lds(N);
-  static size_t attr = 0;
-  if (lds > 64 * 1024 && lds > attr) {
-    (void)hipFuncSetAttribute((const void*)cls_xattn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = lds;
-  }
-  hipLaunchKernelGGL(cls_xattn_bwd_kernel, dim3(H, B), dim3(XA_THREADS), lds, (hipStream_t)stream, (const bf16*)q, ldq, (const bf16*)k, (const bf16*)v, sb,
-                     sn, p, (const bf16*)d_o, lddo, dq, lddq, (bf16*)dk, (bf16*)dv, coef, H, N, scale, drop_p, drop_seed,
-                     drop_p > 0.f ? drop_epoch_ptr() : nullptr);
+  const hipError_t e = launch_dyn_lds<cls_xattn_bwd_kernel>(dim3(H, B), dim3(XA_THREADS), xa_lds(N), (hipStream_t)stream, (const bf16*)q, ldq, (const bf16*)k, (const bf16*)v,
+                                                            sb, sn, p, (const bf16*)d_o, lddo, dq, lddq, (bf16*)dk, (bf16*)dv, coef, H, N, scale, Dropout(drop_p, drop_seed));
+  XVIT_REQUIRE(e == hipSuccess, "xvit_cls_xattn_bwd: N=%d needs %lld bytes of LDS and the kernel's limit could not be raised (%s)", N, (long long)xa_lds(N),
+               hipGetErrorString(e));
   return check_launch("xvit_cls_xattn_bwd");
 }
 
@@ -290,9 +265,10 @@ extern "C" int xvit_xattn_kv_dgrad(const float* coef, const float* R, void* dhn,
   const int slices = xkv_slices(B, N), rpb = (N + slices - 1) / slices;
   const dim3 grid(slices, B), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (2 * H <= 8) hipLaunchKernelGGL((xattn_kv_dgrad_kernel<8>), grid, block, 0, s, coef, R, (bf16*)dhn, lddh, H, N, d, rpb);
-  else if (2 * H <= 16) hipLaunchKernelGGL((xattn_kv_dgrad_kernel<16>), grid, block, 0, s, coef, R, (bf16*)dhn, lddh, H, N, d, rpb);
-  else if (2 * H <= 24) hipLaunchKernelGGL((xattn_kv_dgrad_kernel<24>), grid, block, 0, s, coef, R, (bf16*)dhn, lddh, H, N, d, rpb);
-  else hipLaunchKernelGGL((xattn_kv_dgrad_kernel<32>), grid, block, 0, s, coef, R, (bf16*)dhn, lddh, H, N, d, rpb);
+  auto launch = [&](auto j2) { hipLaunchKernelGGL((xattn_kv_dgrad_kernel<decltype(j2)::value>), grid, block, 0, s, coef, R, (bf16*)dhn, lddh, H, N, d, rpb); };
+  if (2 * H <= 8) launch(Int<8>{});
+  else if (2 * H <= 16) launch(Int<16>{});
+  else if (2 * H <= 24) launch(Int<24>{});
+  else launch(Int<32>{});
   return check_launch("xvit_xattn_kv_dgrad");
 }

@@ -124,10 +124,10 @@ __device__ __forceinline__ void act4(f32x4& v, f32x4& d, const bf16x4 z) {
 }
 // Dropout mask keyed by (seed, batch-local element index idx .. idx + 3): regenerated in the backward, never stored.
 __device__ __forceinline__ void dropout4(const GemmParams& p, f32x4& v, uint64_t idx) {
-  const uint32_t thr = (uint32_t)(p.drop_p * 16777216.0f);
+  const uint32_t thr = (uint32_t)(p.drop_p * kTwo24);
   const uint64_t seed = drop_seed_at(p.drop_seed, p.drop_epoch);
 #pragma unroll
-  for (int c = 0; c < 4; ++c) v[c] = (hash32(seed, idx + c) & 0xFFFFFFu) >= thr ? v[c] * p.drop_inv : 0.f;
+  for (int c = 0; c < 4; ++c) v[c] = draw24(seed, idx + c) >= thr ? v[c] * p.drop_inv : 0.f;
 }
 // Column sums of the stored values: a lane's 4 columns are the same in every row it visits, so they are summed in registers,
 // then over the lanes that share the columns (l, l + GROUP, l + 2 GROUP, ...: GROUP lanes cover one row), and reach memory as ONE
@@ -159,8 +159,7 @@ __device__ __forceinline__ f32x4 epilogue_apply(const GemmParams& p, f32x4 v, in
     act4<XVIT_ACT_GELU>(v, d, bf16x4{});
     if (aux) {   // the pre-activation, or (aux_mode 1) the derivative the backward will multiply by
       const f32x4 s = p.aux_deriv ? d : zv;
-      bf16x4 z = {f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
-      *(bf16x4*)(aux + (int64_t)row * p.ldaux + col) = z;
+      *(bf16x4*)(aux + (int64_t)row * p.ldaux + col) = to_bf16x4(s);
     }
   } else if (ACT == XVIT_ACT_DGELU) {
     const bf16x4 z = *(const bf16x4*)(aux + (int64_t)row * p.ldaux + col);
@@ -179,8 +178,7 @@ __device__ __forceinline__ f32x4 epilogue_apply(const GemmParams& p, f32x4 v, in
     if (p.accumulate) v += *(const f32x4*)dst;
     *(f32x4*)dst = v;
   } else {
-    bf16x4 o = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-    *(bf16x4*)((bf16*)p.C + cb + orow * p.ldc + col) = o;
+    *(bf16x4*)((bf16*)p.C + cb + orow * p.ldc + col) = to_bf16x4(v);
   }
   return v;
 }
@@ -614,8 +612,7 @@ __device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32
       act4<XVIT_ACT_GELU>(v, d, bf16x4{});
       if (e.has_aux) {
         const f32x4 sv = p.aux_deriv ? d : zv;
-        bf16x4 z = {f2bf(sv[0]), f2bf(sv[1]), f2bf(sv[2]), f2bf(sv[3])};
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, z), e.raux, ok ? e.aux : OOB, 0, XVIT_EPI_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, to_bf16x4(sv)), e.raux, ok ? e.aux : OOB, 0, XVIT_EPI_STORE_AUX);
       }
     } else if (ACT == XVIT_ACT_DGELU) {
       const bf16x4 z = __builtin_bit_cast(bf16x4, auxv);
@@ -630,8 +627,7 @@ __device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32
       if (p.accumulate) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(e.rc, off, 0, 0));
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), e.rc, off, 0, XVIT_EPI_STORE_AUX);
     } else {
-      bf16x4 o = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, o), e.rc, ok ? e.c : OOB, 0, XVIT_EPI_STORE_AUX);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, to_bf16x4(v)), e.rc, ok ? e.c : OOB, 0, XVIT_EPI_STORE_AUX);
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) e.csum[c] += ok ? v[c] : 0.f;   // the lane's 4 columns are the same in every body
@@ -764,8 +760,7 @@ __device__ __forceinline__ void wide_issue_aux(const GemmParams& p, const WideEp
 }
 
 __device__ __forceinline__ u32x4_t pack_bf16x8(const f32x4& a, const f32x4& b) {
-  const bf16x8 o = {f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(b[0]), f2bf(b[1]), f2bf(b[2]), f2bf(b[3])};
-  return __builtin_bit_cast(u32x4_t, o);
+  return __builtin_bit_cast(u32x4_t, to_bf16x8(a, b));
 }
 
 // activation + dropout on 4 of the lane's 8 elements (columns col .. col + 3 of row `row`)
@@ -774,8 +769,7 @@ __device__ __forceinline__ void wide_half(const GemmParams& p, f32x4& v, const b
   f32x4 d;
   act4<ACT>(v, d, z);
   if (ACT == ACT_GELU_D) {   // the derivative for the aux tensor, packed to bf16 at once (registers)
-    const bf16x4 db = {f2bf(d[0]), f2bf(d[1]), f2bf(d[2]), f2bf(d[3])};
-    dpack = __builtin_bit_cast(u32x2_t, db);
+    dpack = __builtin_bit_cast(u32x2_t, to_bf16x4(d));
   }
   if (DROP) dropout4(p, v, idx);
 }

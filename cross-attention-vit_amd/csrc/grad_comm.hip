@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void grad_pack_kernel(const PackTable t, 
     const int64_t v = v0 + (int64_t)k * kThreads;
     if (v < nv) {
       const f32x4 x = a[k] * scale, y = c[k] * scale;
-      ((bf16x8*)out)[v] = bf16x8{f2bf(x[0]), f2bf(x[1]), f2bf(x[2]), f2bf(x[3]), f2bf(y[0]), f2bf(y[1]), f2bf(y[2]), f2bf(y[3])};
+      ((bf16x8*)out)[v] = to_bf16x8(x, y);
     }
   }
 }

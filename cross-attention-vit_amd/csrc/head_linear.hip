@@ -55,7 +55,7 @@ __global__ __launch_bounds__(64) void head_rows_kernel(const HeadParams p) {
   const int col = tn * 32 + r;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int row = tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * hl;
+    const int row = tm * 32 + acc_row(i, hl);
     if (row < p.B) {
       p.out[(int64_t)row * p.out_sb + (int64_t)h * p.out_sh + col] = acc[i];
       if (p.out_bf16) p.out_bf16[(int64_t)row * p.ob_sb + (int64_t)h * p.ob_sh + col] = f2bf(acc[i]);
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void head_cols_kernel(const HeadParams p) {
   // the four K-quarters meet in LDS and are added in wave order (fixed: bit-reproducible)
   if (wave > 0) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) part[wave - 1][((i & 3) + 8 * (i >> 2) + 4 * hl) * 33 + r] = acc[i];
+    for (int i = 0; i < 16; ++i) part[wave - 1][acc_row(i, hl) * 33 + r] = acc[i];
   }
   __syncthreads();
   if (wave > 0) return;
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void head_cols_kernel(const HeadParams p) {
   const float bs = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int rl = (i & 3) + 8 * (i >> 2) + 4 * hl, row = tm * 32 + rl;
+    const int rl = acc_row(i, hl), row = tm * 32 + rl;
     if (row < p.B) {
       const float v = ((acc[i] + part[0][rl * 33 + r]) + part[1][rl * 33 + r]) + part[2][rl * 33 + r];
       const float o = fmaf(v, p.rs ? p.rs[(int64_t)row * p.rs_ld + h] : 1.f, p.bias_scale ? bs * p.bias_scale[(int64_t)row * p.bsc_ld + h] : bs);
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void head_wgrad_kernel(const HeadParams p) {
     float a[16], w[16], sc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int b = k0 + 8 * (i >> 2) + 4 * hl + (i & 3);
+      const int b = k0 + acc_row(i, hl);
       const bool in = b < p.B;
       const int bc = in ? b : 0;
       sc[i] = in ? (p.rs ? p.rs[(int64_t)bc * p.rs_ld + h] : 1.f) : 0.f;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void head_wgrad_kernel(const HeadParams p) {
   const int col = tn * 32 + r;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int row = h * HL_DH + tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * hl;
+    const int row = h * HL_DH + tm * 32 + acc_row(i, hl);
     p.out[(int64_t)row * p.ldo + col] = acc[i];
   }
 }
@@ -139,16 +139,29 @@ __global__ __launch_bounds__(64) void head_wgrad_kernel(const HeadParams p) {
 // Dropout on the probabilities (drop_p > 0; mask of xvit_dropout on a contiguous [B, H, N] tensor, the one xvit_cls_xattn_fwd applies):
 //   e_m = the kept weights (the operand of the row-sum GEMM; e itself stays whole for the backward), and with inv = 1 / (1 - drop_p)
 //   stat[0][b, h] = rz,  stat[1][b, h] = rz inv (row scale of Wv_h S),  stat[2][b, h] = rz inv sum_n e_m (weight of bv).
+// The reduction over the threads of a column, in two steps around the caller's barrier: col_fold over the lanes with equal (lane & 15)
+// inside a wave — lanes < 16 then store to red[wave][lane] — and col_across over the waves, in wave order (fixed: bit-reproducible).
+template <class Op>
+__device__ __forceinline__ float col_fold(float v, Op op) {
+  v = op(v, __shfl_xor(v, 16));
+  return op(v, __shfl_xor(v, 32));
+}
+template <int NW, class Op>
+__device__ __forceinline__ float col_across(const float (&red)[NW][16], int col, Op op) {
+  float v = red[0][col];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) v = op(v, red[w][col]);
+  return v;
+}
+
 constexpr int SM_T = 1024;   // 64 rows x 16 columns per pass: the kernels are chains of dependent row passes, so more rows per pass = fewer trips
 __global__ __launch_bounds__(SM_T) void cls_softmax_kernel(const float* __restrict__ s, int64_t ld, bf16* __restrict__ e, int64_t lde, float* __restrict__ rz,
-                                                           int H, int N, float scale, bf16* __restrict__ e_m, float drop_p, uint64_t drop_seed_in,
-                                                           const uint64_t* __restrict__ drop_epoch) {
+                                                           int H, int N, float scale, bf16* __restrict__ e_m, const Dropout drop_in) {
   constexpr int NW = SM_T / 64, RP = SM_T / 16;
   __shared__ float red[NW][16];
   __shared__ float redm[NW][16];
-  const bool drop = drop_p > 0.f;
-  const uint64_t drop_seed = drop ? drop_seed_at(drop_seed_in, drop_epoch) : 0;
-  const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
+  const bool drop = drop_in.on();
+  const Dropout dr = drop ? drop_in.at_run_time() : drop_in;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* sb = s + (int64_t)b * N * ld;
   bf16* eb = e + (int64_t)b * N * lde;
@@ -158,45 +171,36 @@ __global__ __launch_bounds__(SM_T) void cls_softmax_kernel(const float* __restri
   float mx = -INFINITY;
   if (col < H)
     for (int n = r0; n < N; n += RP) mx = fmaxf(mx, sb[(int64_t)n * ld + col]);
-  // reduce over the threads of a column: lanes with equal (lane & 15) inside a wave, then the waves (fixed order)
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  mx = col_fold(mx, MaxOp{});
   if (lane < 16) red[wave][lane] = mx;
   __syncthreads();
-  mx = red[0][col];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) mx = fmaxf(mx, red[w][col]);
+  mx = col_across(red, col, MaxOp{});
   __syncthreads();
   float sum = 0.f, summ = 0.f;
-  const float c = scale * 1.4426950408889634f;
+  const float c = scale * LOG2E;
   const uint64_t pidx = ((uint64_t)b * H + col) * (uint64_t)N;
   for (int n = r0; n < N; n += RP) {
     bf16 w = f2bf(0.f), wm = f2bf(0.f);
     if (col < H) {
       w = f2bf(__builtin_amdgcn_exp2f((sb[(int64_t)n * ld + col] - mx) * c));
       sum += bf2f(w);
-      if (drop && (hash32(drop_seed, pidx + n) & 0xFFFFFFu) >= thr) { wm = w; summ += bf2f(w); }
+      if (drop && dr.keep(pidx + n)) { wm = w; summ += bf2f(w); }
     }
     if (col < lde) {
       eb[(int64_t)n * lde + col] = w;
       if (drop) emb[(int64_t)n * lde + col] = wm;
     }
   }
-  sum += __shfl_xor(sum, 16);
-  sum += __shfl_xor(sum, 32);
-  summ += __shfl_xor(summ, 16);
-  summ += __shfl_xor(summ, 32);
+  sum = col_fold(sum, SumOp{});
+  summ = col_fold(summ, SumOp{});
   if (lane < 16) { red[wave][lane] = sum; redm[wave][lane] = summ; }
   __syncthreads();
   if (tid < H) {
-    float t = red[0][tid], tm = redm[0][tid];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) { t += red[w][tid]; tm += redm[w][tid]; }
-    const float z = 1.0f / t;
+    const float z = 1.0f / col_across(red, tid, SumOp{}), tm = col_across(redm, tid, SumOp{});
     const int64_t BH = (int64_t)gridDim.x * H;           // rz is stat[0] of a [3][B][H] block when dropout is on
     rz[(int64_t)b * H + tid] = z;
     if (drop) {
-      const float zi = z / (1.0f - drop_p);
+      const float zi = z / (1.0f - dr.p);
       rz[BH + (int64_t)b * H + tid] = zi;
       rz[2 * BH + (int64_t)b * H + tid] = zi * tm;
     }
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(SM_T) void cls_softmax_kernel(const float* __restri
 // its place in ds, and the second half of coef is p' = m p / (1 - drop_p) — the weights that met the values.
 __global__ __launch_bounds__(SM_T) void cls_softmax_bwd_kernel(const bf16* __restrict__ e, int64_t lde, const float* __restrict__ rz, const float* __restrict__ dp, int64_t ldp,
                                                                float* __restrict__ coef, bf16* __restrict__ dsb, int64_t ldb, int H, int N, float scale,
-                                                               float drop_p, uint64_t drop_seed_in, const uint64_t* __restrict__ drop_epoch) {
+                                                               const Dropout drop_in) {
   constexpr int NW = SM_T / 64, RP = SM_T / 16;
   __shared__ float red[NW][16];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -217,22 +221,17 @@ __global__ __launch_bounds__(SM_T) void cls_softmax_bwd_kernel(const bf16* __res
   const bf16* eb = e + (int64_t)b * N * lde;
   const float* dpb = dp + (int64_t)b * N * ldp;
   const float z = col < H ? rz[(int64_t)b * H + col] : 0.f;
-  const bool drop = drop_p > 0.f;
-  const uint64_t drop_seed = drop ? drop_seed_at(drop_seed_in, drop_epoch) : 0;
-  const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
-  const float inv = drop ? 1.0f / (1.0f - drop_p) : 1.0f;
+  const bool drop = drop_in.on();
+  const Dropout dr = drop ? drop_in.at_run_time() : drop_in;   // off: inv = 1
   const uint64_t pidx = ((uint64_t)b * H + col) * (uint64_t)N;
-  auto mk = [&](int n) { return !drop || (hash32(drop_seed, pidx + n) & 0xFFFFFFu) >= thr ? inv : 0.f; };
+  auto mk = [&](int n) { return !drop || dr.keep(pidx + n) ? dr.inv : 0.f; };
   float dsum = 0.f;
   if (col < H)
     for (int n = r0; n < N; n += RP) dsum = fmaf(bf2f(eb[(int64_t)n * lde + col]) * z, mk(n) * dpb[(int64_t)n * ldp + col], dsum);
-  dsum += __shfl_xor(dsum, 16);
-  dsum += __shfl_xor(dsum, 32);
+  dsum = col_fold(dsum, SumOp{});
   if (lane < 16) red[wave][lane] = dsum;
   __syncthreads();
-  dsum = red[0][col];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) dsum += red[w][col];
+  dsum = col_across(red, col, SumOp{});
   float* cb = coef + (int64_t)b * N * 2 * H;
   bf16* db = dsb + (int64_t)b * N * ldb;
   for (int n = r0; n < N; n += RP) {
@@ -314,8 +313,8 @@ extern "C" int xvit_cls_softmax_fwd(const float* s, int64_t lds, void* e_bf16, i
   XVIT_REQUIRE(s && e_bf16 && rz, "xvit_cls_softmax_fwd: null pointer");
   XVIT_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 16 && lds >= H && lde >= H && lde <= 16, "xvit_cls_softmax_fwd: need H <= 16, lds >= H, H <= lde <= 16 (B=%d H=%d N=%d)", B, H, N);
   XVIT_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || e_masked_bf16), "xvit_cls_softmax_fwd: dropout_p must be in [0, 1) and needs e_masked");
-  hipLaunchKernelGGL(cls_softmax_kernel, dim3(B), dim3(SM_T), 0, (hipStream_t)stream, s, lds, (bf16*)e_bf16, lde, rz, H, N, scale, (bf16*)e_masked_bf16, dropout_p,
-                     dropout_seed, dropout_p > 0.f ? drop_epoch_ptr() : nullptr);
+  hipLaunchKernelGGL(cls_softmax_kernel, dim3(B), dim3(SM_T), 0, (hipStream_t)stream, s, lds, (bf16*)e_bf16, lde, rz, H, N, scale, (bf16*)e_masked_bf16,
+                     Dropout(dropout_p, dropout_seed));
   return check_launch("xvit_cls_softmax_fwd");
 }
 
@@ -325,7 +324,7 @@ extern "C" int xvit_cls_softmax_bwd(const void* e_bf16, int64_t lde, const float
   XVIT_REQUIRE(B > 0 && N > 0 && H > 0 && H <= 16 && lde >= H && ldp >= H && ldb >= H && ldb <= 16, "xvit_cls_softmax_bwd: need H <= 16, lde, ldp >= H, H <= ldb <= 16");
   XVIT_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "xvit_cls_softmax_bwd: dropout_p must be in [0, 1)");
   hipLaunchKernelGGL(cls_softmax_bwd_kernel, dim3(B), dim3(SM_T), 0, (hipStream_t)stream, (const bf16*)e_bf16, lde, rz, dp, ldp, coef, (bf16*)ds_bf16, ldb, H, N, scale,
-                     dropout_p, dropout_seed, dropout_p > 0.f ? drop_epoch_ptr() : nullptr);
+                     Dropout(dropout_p, dropout_seed));
   return check_launch("xvit_cls_softmax_bwd");
 }
 

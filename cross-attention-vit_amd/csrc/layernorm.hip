@@ -49,10 +49,7 @@ __global__ __launch_bounds__(LN_WAVES * 64) void ln_fwd_kernel(const float* __re
         f32x4 of;
 #pragma unroll
         for (int e = 0; e < 4; ++e) of[e] = (v[i][e] - mu) * rs * g[e] + b[e];
-        if (y) {
-          bf16x4 o = {f2bf(of[0]), f2bf(of[1]), f2bf(of[2]), f2bf(of[3])};
-          *(bf16x4*)(y + (int64_t)row * ldy + c * 4) = o;
-        }
+        if (y) *(bf16x4*)(y + (int64_t)row * ldy + c * 4) = to_bf16x4(of);
         if (yf) *(f32x4*)(yf + (int64_t)row * ldyf + c * 4) = of;   // the single-token CLS path keeps its operands in fp32
       }
     }
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(LNB_WAVES * 64, V <= 3 ? XVIT_LNB_OCC : (V <= 4 ? 2
       const int c = lane + i * 64;
       const bool ok = c < nv;
       in.xv[i] = ok ? xr[c] : f32x4{0.f, 0.f, 0.f, 0.f};
-      in.dv[i] = ok ? *(const bf16x4*)(dyr + c * 4) : bf16x4{f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
+      in.dv[i] = ok ? *(const bf16x4*)(dyr + c * 4) : to_bf16x4(f32x4{0.f, 0.f, 0.f, 0.f});
       in.rv[i] = (ok && dres) ? *(const f32x4*)(dres + (int64_t)row * lddres + c * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   };
@@ -132,10 +129,7 @@ __global__ __launch_bounds__(LNB_WAVES * 64, V <= 3 ? XVIT_LNB_OCC : (V <= 4 ? 2
         }
         sx[i] += o;
         *(f32x4*)(dx + (int64_t)row * lddx + c * 4) = o;
-        if (dxb) {
-          bf16x4 ob = {f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
-          *(bf16x4*)(dxb + (int64_t)row * lddxb + c * 4) = ob;
-        }
+        if (dxb) *(bf16x4*)(dxb + (int64_t)row * lddxb + c * 4) = to_bf16x4(o);
       }
     }
   };
@@ -220,9 +214,14 @@ extern "C" int64_t xvit_layernorm_bwd_workspace_bytes(int rows, int d) {
   return (int64_t)g * 4 * d * (int64_t)sizeof(float);
 }
 
-static int ln_grid(int rows) {
-  const int want = (rows + LN_WAVES - 1) / LN_WAVES;
-  return want < 2048 ? want : 2048;  // grid-stride beyond 8 blocks/CU
+static int ln_grid(int rows) { return grid_for(rows, LN_WAVES, 2048); }   // a row per wave; grid-stride beyond 8 blocks/CU
+
+// f(Int<V>{}) for the V (float4 per lane) of the instantiation that holds a row of d floats: 3 (d <= 768), 4 (d <= 1024) or 16
+template <class F>
+static auto ln_with_v(int d, F&& f) {
+  if (d <= 768) return f(Int<3>{});
+  if (d <= 1024) return f(Int<4>{});
+  return f(Int<16>{});
 }
 
 extern "C" int xvit_layernorm_fwd(const float* x, const float* x_alt, int64_t ldx, int seq_len, int64_t ld_alt, const float* gamma, const float* beta,
@@ -236,9 +235,9 @@ extern "C" int xvit_layernorm_fwd(const float* x, const float* x_alt, int64_t ld
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(ln_grid(rows)), block(LN_WAVES * 64);
   bf16* yb = (bf16*)y;
-  if (d <= 768) hipLaunchKernelGGL((ln_fwd_kernel<3>), grid, block, 0, s, x, x_alt, ldx, seq_len, ld_alt, gamma, beta, eps, yb, ldy, y_f32, ldyf, mean, rstd, rows, d);
-  else if (d <= 1024) hipLaunchKernelGGL((ln_fwd_kernel<4>), grid, block, 0, s, x, x_alt, ldx, seq_len, ld_alt, gamma, beta, eps, yb, ldy, y_f32, ldyf, mean, rstd, rows, d);
-  else hipLaunchKernelGGL((ln_fwd_kernel<16>), grid, block, 0, s, x, x_alt, ldx, seq_len, ld_alt, gamma, beta, eps, yb, ldy, y_f32, ldyf, mean, rstd, rows, d);
+  ln_with_v(d, [&](auto v) {
+    hipLaunchKernelGGL((ln_fwd_kernel<decltype(v)::value>), grid, block, 0, s, x, x_alt, ldx, seq_len, ld_alt, gamma, beta, eps, yb, ldy, y_f32, ldyf, mean, rstd, rows, d);
+  });
   return check_launch("xvit_layernorm_fwd");
 }
 
@@ -254,28 +253,18 @@ extern "C" int xvit_layernorm_bwd(const void* dy, int64_t lddy, const float* x, 
   XVIT_REQUIRE(!dressum || dres, "xvit_layernorm_bwd: dressum needs dres");
   hipStream_t s = (hipStream_t)stream;
   const int g = ln_bwd_grid(rows);
-  XVIT_REQUIRE(!workspace || workspace_bytes >= (int64_t)g * 4 * d * (int64_t)sizeof(float), "xvit_layernorm_bwd: workspace too small (%lld bytes)",
+  XVIT_REQUIRE(!workspace || workspace_bytes >= xvit_layernorm_bwd_workspace_bytes(rows, d), "xvit_layernorm_bwd: workspace too small (%lld bytes)",
                (long long)workspace_bytes);
   const dim3 grid(g), block(LNB_WAVES * 64);
+  // 32 d bytes of dynamic LDS: over the 64 KiB a kernel may ask for by default once d > 2048 (128 KiB at d = 4096, one block per CU as the
+  // V = 16 instance's launch bounds already assume)
   const size_t lds = (size_t)LNB_WAVES * 2 * d * sizeof(float);
-  const bf16* dyb = (const bf16*)dy;
-  bf16* dxbb = (bf16*)dxb;
-  if (d <= 768)
-    hipLaunchKernelGGL((ln_bwd_kernel<3>), grid, block, lds, s, dyb, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx, dxbb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
-  else if (d <= 1024)
-    hipLaunchKernelGGL((ln_bwd_kernel<4>), grid, block, lds, s, dyb, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx, dxbb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
-  else {
-    // 32 d bytes of dynamic LDS: over the 64 KiB a kernel may ask for by default once d > 2048 (128 KiB at d = 4096, one block per CU
-    // as this instance's launch bounds already assume), so the instance's limit is raised before such a launch
-    static size_t attr = 0;
-    if (lds > 64 * 1024 && lds > attr) {
-      const hipError_t e = hipFuncSetAttribute((const void*)ln_bwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      XVIT_REQUIRE(e == hipSuccess, "xvit_layernorm_bwd: d=%d needs %lld bytes of LDS and the kernel's limit could not be raised (%s)", d, (long long)lds,
-                   hipGetErrorString(e));
-      attr = lds;
-    }
-    hipLaunchKernelGGL((ln_bwd_kernel<16>), grid, block, lds, s, dyb, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx, dxbb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
-  }
+  const hipError_t e = ln_with_v(d, [&](auto v) {
+    return launch_dyn_lds<ln_bwd_kernel<decltype(v)::value>>(grid, block, lds, s, (const bf16*)dy, lddy, x, x_alt, ldx, seq_len, ld_alt, mean, rstd, gamma, dres, lddres, dx, lddx,
+                                                            (bf16*)dxb, lddxb, dgamma, dbeta, dxsum, dressum, workspace, rows, d);
+  });
+  XVIT_REQUIRE(e == hipSuccess, "xvit_layernorm_bwd: d=%d needs %lld bytes of LDS and the kernel's limit could not be raised (%s)", d, (long long)lds,
+               hipGetErrorString(e));
   if (workspace) {
     // without dxsum / dressum the kernel skips round 1: those slices of the workspace are never read either
     hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((d + 255) / 256), dim3(256), 0, s, workspace, dgamma, dbeta, dxsum, dressum, g, d);

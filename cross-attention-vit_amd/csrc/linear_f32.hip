@@ -23,7 +23,7 @@ struct F32Params {
   bf16* c_bf16; bf16* z_bf16;
   int64_t lda, ldw, ldc, ldr, ldcb, ldzb;
   int M, N, K, k_per_split, split_k, act;
-  float drop_p, drop_inv; uint64_t drop_seed; const uint64_t* drop_epoch;
+  Dropout drop;
 };
 
 __device__ __forceinline__ void f32_epilogue(const F32Params& p, float v, int row, int col) {
@@ -32,10 +32,7 @@ __device__ __forceinline__ void f32_epilogue(const F32Params& p, float v, int ro
     if (p.z_bf16) p.z_bf16[(int64_t)row * p.ldzb + col] = f2bf(v);
     v = gelu_f(v);
   }
-  if (p.drop_p > 0.f) {   // the mask of xvit_dropout on a contiguous [M, N] tensor with this seed
-    const uint32_t thr = (uint32_t)(p.drop_p * 16777216.0f);
-    v = (hash32(drop_seed_at(p.drop_seed, p.drop_epoch), (uint64_t)row * p.N + col) & 0xFFFFFFu) >= thr ? v * p.drop_inv : 0.f;
-  }
+  if (p.drop.on()) v = p.drop.at_run_time().keep((uint64_t)row * p.N + col) ? v * p.drop.inv : 0.f;   // the mask of xvit_dropout on a contiguous [M, N] tensor
   if (p.res) v += p.res[(int64_t)row * p.ldr + col];
   p.C[(int64_t)row * p.ldc + col] = v;
   if (p.c_bf16) p.c_bf16[(int64_t)row * p.ldcb + col] = f2bf(v);
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(64) void linear_f32_kernel(const F32Params p) {
   if (col >= p.N) return;
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
-    const int row = m0 + (t & 3) + 8 * (t >> 2) + 4 * h;
+    const int row = m0 + acc_row(t, h);
     if (row < p.M) {
       if (p.slab) p.slab[((int64_t)split * p.M + row) * p.N + col] = acc[t];
       else f32_epilogue(p, acc[t], row, col);
@@ -120,7 +117,7 @@ extern "C" int xvit_linear_f32(const float* x, int64_t ldx, const float* W, int6
   p.M = M; p.N = N; p.K = K; p.act = act;
   p.split_k = f32_split(M, N, K);
   p.k_per_split = (((K + 15) / 16 + p.split_k - 1) / p.split_k) * 16;
-  p.drop_p = dropout_p; p.drop_inv = 1.0f / (1.0f - dropout_p); p.drop_seed = dropout_seed; p.drop_epoch = dropout_p > 0.f ? drop_epoch_ptr() : nullptr;
+  p.drop = Dropout(dropout_p, dropout_seed);
   const int64_t need = xvit_linear_f32_workspace_bytes(M, N, K);
   XVIT_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "xvit_linear_f32: needs %lld bytes of workspace (got %lld)", (long long)need,
                (long long)workspace_bytes);
@@ -128,10 +125,6 @@ extern "C" int xvit_linear_f32(const float* x, int64_t ldx, const float* W, int6
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(((M + 31) / 32) * ((N + 31) / 32), p.split_k);
   hipLaunchKernelGGL(linear_f32_kernel, grid, dim3(64), 0, s, p);
-  if (p.slab) {
-    const int64_t work = (int64_t)M * N;
-    const int g = (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-    hipLaunchKernelGGL(linear_f32_reduce_kernel, dim3(g), dim3(256), 0, s, p);
-  }
+  if (p.slab) hipLaunchKernelGGL(linear_f32_reduce_kernel, dim3(grid_for((int64_t)M * N, 256, 2048)), dim3(256), 0, s, p);
   return check_launch("xvit_linear_f32");
 }

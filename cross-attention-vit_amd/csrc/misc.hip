@@ -9,32 +9,38 @@ namespace xvit {
 // one 16/32-byte run each), so reads are fully coalesced; a wave then covers 4 H-rows of 8
 // patches and its writes land as whole 128-byte lines of 8 different token rows.
 // ------------------------------------------------------------------------------------------
+// Where the VEC voxels at linear volume index idx * VEC live in the patch matrix: element offset (patch row) * patch_dim + (offset
+// inside the patch) of the first; the run stays inside one patch row (VEC divides wp).
+struct PatchGeom { int M, D, H, W, dp, hp, wp; int64_t stride_b, stride_m; int row_off; };
+template <int VEC>
+__device__ __forceinline__ int64_t patch_elem(const PatchGeom& g, int64_t idx) {
+  const int Wv = g.W / VEC;
+  const int Dn = g.D / g.dp, Wn = g.W / g.wp;
+  const int wv = (int)(idx % Wv);
+  int64_t r = idx / Wv;
+  const int hh = (int)(r % g.H); r /= g.H;
+  const int dd = (int)(r % g.D); r /= g.D;
+  const int vol = (int)r;  // b*M + m
+  const int b = vol / g.M, m = vol - b * g.M;
+  const int w0 = wv * VEC;
+  const int w = w0 / g.wp, p3 = w0 - w * g.wp;
+  const int h = hh / g.hp, p2 = hh - h * g.hp;
+  const int d = dd / g.dp, p1 = dd - d * g.dp;
+  const int t = (h * Wn + w) * Dn + d;
+  const int f = (p1 * g.hp + p2) * g.wp + p3;
+  return ((int64_t)b * g.stride_b + (int64_t)m * g.stride_m + t + g.row_off) * (g.dp * g.hp * g.wp) + f;
+}
+
 template <typename T, int VEC>
-__global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ out, int B, int M, int D, int H, int W, int dp, int hp, int wp,
-                                int64_t stride_b, int64_t stride_m, int row_off, int64_t total_vec) {
-  const int Wv = W / VEC;
-  const int Dn = D / dp, Wn = W / wp;
-  const int pd = dp * hp * wp;
+__global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ out, const PatchGeom g, int64_t total_vec) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int wv = (int)(idx % Wv);
-    int64_t r = idx / Wv;
-    const int hh = (int)(r % H); r /= H;
-    const int dd = (int)(r % D); r /= D;
-    const int vol = (int)r;  // b*M + m
-    const int b = vol / M, m = vol - b * M;
-    const int w0 = wv * VEC;
-    const int w = w0 / wp, p3 = w0 - w * wp;
-    const int h = hh / hp, p2 = hh - h * hp;
-    const int d = dd / dp, p1 = dd - d * dp;
-    const int t = (h * Wn + w) * Dn + d;
-    const int f = (p1 * hp + p2) * wp + p3;
-    bf16* dst = out + ((int64_t)b * stride_b + (int64_t)m * stride_m + t + row_off) * pd + f;
+    bf16* dst = out + patch_elem<VEC>(g, idx);
     const T* src = img + idx * VEC;
     if constexpr (VEC == 8) {
       bf16x8 o;
       if constexpr (sizeof(T) == 4) {
         const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
-        o = bf16x8{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(c[0]), f2bf(c[1]), f2bf(c[2]), f2bf(c[3])};
+        o = to_bf16x8(a, c);
       } else {
         o = *(const bf16x8*)src;
       }
@@ -48,25 +54,9 @@ __global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ ou
 // unpatchify: the exact inverse of patchify_kernel (fp32 patch rows -> fp32 / bf16 volume).  Threads walk the OUTPUT in memory
 // order, 8 voxels = one 32 / 16-byte run each, so the volume is written fully coalesced; each reads its 32 bytes from one patch row.
 template <typename T, int VEC>
-__global__ void unpatchify_kernel(const float* __restrict__ in, T* __restrict__ img, int B, int M, int D, int H, int W, int dp, int hp, int wp,
-                                  int64_t stride_b, int64_t stride_m, int row_off, int64_t total_vec) {
-  const int Wv = W / VEC;
-  const int Dn = D / dp, Wn = W / wp;
-  const int pd = dp * hp * wp;
+__global__ void unpatchify_kernel(const float* __restrict__ in, T* __restrict__ img, const PatchGeom g, int64_t total_vec) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int wv = (int)(idx % Wv);
-    int64_t r = idx / Wv;
-    const int hh = (int)(r % H); r /= H;
-    const int dd = (int)(r % D); r /= D;
-    const int vol = (int)r;  // b*M + m
-    const int b = vol / M, m = vol - b * M;
-    const int w0 = wv * VEC;
-    const int w = w0 / wp, p3 = w0 - w * wp;
-    const int h = hh / hp, p2 = hh - h * hp;
-    const int d = dd / dp, p1 = dd - d * dp;
-    const int t = (h * Wn + w) * Dn + d;
-    const int f = (p1 * hp + p2) * wp + p3;
-    const float* src = in + ((int64_t)b * stride_b + (int64_t)m * stride_m + t + row_off) * pd + f;
+    const float* src = in + patch_elem<VEC>(g, idx);
     T* dst = img + idx * VEC;
     if constexpr (VEC == 8) {
       const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
@@ -74,7 +64,7 @@ __global__ void unpatchify_kernel(const float* __restrict__ in, T* __restrict__ 
         ((f32x4*)dst)[0] = a;
         ((f32x4*)dst)[1] = c;
       } else {
-        *(bf16x8*)dst = bf16x8{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(c[0]), f2bf(c[1]), f2bf(c[2]), f2bf(c[3])};
+        *(bf16x8*)dst = to_bf16x8(a, c);
       }
     } else {
       if constexpr (sizeof(T) == 4) *dst = *src;
@@ -118,7 +108,7 @@ __global__ void cast_kernel(const float* __restrict__ src, bf16* __restrict__ ds
   const int64_t nv = n >> 3;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
     const f32x4 a = ((const f32x4*)src)[2 * i], c = ((const f32x4*)src)[2 * i + 1];
-    ((bf16x8*)dst)[i] = bf16x8{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(c[0]), f2bf(c[1]), f2bf(c[2]), f2bf(c[3])};
+    ((bf16x8*)dst)[i] = to_bf16x8(a, c);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) dst[(nv << 3) + threadIdx.x] = f2bf(src[(nv << 3) + threadIdx.x]);
 }
@@ -131,7 +121,7 @@ __global__ void add_cast_kernel(const float* __restrict__ a, const float* __rest
     const f32x4 s0 = ((const f32x4*)a)[2 * i] + ((const f32x4*)b)[2 * i], s1 = ((const f32x4*)a)[2 * i + 1] + ((const f32x4*)b)[2 * i + 1];
     ((f32x4*)out)[2 * i] = s0;
     ((f32x4*)out)[2 * i + 1] = s1;
-    ((bf16x8*)outb)[i] = bf16x8{f2bf(s0[0]), f2bf(s0[1]), f2bf(s0[2]), f2bf(s0[3]), f2bf(s1[0]), f2bf(s1[1]), f2bf(s1[2]), f2bf(s1[3])};
+    ((bf16x8*)outb)[i] = to_bf16x8(s0, s1);
   }
 }
 
@@ -222,13 +212,10 @@ __global__ void colsum_reduce_kernel(const float* __restrict__ part, float* __re
 }
 
 template <typename T>
-__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, float p, float inv_keep, uint64_t seed_in, const uint64_t* __restrict__ epoch) {
-  const uint64_t seed = drop_seed_at(seed_in, epoch);
-  const uint32_t thr = (uint32_t)(p * 16777216.0f);  // drop when the 24-bit hash < p * 2^24
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const bool keep = (hash32(seed, (uint64_t)i) & 0xFFFFFFu) >= thr;
-    y[i] = keep ? (T)((float)x[i] * inv_keep) : (T)0.0f;
-  }
+__global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, const Dropout drop_in) {
+  const Dropout drop = drop_in.at_run_time();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    y[i] = drop.keep((uint64_t)i) ? (T)((float)x[i] * drop.inv) : (T)0.0f;
 }
 
 // ---- tiny fp32 linear (num_classes head) ---------------------------------------------------
@@ -314,9 +301,13 @@ __global__ void mean_ce_kernel(const float* __restrict__ logits_m, const int64_t
 
 using namespace xvit;
 
-static int grid_for(int64_t work, int block) {
-  int64_t g = (work + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+// f(T{}, Int<VEC>{}, units of work): the (image dtype, voxels per thread) instantiation of a patchify / unpatchify launch
+template <class F>
+static void patch_dispatch(int img_dtype, bool vec, int64_t total, F&& f) {
+  by_dtype(img_dtype, [&](auto t) {
+    if (vec) f(t, Int<8>{}, total / 8);
+    else f(t, Int<1>{}, total);
+  });
 }
 
 extern "C" int xvit_patchify(const void* img, int img_dtype, void* out, int B, int M, int D, int H, int W, int dp, int hp, int wp,
@@ -331,14 +322,11 @@ extern "C" int xvit_patchify(const void* img, int img_dtype, void* out, int B, i
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (wp % 8 == 0) && ((reinterpret_cast<uintptr_t>(img) & 31) == 0);
   bf16* o = (bf16*)out;
-  if (vec) {
-    const int64_t tv = total / 8;
-    if (img_dtype == XVIT_F32) hipLaunchKernelGGL((patchify_kernel<float, 8>), dim3(grid_for(tv, 256)), dim3(256), 0, s, (const float*)img, o, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, tv);
-    else hipLaunchKernelGGL((patchify_kernel<bf16, 8>), dim3(grid_for(tv, 256)), dim3(256), 0, s, (const bf16*)img, o, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, tv);
-  } else {
-    if (img_dtype == XVIT_F32) hipLaunchKernelGGL((patchify_kernel<float, 1>), dim3(grid_for(total, 256)), dim3(256), 0, s, (const float*)img, o, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, total);
-    else hipLaunchKernelGGL((patchify_kernel<bf16, 1>), dim3(grid_for(total, 256)), dim3(256), 0, s, (const bf16*)img, o, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, total);
-  }
+  const PatchGeom g = {M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off};
+  patch_dispatch(img_dtype, vec, total, [&](auto t, auto v, int64_t work) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((patchify_kernel<T, decltype(v)::value>), dim3(grid_for(work, 256)), dim3(256), 0, s, (const T*)img, o, g, work);
+  });
   if (zero_rows > 0) {
     const int pd = dp * hp * wp;
     const int64_t work = (int64_t)zero_rows * (pd / 8);
@@ -357,14 +345,11 @@ extern "C" int xvit_unpatchify(const float* patches, void* img, int img_dtype, i
   const int64_t total = (int64_t)B * M * D * H * W;
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (wp % 8 == 0) && ((reinterpret_cast<uintptr_t>(patches) & 31) == 0) && ((reinterpret_cast<uintptr_t>(img) & 31) == 0);
-  if (vec) {
-    const int64_t tv = total / 8;
-    if (img_dtype == XVIT_F32) hipLaunchKernelGGL((unpatchify_kernel<float, 8>), dim3(grid_for(tv, 256)), dim3(256), 0, s, patches, (float*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, tv);
-    else hipLaunchKernelGGL((unpatchify_kernel<bf16, 8>), dim3(grid_for(tv, 256)), dim3(256), 0, s, patches, (bf16*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, tv);
-  } else {
-    if (img_dtype == XVIT_F32) hipLaunchKernelGGL((unpatchify_kernel<float, 1>), dim3(grid_for(total, 256)), dim3(256), 0, s, patches, (float*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, total);
-    else hipLaunchKernelGGL((unpatchify_kernel<bf16, 1>), dim3(grid_for(total, 256)), dim3(256), 0, s, patches, (bf16*)img, B, M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off, total);
-  }
+  const PatchGeom g = {M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off};
+  patch_dispatch(img_dtype, vec, total, [&](auto t, auto v, int64_t work) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((unpatchify_kernel<T, decltype(v)::value>), dim3(grid_for(work, 256)), dim3(256), 0, s, patches, (T*)img, g, work);
+  });
   return check_launch("xvit_unpatchify");
 }
 
@@ -430,17 +415,20 @@ extern "C" int xvit_colsum(const void* x, int x_dtype, int64_t ldx, float* out, 
   const int gx = (n / 4 + 63) / 64;
   const int rpb = colsum_rows_per_block(rows, n);
   const dim3 grid(gx, (rows + rpb - 1) / rpb), block(256);
-  if (x_dtype == XVIT_F32) hipLaunchKernelGGL((colsum_kernel<float>), grid, block, 0, s, (const float*)x, ldx, out, workspace, rows, n, rpb);
-  else hipLaunchKernelGGL((colsum_kernel<bf16>), grid, block, 0, s, (const bf16*)x, ldx, out, workspace, rows, n, rpb);
+  by_dtype(x_dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((colsum_kernel<T>), grid, block, 0, s, (const T*)x, ldx, out, workspace, rows, n, rpb);
+  });
   if (workspace) hipLaunchKernelGGL(colsum_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, workspace, out, (int)grid.y, n, accumulate);
   return check_launch("xvit_colsum");
 }
 
 extern "C" int xvit_dropout(const void* x, void* y, int dtype, int64_t n, float p, uint64_t seed, xvit_stream_t stream) {
   XVIT_REQUIRE(x && y && n > 0 && p >= 0.f && p < 1.f, "xvit_dropout: bad arguments");
-  const float inv = 1.0f / (1.0f - p);
-  if (dtype == XVIT_F32) hipLaunchKernelGGL((dropout_kernel<float>), dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, n, p, inv, seed, drop_epoch_ptr());
-  else hipLaunchKernelGGL((dropout_kernel<bf16>), dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, n, p, inv, seed, drop_epoch_ptr());
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((dropout_kernel<T>), dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, Dropout(p, seed));
+  });
   return check_launch("xvit_dropout");
 }
 
@@ -517,7 +505,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict_
         p[e] = pe; m[e] = me; v[e] = ve;
       }
       *(f32x4*)(t.p + i) = p; *(f32x4*)(t.m + i) = m; *(f32x4*)(t.v + i) = v;
-      if (t.shadow) *(bf16x4*)(t.shadow + i) = bf16x4{f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
+      if (t.shadow) *(bf16x4*)(t.shadow + i) = to_bf16x4(p);
     }
     const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
     for (int64_t i = tail + threadIdx.x; i < end; i += 256) {
@@ -663,9 +651,7 @@ extern "C" int xvit_resize_pad_crop_i16(const void* src_i16, void* dst_bf16, int
   // per dimension: size < target -> pad, before = (target - size) / 2; size > target -> crop, start = size / 2 - target / 2
   auto offset = [](int size, int target) { return size >= target ? size / 2 - target / 2 : -((target - size) / 2); };
   const int64_t total = (int64_t)nvol * D * H * W;
-  int64_t g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(xvit::resize_pad_crop_i16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const int16_t*)src_i16, (xvit::bf16*)dst_bf16,
+  hipLaunchKernelGGL(xvit::resize_pad_crop_i16_kernel, dim3(xvit::grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const int16_t*)src_i16, (xvit::bf16*)dst_bf16,
                      Ds, Hs, Ws, D, H, W, offset(Ds, D), offset(Hs, H), offset(Ws, W), pad_value, total);
   return xvit::check_launch("xvit_resize_pad_crop_i16");
 }

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <type_traits>
+
 #include "../../include/xvit.h"
 
 namespace xvit {
@@ -37,6 +40,40 @@ static void launch_lds(dim3 grid, hipStream_t s, Args... args) {
   hipLaunchKernelGGL(KERNEL, grid, dim3(BLOCK), LDS, s, args...);
 }
 
+// The same for an LDS size known only at run time: the instantiation's limit is raised whenever a launch asks for more than the largest
+// size seen so far (under a lock: the limit only ever grows, whichever threads launch).  Returns hipFuncSetAttribute's status; nothing
+// is launched when it fails.
+template <auto KERNEL, class... Args>
+static hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static std::mutex lock;
+  static size_t limit = 64 * 1024;   // what a kernel may ask for without opting in
+  {
+    std::lock_guard<std::mutex> hold(lock);
+    if (lds > limit) {
+      const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      limit = lds;
+    }
+  }
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args...);
+  return hipSuccess;
+}
+
+// blocks of a grid-stride launch: one thread per unit of work, at most `cap` blocks
+static inline int grid_for(int64_t work, int block, int cap = 4096) {
+  const int64_t g = (work + block - 1) / block;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// Run-time -> compile-time dispatch: f gets a value whose TYPE carries the choice (decltype(t), decltype(v)::value), so that a launch's
+// argument list is written once for all its instantiations.
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F>
+static void by_dtype(int dtype, F&& f) {   // XVIT_F32 / XVIT_BF16 (host-checked)
+  if (dtype == XVIT_F32) f(float{});
+  else f(bf16{});
+}
+
 #define XVIT_REQUIRE(cond, ...)            \
   do {                                     \
     if (!(cond)) {                         \
@@ -48,6 +85,11 @@ static void launch_lds(dim3 grid, hipStream_t s, Args... args) {
 // ---- device helpers ------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 __device__ __forceinline__ bf16 f2bf(float v) { return (bf16)v; }  // v_cvt_pk_bf16_f32, RNE, NaN-safe
+
+__device__ __forceinline__ bf16x4 to_bf16x4(const f32x4& a) { return bf16x4{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3])}; }
+__device__ __forceinline__ bf16x8 to_bf16x8(const f32x4& a, const f32x4& b) {
+  return bf16x8{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(b[0]), f2bf(b[1]), f2bf(b[2]), f2bf(b[3])};
+}
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
@@ -104,67 +146,61 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_perm(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
-__device__ __forceinline__ void swap_rows16(float x, float& a, float& b) {   // (x of the even row, x of the odd row) of each row pair, in both rows
-  typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t_;
-  const unsigned bits = __builtin_bit_cast(unsigned, x);
-  const u32x2_t_ r = __builtin_amdgcn_permlane16_swap(bits, bits, false, false);
-  const unsigned r0 = r.x, r1 = r.y;
-  a = __builtin_bit_cast(float, r0);
-  b = __builtin_bit_cast(float, r1);
-}
-__device__ __forceinline__ void swap_halves32(float x, float& a, float& b) {
-  typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t_;
-  const unsigned bits = __builtin_bit_cast(unsigned, x);
-  const u32x2_t_ r = __builtin_amdgcn_permlane32_swap(bits, bits, false, false);
-  const unsigned r0 = r.x, r1 = r.y;
-  a = __builtin_bit_cast(float, r0);
-  b = __builtin_bit_cast(float, r1);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_perm<0xB1>(v);    // quad_perm [1, 0, 3, 2]
-  v += dpp_perm<0x4E>(v);    // quad_perm [2, 3, 0, 1]
-  v += dpp_perm<0x141>(v);   // row_half_mirror
-  v += dpp_perm<0x140>(v);   // row_mirror
-  float a, b;
-  swap_rows16(v, a, b);
-  v = a + b;
-  swap_halves32(v, a, b);
-  return a + b;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  v = fmaxf(v, dpp_perm<0xB1>(v));
-  v = fmaxf(v, dpp_perm<0x4E>(v));
-  v = fmaxf(v, dpp_perm<0x141>(v));
-  v = fmaxf(v, dpp_perm<0x140>(v));
-  float a, b;
-  swap_rows16(v, a, b);
-  v = fmaxf(a, b);
-  swap_halves32(v, a, b);
-  return fmaxf(a, b);
-}
-
-// Combine a value across the two 32-lane halves of a wave (lane l with lane l ^ 32) in ONE VALU instruction:
-// v_permlane32_swap exchanges the upper half of one register with the lower half of another, so afterwards the pair
-// holds (x.lo, x.lo) and (x.hi, x.hi).  __shfl_xor(x, 32) compiles to a ds_bpermute round trip through the LDS
-// pipe (address arithmetic + lgkmcnt wait) instead.
+// v_permlane16_swap (W = 16) / v_permlane32_swap (W = 32) of x with itself: a = x of the even 16-lane row of each row pair (of the lower
+// half of the wave), b = x of the odd row (upper half), in both.  ONE VALU instruction where __shfl_xor(x, W) is a ds_bpermute round trip.
 // (Note for anyone touching this: __builtin_bit_cast(float, vec.y) on an ext-vector ELEMENT reads element 0 with this
 // hipcc — go through a scalar temporary, as below.)
-__device__ __forceinline__ void swap_halves(float x, float& lo, float& hi) {
+template <int W>
+__device__ __forceinline__ void permlane_swap(float x, float& a, float& b) {
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t_;
   const unsigned bits = __builtin_bit_cast(unsigned, x);
-  const u32x2_t_ r = __builtin_amdgcn_permlane32_swap(bits, bits, false, false);
+  u32x2_t_ r;
+  if constexpr (W == 16) r = __builtin_amdgcn_permlane16_swap(bits, bits, false, false);
+  else r = __builtin_amdgcn_permlane32_swap(bits, bits, false, false);
   const unsigned r0 = r.x, r1 = r.y;
-  lo = __builtin_bit_cast(float, r0);
-  hi = __builtin_bit_cast(float, r1);
+  a = __builtin_bit_cast(float, r0);
+  b = __builtin_bit_cast(float, r1);
 }
+struct SumOp { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
+struct MaxOp { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+template <class Op>
+__device__ __forceinline__ float wave_reduce(float v, Op op) {
+  v = op(v, dpp_perm<0xB1>(v));    // quad_perm [1, 0, 3, 2]
+  v = op(v, dpp_perm<0x4E>(v));    // quad_perm [2, 3, 0, 1]
+  v = op(v, dpp_perm<0x141>(v));   // row_half_mirror
+  v = op(v, dpp_perm<0x140>(v));   // row_mirror
+  float a, b;
+  permlane_swap<16>(v, a, b);
+  v = op(a, b);
+  permlane_swap<32>(v, a, b);
+  return op(a, b);
+}
+__device__ __forceinline__ float wave_sum(float v) { return wave_reduce(v, SumOp{}); }
+__device__ __forceinline__ float wave_max(float v) { return wave_reduce(v, MaxOp{}); }
+
+// Block-wide reduction of an NW-wave block, result in every thread: each wave's result through red[NW], combined in wave order (fixed:
+// bit-reproducible).  The leading barrier lets consecutive calls share `red`.
+template <int NW, class Op>
+__device__ __forceinline__ float block_reduce(float v, Op op, float* red) {
+  v = wave_reduce(v, op);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) r = op(r, red[w]);
+  return r;
+}
+
+// Combine a value across the two 32-lane halves of a wave (lane l with lane l ^ 32)
 __device__ __forceinline__ float half_max(float x) {
   float lo, hi;
-  swap_halves(x, lo, hi);
+  permlane_swap<32>(x, lo, hi);
   return fmaxf(lo, hi);
 }
 __device__ __forceinline__ float half_sum(float x) {
   float lo, hi;
-  swap_halves(x, lo, hi);
+  permlane_swap<32>(x, lo, hi);
   return lo + hi;
 }
 
@@ -242,11 +278,33 @@ __device__ __forceinline__ uint32_t hash32(uint64_t seed, uint64_t idx) {
   return (uint32_t)((z ^ (z >> 31)) >> 16);
 }
 
+__device__ __forceinline__ uint32_t draw24(uint64_t seed, uint64_t idx) { return hash32(seed, idx) & 0xFFFFFFu; }   // uniform on [0, 2^24)
+constexpr float kTwo24 = 16777216.0f;
+
 // A captured step (HIP graph) freezes every kernel argument, the dropout seeds included.  A launch may therefore carry the device address
 // of an epoch counter (xvit_set_dropout_epoch): the seed a kernel then uses is seed + epoch * odd constant, read at run time, so that a
 // replay whose graph increments the counter first draws new masks — the same ones in its forward and its backward.
 __device__ __forceinline__ uint64_t drop_seed_at(uint64_t seed, const uint64_t* __restrict__ epoch) {
   return epoch ? seed + *epoch * 0xD1B54A32D192ED03ull : seed;
 }
+
+// Dropout at rate p as a launch carries it.  Element idx is kept iff its 24-bit draw >= p 2^24 and then scaled by inv = 1 / (1 - p): the
+// mask of xvit_dropout on a contiguous tensor with this seed, regenerated wherever it is needed (forward and backward), never stored.
+// p 2^24 is exact in fp32, on the host as on the device.
+struct Dropout {
+  float p = 0.f, inv = 1.f;
+  uint32_t thr = 0;
+  uint64_t seed = 0;
+  const uint64_t* epoch = nullptr;   // drop_seed_at (captured steps), or nullptr
+  Dropout() = default;
+  Dropout(float p_, uint64_t seed_) : p(p_), inv(1.0f / (1.0f - p_)), thr((uint32_t)(p_ * kTwo24)), seed(seed_), epoch(p_ > 0.f ? drop_epoch_ptr() : nullptr) {}   // host
+  __device__ __forceinline__ bool on() const { return p > 0.f; }
+  __device__ __forceinline__ Dropout at_run_time() const {   // once per thread: the seed of this launch (or replay)
+    Dropout d = *this;
+    d.seed = drop_seed_at(seed, epoch);
+    return d;
+  }
+  __device__ __forceinline__ bool keep(uint64_t idx) const { return draw24(seed, idx) >= thr; }
+};
 
 }  // namespace xvit
