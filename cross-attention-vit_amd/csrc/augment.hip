@@ -148,7 +148,8 @@ __global__ void __launch_bounds__(256) augment_apply_kernel(const S* __restrict_
   const float* __restrict__ P = params + (int64_t)vol * XVIT_AUG_NPARAM;   // wave-uniform: scalar loads
   const float a = P[XVIT_AUG_SCALE], b = P[XVIT_AUG_SHIFT], sigma = P[XVIT_AUG_SIGMA];
   const uint32_t noise_seed = __builtin_bit_cast(uint32_t, P[XVIT_AUG_NOISE_SEED]);
-  const bool exact = ((int)P[XVIT_AUG_FLAGS] & XVIT_AUG_FLAG_EXACT) != 0;
+  const int flags = (int)P[XVIT_AUG_FLAGS];
+  const bool exact = (flags & XVIT_AUG_FLAG_EXACT) != 0, clamp = (flags & XVIT_AUG_FLAG_CLAMP) != 0;
 
   const S* __restrict__ sv = src + (int64_t)vol * g.Ds * g.Hs * g.Ws;
   const uint32_t vox0 = ((uint32_t)z * g.H + y) * g.W + x0;   // < 2^31 by the host check
@@ -202,6 +203,10 @@ __global__ void __launch_bounds__(256) augment_apply_kernel(const S* __restrict_
     }
   }
 
+  if (clamp) {   // xvit_volume_stats' window, in source units: padding lands on its floor
+    const float lo = P[XVIT_AUG_CLAMP_LO], hi = P[XVIT_AUG_CLAMP_HI];
+    for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(v[i], lo), hi);
+  }
   for (int i = 0; i < 8; ++i) v[i] = fmaf(a, v[i], b);
   if (sigma > 0.f)
     for (int i = 0; i < 8; ++i) v[i] = fmaf(sigma, normal_at(noise_seed, vox0 + i), v[i]);

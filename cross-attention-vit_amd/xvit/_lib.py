@@ -47,6 +47,16 @@ class AugmentConfig(C.Structure):
 AUG_NPARAM = 32   # XVIT_AUG_NPARAM
 
 
+class NormConfig(C.Structure):
+    """struct xvit_norm_config (include/xvit.h)."""
+    _fields_ = [("mode", i32), ("clip", i32), ("foreground_above", f32), ("q_lo", f32), ("q_hi", f32)]
+
+
+STATS_NSTAT = 8                                        # XVIT_STATS_NSTAT
+STATS_WINDOW_LO, STATS_WINDOW_BINS = 32768, 32768      # XVIT_STATS_WINDOW_*: the keys the histogram kernel counts in LDS
+NORM_STATS_ONLY, NORM_ZSCORE, NORM_WINDOW = 0, 1, 2    # XVIT_NORM_*
+
+
 # name -> argtypes; every function returns int except the two noted below
 SIGNATURES = {
     "xvit_gemm": [C.POINTER(GemmArgs), vp],
@@ -89,6 +99,7 @@ SIGNATURES = {
     "xvit_resize_pad_crop_i16": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_augment_draw": [C.POINTER(AugmentConfig), vp, i32, i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp],
     "xvit_augment_apply": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "xvit_volume_stats": [vp, i32, i32, i64, C.POINTER(NormConfig), vp, vp, vp, i64, vp],
     "xvit_set_option": [C.c_char_p, i32],
     "xvit_set_dropout_epoch": [C.c_void_p],
     "xvit_adam_step": [vp, vp, i32, f32, f32, f32, f32, f32, i32, f32, vp],
@@ -100,7 +111,7 @@ SIGNATURES = {
 }
 EXPORTS = sorted(list(SIGNATURES) + ["xvit_version", "xvit_last_error_string", "xvit_gemm_workspace_bytes", "xvit_linear_f32_workspace_bytes",
                                     "xvit_colsum_workspace_bytes", "xvit_layernorm_bwd_workspace_bytes", "xvit_patch_embed_wgrad_workspace_bytes", "xvit_attn_fp8_workspace_bytes",
-                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes"])
+                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes"])
 
 _lib = None
 
@@ -131,6 +142,8 @@ def load() -> C.CDLL:
             getattr(lib, name).restype = C.c_int64
         lib.xvit_patch_embed_wgrad_workspace_bytes.argtypes = [C.POINTER(PatchGeom), i32]
         lib.xvit_patch_embed_wgrad_workspace_bytes.restype = C.c_int64
+        lib.xvit_volume_stats_workspace_bytes.argtypes = [i32]
+        lib.xvit_volume_stats_workspace_bytes.restype = C.c_int64
         lib.xvit_version.restype = C.c_int
         lib.xvit_last_error_string.restype = C.c_char_p
         _lib = lib

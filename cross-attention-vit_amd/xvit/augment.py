@@ -5,10 +5,19 @@
     aug.last_params                  # AugmentParams: the table this call drew
     img = aug.apply(raw, params)     # an explicit table: replaying a recorded augmentation, test-time augmentation
 
+    aug = xvit.augment.VolumeAugment((128, 128, 128), normalize="zscore")    # per-volume normalisation, also in eval()
+    aug.last_stats                   # VolumeStats: n, n_w, mean, std, lo, hi, min, max of every volume's foreground
+    xvit.augment.volume_stats(raw)   # the statistics alone
+
 It stands where the reference's loader runs MONAI's random transforms on CPU workers (dataset_ucsf.py:94-113).  The transform set and its
 ranges are this project's own; parity with MONAI's random stream is not claimed.  All modalities of a sample share one spatial transform
 (they are co-registered scans); intensity transforms are drawn per volume.  pad_value is in SOURCE units: it passes through the intensity
 affine like every voxel.
+
+normalize="zscore" | "window" puts a per-volume normalisation in front of the drawn scale / shift (include/xvit.h, "Per-volume intensity
+statistics and normalisation"): exact statistics of the foreground voxels (v > foreground_above) of the WHOLE source volume, from a
+histogram on the device, folded into the table between the draw and the resample.  With clip=True the resampled value is clamped to the
+window [lo, hi] first, pad_value included: the background lands on the window floor.
 """
 from __future__ import annotations
 
@@ -19,7 +28,10 @@ from . import _lib, ops
 NPARAM = _lib.AUG_NPARAM
 # slots of a record: enum XVIT_AUG_* of include/xvit.h, by name
 MATRIX, SCALE, SHIFT, SIGMA, NOISE_SEED, FLAGS, FLIPS, ANGLES, ZOOMS, TRANSLATION = 0, 12, 13, 14, 15, 16, 17, 20, 23, 26
-FLAG_EXACT = 1
+CLAMP_LO, CLAMP_HI = 29, 30
+FLAG_EXACT, FLAG_CLAMP = 1, 2
+NSTAT = _lib.STATS_NSTAT
+_NORM_MODES = {None: _lib.NORM_STATS_ONLY, "zscore": _lib.NORM_ZSCORE, "window": _lib.NORM_WINDOW}
 _COUNTER_STRIDE = 0xD1B54A32D192ED03   # seed' = seed + call index * this (mod 2^64), on the host here and in the draw kernel alike
 _MASK64 = (1 << 64) - 1
 
@@ -58,6 +70,8 @@ class AugmentParams:
     angles = property(lambda s: s.table[..., ANGLES:ANGLES + 3])
     zooms = property(lambda s: s.table[..., ZOOMS:ZOOMS + 3])
     translation = property(lambda s: s.table[..., TRANSLATION:TRANSLATION + 3])
+    clamp_lo = property(lambda s: s.table[..., CLAMP_LO])
+    clamp_hi = property(lambda s: s.table[..., CLAMP_HI])
 
     @property
     def noise_seed(self):
@@ -67,8 +81,74 @@ class AugmentParams:
     def exact(self):
         return (self.table[..., FLAGS].to(torch.int32) & FLAG_EXACT).bool()
 
+    @property
+    def clamped(self):
+        return (self.table[..., FLAGS].to(torch.int32) & FLAG_CLAMP).bool()
+
     def clone(self):
         return AugmentParams(self.table.clone())
+
+
+class VolumeStats:
+    """Named views of a statistics table [B, M, 8] (fp64) of xvit_volume_stats.  The table stays on the device: reading a value is the one
+    host synchronisation, paid only by who reads."""
+
+    def __init__(self, table: torch.Tensor):
+        if table.dtype != torch.float64 or table.dim() != 3 or table.shape[2] != NSTAT:
+            raise ValueError(f"VolumeStats: need an fp64 [B, M, {NSTAT}] table, got {table.dtype} {tuple(table.shape)}")
+        self.table = table
+
+    n = property(lambda s: s.table[..., 0])        # foreground voxels
+    n_w = property(lambda s: s.table[..., 1])      # ... of them inside [lo, hi]
+    mean = property(lambda s: s.table[..., 2])     # over the window
+    std = property(lambda s: s.table[..., 3])      # population standard deviation over the window
+    lo = property(lambda s: s.table[..., 4])
+    hi = property(lambda s: s.table[..., 5])
+    min = property(lambda s: s.table[..., 6])      # of the foreground
+    max = property(lambda s: s.table[..., 7])
+
+    def clone(self):
+        return VolumeStats(self.table.clone())
+
+
+def norm_config(normalize=None, foreground_above=0.0, percentiles=None, clip=False):
+    """_lib.NormConfig from the Python arguments, validated as xvit_volume_stats validates it."""
+    if normalize not in _NORM_MODES:
+        raise ValueError(f"normalize={normalize!r} must be None, 'zscore' or 'window'")
+    fg = float(foreground_above)
+    if fg != fg:
+        raise ValueError("foreground_above is NaN")
+    c = _lib.NormConfig()
+    c.mode, c.clip, c.foreground_above = _NORM_MODES[normalize], int(bool(clip)), fg
+    if percentiles is None:
+        c.q_lo, c.q_hi = -1.0, -1.0
+    else:
+        q = tuple(float(v) for v in percentiles)
+        if len(q) != 2 or not 0.0 <= q[0] <= q[1] <= 1.0:
+            raise ValueError(f"percentiles={tuple(percentiles)} need 0 <= q_lo <= q_hi <= 1")
+        c.q_lo, c.q_hi = q
+    return c
+
+
+def _stat_volumes(raw, who):
+    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
+        raise RuntimeError(f"{who}: the volumes must be a GPU tensor; this stage has no CPU path")
+    if raw.dim() < 3:
+        raise ValueError(f"{who}: need [B, M, ...] volumes, got {tuple(raw.shape)}")
+    if not raw.is_contiguous():
+        raise ValueError(f"{who}: the volumes must be contiguous (the source is read once, in place)")
+    return raw
+
+
+def volume_stats(raw, foreground_above=0.0, percentiles=None) -> VolumeStats:
+    """Exact per-volume statistics of raw [B, M, ...] (int16 or bf16 on the GPU) over its foreground v > foreground_above: two launches,
+    no host synchronisation until the result is read.  percentiles=(q_lo, q_hi): lo / hi by nearest rank and mean / std over [lo, hi]."""
+    raw = _stat_volumes(raw, "volume_stats")
+    config = norm_config(None, foreground_above, percentiles)
+    B, M = raw.shape[:2]
+    stats = torch.empty(B, M, NSTAT, dtype=torch.float64, device=raw.device)
+    ops.volume_stats(raw, config, stats, ops.volume_stats_workspace(B * M, raw.device))
+    return VolumeStats(stats)
 
 
 def _prob(name, p):
@@ -95,15 +175,19 @@ def _half_widths(name, r):
 class VolumeAugment(torch.nn.Module):
     """Pad / crop to img_size, one random affine resample (flips, rotation about the volume centre, per-axis zoom, translation) and one
     random intensity transform (scale, shift, Gaussian noise), in two launches: the draw into a readable table and the resample.
+    normalize="zscore" | "window" adds two launches between them (xvit.augment.volume_stats, folded into the table): the drawn scale /
+    shift then act on (v - mean) / std, or on (v - lo) / (hi - lo), of the volume's foreground v > foreground_above, lo / hi being the
+    `percentiles` by nearest rank (None: min / max) and mean / std taken inside [lo, hi]; clip clamps to [lo, hi] first.  It is not
+    random and runs in eval() as in train(); intensity_scale / intensity_shift then apply to the normalised values.
 
     Call k uses seed + k, so a run is reproducible from `seed`; eval() switches every probability off (pad / crop and the fixed intensity
     affine only) and does not advance k.  capturable=True keeps k in a device counter so that the call can sit inside torch.cuda.graph and
-    draw anew at every replay; call the stage once before capturing (it allocates its table and counter then)."""
+    draw anew at every replay; call the stage once before capturing (it allocates its table, counter and statistics buffers then)."""
 
     def __init__(self, img_size, pad_value=-1.0, flip_prob=(.5, .5, .5), rotate_prob=.5, rotate_range=(.26, .26, .26), zoom_prob=.5,
                  zoom_range=(.9, 1.1), translate_prob=.5, translate_range=(8, 8, 8), scale_intensity_prob=.5, scale_intensity_range=(.9, 1.1),
                  shift_intensity_prob=.5, shift_intensity_range=(-.1, .1), noise_prob=.2, noise_std=.05, intensity_scale=1.0, intensity_shift=0.0,
-                 out_dtype=torch.bfloat16, seed=0, capturable=False):
+                 out_dtype=torch.bfloat16, seed=0, capturable=False, normalize=None, foreground_above=0.0, percentiles=(0.005, 0.995), clip=True):
         super().__init__()
         self.img_size = tuple(int(v) for v in img_size)
         if len(self.img_size) != 3 or min(self.img_size) <= 0:
@@ -132,10 +216,18 @@ class VolumeAugment(torch.nn.Module):
         e.rotate_prob = e.zoom_prob = e.translate_prob = e.scale_prob = e.shift_prob = e.noise_prob = 0.0
         self._eval_config = e
         self.pad_value, self.out_dtype, self.seed, self.capturable = float(pad_value), out_dtype, int(seed), bool(capturable)
+        try:
+            self.norm_config = norm_config(normalize, foreground_above, percentiles, clip)
+        except ValueError as e:
+            raise ValueError(f"VolumeAugment: {e}") from None
+        self.normalize = normalize
         self.calls = 0             # host call index (capturable: see call_index)
         self._counter = None       # capturable: the device call index
         self._tables = {}          # capturable: one static table per (B, M, device)
+        self._stats = {}           # capturable: one static statistics table per (B, M, device)
+        self._workspaces = {}      # normalize: the histogram workspace per (B M, device), zero between calls
         self.last_params = None
+        self.last_stats = None
 
     @property
     def call_index(self) -> int:
@@ -167,7 +259,23 @@ class VolumeAugment(torch.nn.Module):
             self._tables[key] = torch.empty(B, M, NPARAM, dtype=torch.float32, device=device)
             if self._counter is None:
                 self._counter = torch.zeros(1, dtype=torch.int64, device=device)
+            if self.normalize is not None:
+                self._stats[key] = torch.empty(B, M, NSTAT, dtype=torch.float64, device=device)
+                self._workspaces[(B * M, device)] = ops.volume_stats_workspace(B * M, device)
         return self._tables[key]
+
+    def _normalise(self, raw, table):
+        """Statistics of raw, folded into the table just drawn (two launches) -> VolumeStats."""
+        B, M = raw.shape[:2]
+        if self.capturable:
+            self._table(B, M, raw.device)                  # the static buffers are allocated together
+            stats = self._stats[(B, M, raw.device)]
+        else:
+            stats = torch.empty(B, M, NSTAT, dtype=torch.float64, device=raw.device)
+            if (B * M, raw.device) not in self._workspaces:
+                self._workspaces[(B * M, raw.device)] = ops.volume_stats_workspace(B * M, raw.device)
+        ops.volume_stats(raw, self.norm_config, stats, self._workspaces[(B * M, raw.device)], table)
+        return VolumeStats(stats)
 
     def draw(self, B, M, vol_shape, device) -> AugmentParams:
         """One table for B x M volumes of vol_shape; advances the call index in training mode."""
@@ -187,5 +295,9 @@ class VolumeAugment(torch.nn.Module):
 
     def forward(self, raw):
         raw = self._volumes(raw)
+        if self.normalize is not None and raw.dtype == torch.float32:
+            self._normalise(raw, None)     # the library refuses it before any launch (TypeError): nothing is drawn
         self.last_params = self.draw(raw.shape[0], raw.shape[1], tuple(raw.shape[2:]), raw.device)
+        if self.normalize is not None:
+            self.last_stats = self._normalise(raw, self.last_params.table)
         return self.apply(raw, self.last_params)

@@ -738,7 +738,7 @@ def resize_pad_crop_i16(vol, img_size, pad_value=-1.0):
     return out
 
 
-I16 = 2   # XVIT_I16: source volumes of augment_apply only
+I16 = 2   # XVIT_I16: source volumes of augment_apply and volume_stats only
 
 
 def augment_draw(config, params, vol_shape, img_size, seed, counter=None, advance=False):
@@ -770,3 +770,33 @@ def augment_apply(src, params, img_size, pad_value=-1.0, out_dtype=torch.bfloat1
          lambda: _lib.load().xvit_augment_apply(_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params), B * M, Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
          "xvit_augment_apply")
     return out
+
+
+def volume_stats_workspace(nvol, device):
+    """The zero-filled histogram workspace of volume_stats for nvol volumes (xvit_volume_stats_workspace_bytes): every call leaves it
+    zero again, so it is filled once, here."""
+    return torch.zeros(_lib.load().xvit_volume_stats_workspace_bytes(int(nvol)), dtype=torch.uint8, device=device)
+
+
+def volume_stats(src, config, stats, workspace, params=None):
+    """xvit_volume_stats (include/xvit.h): per-volume foreground statistics of src [B, M, ...] (int16 or bf16, contiguous) into stats
+    [B, M, 8] (fp64): n, n_w, mean, std, lo, hi, min, max.  config: _lib.NormConfig.  params: the table [B, M, 32] of augment_draw, into
+    which the normalisation is folded (mode 1 / 2), or None.  workspace: volume_stats_workspace(B * M, device).  An fp32 source is a
+    TypeError carrying the library's message."""
+    assert src.dim() >= 3 and src.is_contiguous() and stats.dtype == torch.float64 and stats.is_contiguous()
+    B, M = src.shape[:2]
+    nvox = src.numel() // (B * M)
+    assert tuple(stats.shape) == (B, M, _lib.STATS_NSTAT), f"stats {tuple(stats.shape)} do not match {B} x {M} volumes"
+    if params is not None:
+        assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B, M, _lib.AUG_NPARAM)
+    sdt = I16 if src.dtype == torch.int16 else _dt(src)
+    try:
+        _run("volume_stats", src.numel() * float(src.element_size()), "byte",
+             lambda: _lib.load().xvit_volume_stats(_ptr(src), sdt, B * M, nvox, C.byref(config), _ptr(stats), _ptr(params), _ptr(workspace),
+                                                   workspace.numel() * workspace.element_size(), _stream()),
+             "xvit_volume_stats")
+    except RuntimeError as e:
+        if src.dtype == torch.float32:
+            raise TypeError(str(e)) from None
+        raise
+    return stats

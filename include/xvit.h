@@ -26,10 +26,10 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 309 /* 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 310 /* 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
-enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply only */ };
+enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
 
 typedef void* xvit_stream_t; /* hipStream_t */
 
@@ -331,10 +331,12 @@ int xvit_resize_pad_crop_i16(const void* src_i16, void* dst_bf16, int nvol, int 
  * Record (fp32 slots):
  *    0..11  A | t, row-major 3 x 4: source voxel index p = A (z, y, x) + t for the destination voxel index (z, y, x)
  *    12, 13 intensity: v = a v + b                       14  noise sigma (0: no noise)
- *    15     noise seed, a uint32 bit pattern             16  flags (integer-valued): bit 0 = exact path: A is a diagonal of +-1 and t is integral
+ *    15     noise seed, a uint32 bit pattern             16  flags (integer-valued): bit 0 = exact path: A is a diagonal of +-1 and t is integral;
+ *                                                            bit 1 = clamp: the resampled value is clamped to [slot 29, slot 30] before a v + b
  *    17..19 flips (1 = the axis is reversed)             20..22 rotation angles, radians (0 when not drawn)
- *    23..25 zooms (1 when not drawn)                     26..28 translation in voxels (0 when not drawn)        29..31 zero
- * Slots 17..28 record what was drawn; xvit_augment_apply reads slots 0..16 only.
+ *    23..25 zooms (1 when not drawn)                     26..28 translation in voxels (0 when not drawn)
+ *    29, 30 clamp window lo, hi in SOURCE units (zero as drawn; xvit_volume_stats writes them)                   31  zero
+ * Slots 17..28 record what was drawn; xvit_augment_apply reads slots 0..16 and, only when flag bit 1 is set, slots 29 and 30.
  *
  * xvit_augment_draw.  Uniform numbers are u(i) = (hash32(seed', i) & 0xFFFFFF) / 2^24 with the dropout hash (xvit_dropout), seed' = seed +
  * *counter * 0xD1B54A32D192ED03 when a device counter is given (read at run time; advance != 0: one thread stores counter + 1 after every
@@ -354,7 +356,9 @@ int xvit_resize_pad_crop_i16(const void* src_i16, void* dst_bf16, int nvol, int 
  *
  * xvit_augment_apply.  src [nvol, Ds, Hs, Ws] int16 / bf16 / fp32 -> dst [nvol, D, H, W] bf16 / fp32, both contiguous; a volume has fewer than
  * 2^31 voxels on either side.  General path: trilinear interpolation at p (fp32), source voxels outside the volume counting as pad_value
- * (borders blend with it); exact path (flag bit 0): the source voxel at the integer index is copied (a flip is a reversed run).  Then
+ * (borders blend with it); exact path (flag bit 0): the source voxel at the integer index is copied (a flip is a reversed run).  With
+ * flag bit 1 (XVIT_AUG_FLAG_CLAMP) the value, pad_value included, is then clamped in source units, v = fminf(fmaxf(v, lo), hi) with lo, hi
+ * of slots 29, 30 (a NaN becomes lo); with the bit clear nothing of this happens and the slots are not read.  Then
  * v = a v + b; sigma > 0: v += sigma n with n = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((hash32(noise_seed, 2 i) & 0xFFFFFF) + 1) / 2^24,
  * u2 = (hash32(noise_seed, 2 i + 1) & 0xFFFFFF) / 2^24 for voxel i = (z H + y) W + x of its volume; one rounding to the destination dtype.
  * With a = 1, b = 0, sigma = 0, int16 -> bf16 the exact path reproduces xvit_resize_pad_crop_i16 bit for bit.  A workgroup owns one
@@ -362,8 +366,8 @@ int xvit_resize_pad_crop_i16(const void* src_i16, void* dst_bf16, int nvol, int 
  * ---------------------------------------------------------------------------------------- */
 #define XVIT_AUG_NPARAM 32
 enum { XVIT_AUG_MATRIX = 0, XVIT_AUG_SCALE = 12, XVIT_AUG_SHIFT = 13, XVIT_AUG_SIGMA = 14, XVIT_AUG_NOISE_SEED = 15, XVIT_AUG_FLAGS = 16,
-       XVIT_AUG_FLIPS = 17, XVIT_AUG_ANGLES = 20, XVIT_AUG_ZOOMS = 23, XVIT_AUG_TRANSLATION = 26 };
-enum { XVIT_AUG_FLAG_EXACT = 1 };
+       XVIT_AUG_FLIPS = 17, XVIT_AUG_ANGLES = 20, XVIT_AUG_ZOOMS = 23, XVIT_AUG_TRANSLATION = 26, XVIT_AUG_CLAMP_LO = 29, XVIT_AUG_CLAMP_HI = 30 };
+enum { XVIT_AUG_FLAG_EXACT = 1, XVIT_AUG_FLAG_CLAMP = 2 };
 typedef struct xvit_augment_config {
   float flip_prob[3];                          /* per axis z, y, x */
   float rotate_prob, rotate_range[3];          /* radians, about z, y, x */
@@ -378,6 +382,62 @@ int xvit_augment_draw(const xvit_augment_config* config, float* params, int B, i
                       uint64_t* counter, int advance, xvit_stream_t stream);
 int xvit_augment_apply(const void* src, int src_dtype, void* dst, int dst_dtype, const float* params, int nvol, int Ds, int Hs, int Ws, int D, int H,
                        int W, float pad_value, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-volume intensity statistics and normalisation (stands where a loader runs MONAI's NormalizeIntensity(nonzero=True) or
+ * ScaleIntensityRangePercentiles on the CPU: MRI intensities carry no unit, so every volume is normalised by its own statistics).  The
+ * rule is this project's own; parity with MONAI's numerics is NOT claimed.
+ *
+ * A 16-bit source has at most 65 536 distinct values, so a per-volume histogram holds everything needed, exactly, and integer atomics make
+ * it independent of the execution order: the result is bit-reproducible with no switch.  Sources: int16, keyed by v + 32768; bf16, keyed
+ * by a monotone key of the bit pattern (all bits of negative patterns flipped, the sign bit of the others set), so that key order is value
+ * order (-0.0 sorts directly below +0.0).  fp32 sources are refused: there is no 2^32-bin path.
+ *
+ * Definitions, per volume and over the whole source volume (src [nvol, nvox], contiguous), not the crop:
+ *    Foreground  F = { v : v > foreground_above }.  NaN compares false and is never foreground.  n = |F|.
+ *    With percentiles (q_lo, q_hi), 0 <= q_lo <= q_hi <= 1:  k = max(1, ceil(q n)), computed in double from the fp32 q (nearest rank);
+ *    lo is the k_lo-th smallest value of F and hi the k_hi-th smallest.  Without percentiles (q_lo < 0): lo = min F, hi = max F.
+ *    W = { v in F : lo <= v <= hi },  n_w = |W|.
+ *    mu is the mean of W;  sigma = sqrt(mean((v - mu)^2)) over W, the population standard deviation.
+ * sigma is taken in two passes over the HISTOGRAM: mu first, then sum h (v - mu)^2 in double (no sum v^2 - (sum v)^2 / n cancellation).
+ * For int16, sum h v is an exact int64 sum and mu = (double)S / n_w is rounded once; for bf16 the sum is a double sum in a fixed order.
+ *
+ * stats [nvol, XVIT_STATS_NSTAT] (fp64, 8-byte aligned):  n, n_w, mu, sigma, lo, hi, min F, max F.   n = 0 gives a record of zeros.
+ *
+ * Folding (params != NULL and mode != XVIT_NORM_STATS_ONLY): params is the table of xvit_augment_draw, [nvol, XVIT_AUG_NPARAM].  With
+ * (a, b) the record's slots 12 / 13 as the draw wrote them,
+ *    XVIT_NORM_ZSCORE:  a_n = 1 / sigma', b_n = -mu / sigma',  sigma' = sigma if sigma > 0, else 1;
+ *    XVIT_NORM_WINDOW:  r = hi - lo if positive, else 1;  a_n = 1 / r, b_n = -lo / r;
+ *    n = 0:  a_n = 1, b_n = 0, no clamp (the record is left as it is);
+ *    SCALE <- fl32(a a_n),  SHIFT <- fl32(a b_n + b), both computed in double: the normalisation comes first and the drawn scale / shift
+ *    act on normalised values.  With clip != 0: slot 29 <- lo, slot 30 <- hi (exact in fp32 for either source type) and
+ *    FLAGS |= XVIT_AUG_FLAG_CLAMP, so that xvit_augment_apply clamps the resampled source-unit value to [lo, hi] before a v + b (padding
+ *    included: the background lands on the window floor).  No other slot is written.
+ *
+ * Two launches.  (a) The histogram counts foreground voxels only (the background bin would otherwise take more than half of a brain
+ * volume's voxels in one address), in 32-bit counters: keys in [XVIT_STATS_WINDOW_LO, XVIT_STATS_WINDOW_LO + XVIT_STATS_WINDOW_BINS), the
+ * non-negative half of either key space, are counted in LDS and flushed with global integer atomics, the others go straight to global
+ * memory.  The window is a performance choice; no result depends on it.  16-byte loads with a scalar head and tail per workgroup (a volume's
+ * base is only 2-byte aligned when nvox is odd).  (b) One workgroup per volume scans its 65 536 bins: prefix counts -> lo, hi, n_w, mu, then
+ * sigma; it writes the record, folds, and leaves the histogram zeroed.  The workspace (xvit_volume_stats_workspace_bytes(nvol), 16-byte
+ * aligned, caller-owned) must therefore be zero-filled ONCE by the caller and is zero again after every call: no memset, and the pair can
+ * be captured in a graph.  One workspace serves one stream at a time.
+ * Argument errors, raised before any launch: null pointers, an fp32 or unknown source dtype, nvol <= 0, nvox <= 0 or >= 2^31, an unknown
+ * mode, a NaN foreground_above, percentiles out of order or above 1, misaligned stats / params / workspace, a workspace that is too small.
+ * cfg is a HOST struct, read during the call.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_STATS_NSTAT 8
+enum { XVIT_STATS_WINDOW_LO = 32768, XVIT_STATS_WINDOW_BINS = 32768 };
+enum { XVIT_NORM_STATS_ONLY = 0, XVIT_NORM_ZSCORE = 1, XVIT_NORM_WINDOW = 2 };
+typedef struct xvit_norm_config {
+  int mode;                /* 0 stats only, 1 zscore, 2 window */
+  int clip;                /* != 0: write the clamp window and set XVIT_AUG_FLAG_CLAMP */
+  float foreground_above;  /* F = { v > foreground_above }; -inf: every voxel that is not NaN */
+  float q_lo, q_hi;        /* q_lo < 0: no percentiles */
+} xvit_norm_config;
+int64_t xvit_volume_stats_workspace_bytes(int nvol);
+int xvit_volume_stats(const void* src, int src_dtype, int nvol, int64_t nvox, const xvit_norm_config* cfg, double* stats, float* params /* NULL: no fold */,
+                      void* workspace, int64_t workspace_bytes, xvit_stream_t stream);
 
 /* x[m, b, 0, :] = cls + pos[0]  (model_cross.py:195-197, the CLS row); x fp32 [M*B, N, d] */
 int xvit_cls_row_fwd(const float* cls, const float* pos, float* x, int MB, int N, int d, xvit_stream_t stream);

@@ -3,10 +3,14 @@
     python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE]
 
 Arms, interleaved inside every repeat (so that drift hits them alike): xvit_resize_pad_crop_i16 (twice: two identical arms), the exact
-path as identity, the exact path with all three flips, the general path (every random transform on) and the draw kernel.  Times are
+path as identity, the exact path with all three flips, the general path (every random transform on), the draw kernel, the statistics pair
+of xvit_volume_stats alone (histogram + scan, 0.5 % / 99.5 % percentiles, no fold) and the whole stage (every random transform on) without
+and with normalize="zscore" (two and four launches).  Times are
 device-event times per launch (median over the repeats); GB/s counts the source bytes the destination maps to, read once, plus the
 destination bytes.  The identity arm is held against xvit_resize_pad_crop_i16: it may be slower by no more than the spread, which is the
-largest max - min over the repeats of the two identical arms.  Exit status 1 when it is.  The other arms are reported, not gated."""
+largest max - min over the repeats of the two identical arms.  Exit status 1 when it is.  The other arms are reported, not gated: the
+statistics pair against the time of reading every raw volume once at the achievable HBM rate (6.3 TB/s) and against the apply launches of
+the same run."""
 from __future__ import annotations
 
 import argparse
@@ -30,7 +34,7 @@ def main() -> int:
     if not torch.cuda.is_available():
         raise SystemExit("augment_bench: needs a GPU; a CPU run measures nothing")
     from xvit import ops
-    from xvit.augment import AugmentParams, VolumeAugment
+    from xvit.augment import NSTAT, AugmentParams, VolumeAugment, norm_config
 
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
@@ -45,6 +49,12 @@ def main() -> int:
     assert bool(t_ident.exact.all()) and bool(t_flip.exact.all()) and not bool(t_full.exact.any())
     assert torch.equal(ident.apply(src, t_ident).view(torch.int16), ops.resize_pad_crop_i16(src, DST, -1.0).view(torch.int16))
     table = AugmentParams(torch.empty(B, M, 32, dtype=torch.float32, device=dev))
+    on = dict(flip_prob=(1, 1, 1), rotate_prob=1, zoom_prob=1, translate_prob=1, scale_intensity_prob=1, shift_intensity_prob=1, noise_prob=0)
+    stage_plain = VolumeAugment(DST, intensity_scale=1e-3, **on)
+    stage_norm = VolumeAugment(DST, normalize="zscore", **on)
+    stats_cfg = norm_config(None, 0.0, (0.005, 0.995))
+    stats = torch.empty(B, M, NSTAT, dtype=torch.float64, device=dev)
+    workspace = ops.volume_stats_workspace(B * M, dev)
 
     arms = [
         ("xvit_resize_pad_crop_i16", lambda: ops.resize_pad_crop_i16(src, DST, -1.0)),
@@ -52,6 +62,9 @@ def main() -> int:
         ("exact path, three flips", lambda: ident.apply(src, t_flip)),
         ("general path", lambda: ident.apply(src, t_full)),
         ("draw kernel", lambda: ops.augment_draw(full.config, table.table, SRC, DST, 1)),
+        ("statistics pair", lambda: ops.volume_stats(src, stats_cfg, stats, workspace)),
+        ("stage, normalize=None", lambda: stage_plain(src)),
+        ("stage, normalize=zscore", lambda: stage_norm(src)),
         ("xvit_resize_pad_crop_i16 (again)", lambda: ops.resize_pad_crop_i16(src, DST, -1.0)),
     ]
     for _, fn in arms:          # warm-up: code objects, allocator
@@ -71,13 +84,14 @@ def main() -> int:
     nvol = B * M
     src_elems = nvol * min(SRC[0], DST[0]) * min(SRC[1], DST[1]) * min(SRC[2], DST[2])
     nbytes = src_elems * 2 + nvol * DST[0] * DST[1] * DST[2] * 2
+    raw_bytes = src.numel() * 2
     lines = [f"augment_bench: B={B} M={M} {SRC} int16 -> {DST} bf16, {a.reps} repeats x {a.inner} launches per arm, interleaved; "
              f"{nbytes / 1e6:.1f} MB per launch (source region read once + destination)"]
     med = {}
     for name, _ in arms:
         t = times[name]
         med[name] = statistics.median(t)
-        rate = "" if name == "draw kernel" else f"  {nbytes / med[name] / 1e3:8.1f} GB/s"
+        rate = "" if name == "draw kernel" or name.startswith("stage") else f"  {(raw_bytes if name == 'statistics pair' else nbytes) / med[name] / 1e3:8.1f} GB/s"
         lines.append(f"  {name:34s} median {med[name]:8.2f} us  (min {min(t):8.2f}, max {max(t):8.2f}){rate}")
     same = ("xvit_resize_pad_crop_i16", "xvit_resize_pad_crop_i16 (again)")
     spread = max(max(times[n]) - min(times[n]) for n in same)
@@ -86,6 +100,11 @@ def main() -> int:
     ok = delta <= spread
     lines.append(f"  identity vs xvit_resize_pad_crop_i16: {delta:+.2f} us ({med['exact path, identity'] / ref:.3f} x); spread between the identical arms' repeats "
                  f"{spread:.2f} us; the two identical arms' medians differ by {abs(med[same[0]] - med[same[1]]):.2f} us -> {'OK' if ok else 'SLOWER THAN THE SPREAD ALLOWS'}")
+    pair, floor = med["statistics pair"], raw_bytes / 6.3e12 * 1e6
+    lines.append(f"  statistics pair: reads {raw_bytes / 1e6:.1f} MB of raw volumes (GB/s above counts these); once at 6.3 TB/s is {floor:.1f} us: {pair / floor:.2f} x that; "
+                 f"{pair / med['general path']:.2f} x the general-path apply, {pair / med['exact path, identity']:.2f} x the identity apply")
+    lines.append(f"  stage with normalize=zscore - stage without: {med['stage, normalize=zscore'] - med['stage, normalize=None']:+.2f} us "
+                 f"(statistics pair alone {pair:.2f} us)")
     text = "\n".join(lines)
     print(text)
     if a.out:
