@@ -522,8 +522,9 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict_
 
 // Sum of g*g over one 16384-element chunk per block, written with ONE plain store to partials[blockIdx.x]: no float atomics, so the
 // norm is bit-identical from run to run.  Summation order per chunk (all fp32, the products fused into the adds): 16-byte path: four
-// accumulators per thread, 16 sequential adds each, 2 adds to join them; scalar path: 64 sequential adds; then 6 levels across the
-// wave and 3 adds across the four waves.  With non-negative terms that is a relative error of at most (64 + 6 + 3 + 1) * 2^-24 = 4.4e-6.
+// accumulators per thread, 16 sequential adds each (one more for a tail element), 2 levels to join them; scalar path: 64 sequential
+// adds; then 6 levels across the wave and 3 adds across the four waves, 2 of them on any path.  With non-negative terms the relative
+// error is at most the roundings on the longest path: (64 + 6 + 2) * 2^-24 = 4.3e-6 (scalar), (17 + 2 + 6 + 2) * 2^-24 = 1.6e-6 (16-byte).
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const AdamTensor* __restrict__ table, const int2* __restrict__ chunks, float* __restrict__ partials) {
   __shared__ float wave_part[4];
   const int2 ch = chunks[blockIdx.x];

@@ -348,3 +348,16 @@ def test_rows_combine_all_dtype_and_stride_combinations():
     assert float(t5[:, 0].abs().max()) == 0.0 and float(t5b[:, 0].float().abs().max()) == 0.0 and torch.equal(t5[:, 1:], tok[:, 1:])
     with pytest.raises(AssertionError):
         ops.rows_combine(tok[:, :, 0], a=vec[:, :N])      # last stride must be one
+
+
+@pytest.mark.parametrize("d", [1, 255, 256, 257, 513])
+def test_rows_combine_every_pairing_at_the_column_loop_edges(d):
+    """d round 256 and 512 (the c += 256 loop runs once, twice and three times), rows 1 and 3, every dtype pairing of dst / dst2 / a / b
+    with a-only, b-only and neither, `dst is a`, four different row strides larger than d: bit for bit, with sentinels in the padding and a
+    guard row behind every destination (tests/_optim_check.py rows_combine_check)."""
+    import _optim_check as X
+    n = 0
+    for case in X.rows_combine_cases(d):
+        X.rows_combine_check(*case)
+        n += 1
+    assert n == 2 * (54 + 18)
