@@ -38,6 +38,7 @@ struct GemmParams {
   int aux_deriv = 0;             // aux holds GELU'(z) instead of z: ACT_GELU writes the derivative, ACT_DGELU multiplies by it
   int narrow_epi = 0;            // force the 8-byte-per-lane epilogue (A/B measurements)
   int ncg = 1;                   // gemm_big_kernel: column tiles per super-column of the tile walk
+  int res_in_body = 0;           // load the fp32 residual inside the epilogue body instead of one region ahead (A/B measurements)
   // Patch rows gathered straight from the volume (xvit_patch_embed_*; reference model_cross.py:193, the einops rearrange
   // 'b c (d p1) (h p2) (w p3) -> b (h w d) (p1 p2 p3 c)' in front of patch_to_embedding): the [rows, dp hp wp] patch matrix is
   // never stored.  mode 1: the A rows of the forward NT product; mode 2: the weight gradient (TN), whose contraction runs over
@@ -584,11 +585,17 @@ struct BigEpi {
 // stores retire through ONE in-order vmcnt, so a load issued right after a region's stores can only be waited for once
 // those stores have been acknowledged by memory.  Loading z inside each body cost the GELU' dgrad ~15 us per tile round
 // (505 TFLOP/s where the same shape without an epilogue load reaches 860).  LoadCursor is a second copy of the row state
-// that runs one region ahead of the store cursor in BigEpi.  (The fp32 residual loads of the out-proj / FFN2 epilogues
-// stay in the body: those epilogues are bound by their 8 B/element of HBM traffic, and prefetching them as well doubled
-// the number of inlined epilogue variants — minutes of compile time and register spills.)
-struct LoadCursor { uint32_t row, aux; };
-struct EpiLoads { u32x2_t aux[4]; };
+// that runs one region ahead of the store cursor in BigEpi.
+// The fp32 residual of the plain bias + residual epilogues (out-proj, FFN2, patch embedding: no activation, dropout, accumulate
+// or split-K slab) is prefetched the same way, RESPF below, through the same cursor: it carries the residual offset and its row
+// modulo and steps them with the body's rule.  Only those two copies (PERM or not) exist; every other epilogue keeps the load
+// in its body, because a prefetching twin of each (activation, dropout) variant doubled the inlined epilogues behind one K
+// loop: minutes of compile time and register spills.  Those epilogues are NOT bound by their 8 B/element of HBM traffic, as was
+// assumed here before: with the load in the body each body waited a memory round trip behind the previous rows' stores.
+// Measured at configs[1] (profiles/gemm_res_prefetch_ab.txt, parent against this build, alternated on one box): out-proj
+// 150.0 -> 124.4 us, FFN2 315.5 -> 292.5, the patch-embedding shape 764 -> 715, bench.py 34.93 -> 34.37 ms per step.
+struct LoadCursor { uint32_t row, aux, res, rrem; };
+struct EpiLoads { u32x2_t aux[4]; u32x4_t res[4]; };
 
 __device__ __forceinline__ void big_epi_issue_aux(const GemmParams& p, const BigEpi& e, LoadCursor& lc, EpiLoads& L) {
 #pragma unroll
@@ -599,10 +606,24 @@ __device__ __forceinline__ void big_epi_issue_aux(const GemmParams& p, const Big
   }
 }
 
-template <int ACT, bool DROP>
-__device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32x4 v, u32x2_t auxv) {
+// e.rres is not clamped to the tensor's size: rows past M and columns past N are kept out by the predicate alone
+__device__ __forceinline__ void big_epi_issue_res(const GemmParams& p, const BigEpi& e, LoadCursor& lc, EpiLoads& L) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const bool ok = e.col_ok && lc.row < (uint32_t)p.M;
+    L.res[b] = __builtin_amdgcn_raw_buffer_load_b128(e.rres, ok ? lc.res : OOB, 0, XVIT_EPI_RES_AUX);
+    lc.row += 4; lc.res += e.res_step; lc.rrem += 4;
+    if (lc.rrem >= e.rmod) { lc.rrem -= e.rmod; lc.res -= e.res_wrap; }
+  }
+}
+
+// RESPF: `resv` is this body's residual, loaded one region ahead (wave_tile_epilogue takes this copy only for a residual
+// with no split-K slab and no accumulate)
+template <int ACT, bool DROP, bool RESPF = false>
+__device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32x4 v, u32x2_t auxv, u32x4_t resv) {
+  static_assert(!RESPF || (ACT == XVIT_ACT_NONE && !DROP), "the residual is prefetched in the plain bias + residual epilogue only");
   const bool ok = e.col_ok && e.row < (uint32_t)p.M;
-  if (e.to_slab) {   // split-K partial sums, [M][N] fp32
+  if (!RESPF && e.to_slab) {   // split-K partial sums, [M][N] fp32
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), e.rslab, ok ? e.slab : OOB, 0, XVIT_EPI_STORE_AUX);
   } else {
     v += e.bias;
@@ -621,10 +642,11 @@ __device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32
       else act4<XVIT_ACT_DGELU>(v, d, z);
     }
     if (DROP) dropout4(p, v, e.drop_base + (uint64_t)e.row * p.N + e.col);
-    if (e.has_res) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(e.rres, ok ? e.res : OOB, 0, XVIT_EPI_RES_AUX));
+    if constexpr (RESPF) v += __builtin_bit_cast(f32x4, resv);
+    else if (e.has_res) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(e.rres, ok ? e.res : OOB, 0, XVIT_EPI_RES_AUX));
     if (p.c_f32) {
       const uint32_t off = ok ? e.c : OOB;
-      if (p.accumulate) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(e.rc, off, 0, 0));
+      if (!RESPF && p.accumulate) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(e.rc, off, 0, 0));
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), e.rc, off, 0, XVIT_EPI_STORE_AUX);
     } else {
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, to_bf16x4(v)), e.rc, ok ? e.c : OOB, 0, XVIT_EPI_STORE_AUX);
@@ -641,8 +663,8 @@ __device__ __forceinline__ void big_epi_body(const GemmParams& p, BigEpi& e, f32
 
 // Region R (0..7) of the wave's 128-row tile = 4 bodies = rows 16 R .. 16 R + 15; regions 0-3 and 4-7 share one LDS
 // transpose pass each (64 rows: accumulators -> LDS column-wise, read back row-wise).  `cur` holds this region's
-// pre-issued z loads (GELU' only); the next region's are issued before this region's stores.
-template <int ACT, bool DROP, int R, bool PERM = false>
+// pre-issued z loads (GELU' only) or residual loads (RESPF only); the next region's are issued before this region's stores.
+template <int ACT, bool DROP, int R, bool PERM = false, bool RESPF = false>
 __device__ __forceinline__ void big_epi_regions(const GemmParams& p, BigEpi& e, LoadCursor& lc, EpiLoads& cur, const f32x4 (&acc)[8][4], XVIT_LDS char* slice,
                                                 const uint32_t (&woff)[8], const uint32_t (&roff)[4]) {
   if constexpr ((R & 3) == 0) {
@@ -657,23 +679,25 @@ __device__ __forceinline__ void big_epi_regions(const GemmParams& p, BigEpi& e, 
   }
   EpiLoads nxt;
   if constexpr (ACT == XVIT_ACT_DGELU && R < 7) big_epi_issue_aux(p, e, lc, nxt);
+  if constexpr (RESPF && R < 7) big_epi_issue_res(p, e, lc, nxt);
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     const int it = (R & 3) * 4 + b;
     const f32x4 v = *(const XVIT_LDS f32x4*)(slice + it * 1024 + roff[it & 3]);
-    big_epi_body<ACT, DROP>(p, e, v, cur.aux[b]);
+    big_epi_body<ACT, DROP, RESPF>(p, e, v, cur.aux[b], cur.res[b]);
   }
   __builtin_amdgcn_sched_barrier(0);   // one region per scheduling window
-  if constexpr (R < 7) big_epi_regions<ACT, DROP, R + 1, PERM>(p, e, lc, nxt, acc, slice, woff, roff);
+  if constexpr (R < 7) big_epi_regions<ACT, DROP, R + 1, PERM, RESPF>(p, e, lc, nxt, acc, slice, woff, roff);
 }
 
-template <int ACT, bool DROP, bool PERM = false>
+template <int ACT, bool DROP, bool PERM = false, bool RESPF = false>
 __device__ __forceinline__ void big_epilogue(const GemmParams& p, BigEpi& e, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, const uint32_t (&woff)[8],
                                              const uint32_t (&roff)[4]) {
-  LoadCursor lc = {e.row, e.aux};
+  LoadCursor lc = {e.row, e.aux, e.res, e.rrem};
   EpiLoads first;
   if constexpr (ACT == XVIT_ACT_DGELU) big_epi_issue_aux(p, e, lc, first);
-  big_epi_regions<ACT, DROP, 0, PERM>(p, e, lc, first, acc, slice, woff, roff);
+  if constexpr (RESPF) big_epi_issue_res(p, e, lc, first);
+  big_epi_regions<ACT, DROP, 0, PERM, RESPF>(p, e, lc, first, acc, slice, woff, roff);
   if (p.colsum && !e.to_slab) colsum_flush<16>(e.colsum_dst, e.csum, e.col_ok);   // += column sums of the stored tile
 }
 
@@ -839,7 +863,9 @@ __device__ __forceinline__ void wave_tile_epilogue_wide(const GemmParams& p, con
 
 // Epilogue of one wave's 128 x 64 accumulator tile whose first element is (row0, col0); shared by every tile kernel
 // (the block's stage buffers are idle by now: wave w bounces through smem + w * EPI_WAVE_BYTES).
-template <bool PERM = false>
+// RES_PF: this kernel may carry a residual, so it holds the prefetching copy of the plain epilogue (the patch-embedding
+// weight gradients never do).
+template <bool PERM = false, bool RES_PF = true>
 __device__ __forceinline__ void wave_tile_epilogue(const GemmParams& p, const f32x4 (&acc)[8][4], XVIT_LDS char* smem, int wave, int lane, int row0, int col0,
                                                    int batch, int split) {
   const int nbatch = gridDim.z / p.split_k;
@@ -901,9 +927,18 @@ __device__ __forceinline__ void wave_tile_epilogue(const GemmParams& p, const f3
     e.res_wrap = rmap ? e.rmod * (uint32_t)p.ldr * 4u : 0u;
   }
   // one specialised, fully unrolled copy per (activation, dropout): every acc[][] index is a compile-time constant
+  // a plain bias + residual epilogue loads its residual one region ahead; nothing is read where the split-K reduce adds it
+  const bool res_pf = RES_PF && e.has_res && !e.to_slab && !p.accumulate && p.act == XVIT_ACT_NONE && p.drop_p == 0.f && !p.res_in_body;
   if constexpr (PERM) {   // the patch-embedding forward: bias + positional residual only
-    big_epilogue<XVIT_ACT_NONE, false, true>(p, e, acc, slice, woff, roff);
+    if (res_pf) big_epilogue<XVIT_ACT_NONE, false, true, true>(p, e, acc, slice, woff, roff);
+    else big_epilogue<XVIT_ACT_NONE, false, true>(p, e, acc, slice, woff, roff);
     return;
+  }
+  if constexpr (RES_PF) {
+    if (res_pf) {
+      big_epilogue<XVIT_ACT_NONE, false, false, true>(p, e, acc, slice, woff, roff);
+      return;
+    }
   }
   if (p.drop_p > 0.f) {
     if (p.act == XVIT_ACT_GELU) big_epilogue<XVIT_ACT_GELU, true>(p, e, acc, slice, woff, roff);
@@ -1075,7 +1110,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
   __syncthreads();   // every wave is done reading the last stage: the stage buffers become the transpose slices
   if constexpr (GATHER == 4) scatter_epilogue(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64);
   else if constexpr (WIDE_ACT >= 0) wave_tile_epilogue_wide<WIDE_ACT>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch);
-  else wave_tile_epilogue<GATHER == 1>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch, split);
+  else wave_tile_epilogue<GATHER == 1, GATHER <= 1>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch, split);
 }
 
 // split-K second pass: sum the partial tiles in a fixed order (bit-reproducible), then the full epilogue
@@ -1108,6 +1143,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // (e.g. the reference's batch 8: M = 4104 rows -> 17 x 3 big tiles for a d-wide GEMM).
 static std::atomic<int> g_gemm_tile{0};      // xvit_set_option("gemm_tile"): 0 = auto, 1 = always the 128x128 kernel
 static std::atomic<int> g_gemm_epi{0};       // xvit_set_option("gemm_epilogue"): 0 = auto, 1 = always the 8-byte-per-lane epilogue
+static std::atomic<int> g_gemm_res_pf{0};    // xvit_set_option("gemm_res_prefetch"): 0 = fp32 residual loaded one region ahead, 1 = loaded in the epilogue body
 static std::atomic<int> g_gemm_group{0};     // xvit_set_option("gemm_group"): 0 = auto, n > 0 = column tiles per super-column of the 256x256 tile walk
 
 static bool use_big_tile(const xvit_gemm_args* a) {
@@ -1157,6 +1193,7 @@ extern "C" int xvit_set_option(const char* name, int value) {
   if (n == "gemm_tile") { XVIT_REQUIRE(value >= 0 && value <= 2, "xvit_set_option: gemm_tile must be 0 (auto), 1 (128x128 only) or 2 (256x256 whenever M, N >= 256)"); g_gemm_tile = value; return 0; }
   if (n == "gemm_group") { XVIT_REQUIRE(value >= 0 && value <= 4096, "xvit_set_option: gemm_group must be in [0, 4096]"); g_gemm_group = value; return 0; }
   if (n == "gemm_epilogue") { XVIT_REQUIRE(value == 0 || value == 1, "xvit_set_option: gemm_epilogue must be 0 (auto) or 1 (narrow)"); g_gemm_epi = value; return 0; }
+  if (n == "gemm_res_prefetch") { XVIT_REQUIRE(value == 0 || value == 1, "xvit_set_option: gemm_res_prefetch must be 0 (one region ahead) or 1 (in the body)"); g_gemm_res_pf = value; return 0; }
   if (n == "attn_peel") { XVIT_REQUIRE(value >= 0 && value <= 2, "xvit_set_option: attn_peel must be 0 (token 0 stays on the tile grid), 1 (auto: large grids) or 2 (whenever N = 64 m + 1)"); set_attn_peel(value); return 0; }
   set_error("xvit_set_option: unknown option '%s'", name);
   return XVIT_ERR_ARG;
@@ -1217,6 +1254,7 @@ extern "C" int xvit_gemm(const xvit_gemm_args* a, xvit_stream_t stream) {
   p.drop_p = a->dropout_p; p.drop_inv = 1.0f / (1.0f - a->dropout_p); p.drop_seed = a->dropout_seed;
   p.drop_epoch = a->dropout_p > 0.f ? drop_epoch_ptr() : nullptr;
   p.narrow_epi = g_gemm_epi.load(std::memory_order_relaxed);
+  p.res_in_body = g_gemm_res_pf.load(std::memory_order_relaxed);
   p.aux_deriv = a->aux_mode;
   hipStream_t s = (hipStream_t)stream;
   const int gz = a->batch * a->split_k;
@@ -1315,6 +1353,7 @@ extern "C" int xvit_patch_embed_fwd(const void* img, const xvit_patch_geom* g, c
   p.ldb = ldw; p.ldc = ldx; p.ldr = ldpos;
   p.M = (int)pe_rows(g); p.N = d; p.K = (int)pd;
   p.k_per_split = p.K;
+  p.res_in_body = g_gemm_res_pf.load(std::memory_order_relaxed);
   if (pos) { p.res_row_mod = p.g.ntok; p.res_row_off = 0; }   // x row (s, n) += pos[n]  (model_cross.py:197)
   set_tile_grid(p, TBM, XVIT_GEMM_NT, false);
   launch_big<false, false, -1, 1>(p, 1, (hipStream_t)stream);
