@@ -350,6 +350,15 @@ class ModelCross(EpochStatsMixin, _Base):
         self.transformer = nn.Sequential(*(MultiScaleBlock(config) for _ in range(config.num_multi_blocks)))
         self.norm = nn.ModuleList(nn.LayerNorm(d) for _ in range(M))
         self.mlp_head = nn.ModuleList(_mlp_container(config, config.num_classes) for _ in range(M))
+        # patch dropout (not in the reference; off unless the config carries a rate): in train() every sequence keeps a random
+        # subset of its patch tokens, the same for all modalities of a sample with patch_dropout_shared; eval() keeps every token
+        self.patch_dropout = float(getattr(config, "patch_dropout", 0.0))
+        self.patch_dropout_shared = bool(getattr(config, "patch_dropout_shared", False))
+        if not 0.0 <= self.patch_dropout < 1.0:
+            raise ValueError(f"patch_dropout must be in [0, 1), got {self.patch_dropout}")
+        # int32 [M, B, K]: the patch indices the last forward kept (None: it kept them all).  The tensor a capture leaves here is the
+        # graph's own and follows its replays; any later forward call replaces the attribute, not that tensor
+        self.last_token_keep = None
         self.initialize_model()
 
     def _sync_flat_weights(self):
@@ -365,6 +374,17 @@ class ModelCross(EpochStatsMixin, _Base):
         grp.refresh(force=XF.SHADOWS.force)
         XF.SHADOWS.force = False
 
+    def _draw_token_keep(self, img):
+        """Patch dropout: draw, on the current stream and without a host read-back, which K of the P patches each of the M * B sequences
+        keeps -> (keep_idx int32 [M*B, K], slot int32 [M*B, P]).  The pair is allocated by every forward, like the activations: under
+        capture it lives in the graph's own pool, so a replay redraws into memory that no eager step of another batch can move or free.
+        The seed comes from the dropout seed stream."""
+        B, M, P = img.shape[0], self.num_modalities, self.pos_embedding.shape[1] - 1
+        K = XF.patch_keep_count(P, self.patch_dropout)
+        keep_idx = torch.empty(M * B, K, dtype=torch.int32, device=img.device)
+        slot = torch.empty(M * B, P, dtype=torch.int32, device=img.device)
+        return XF.ops.token_select_draw(keep_idx, slot, B, self.patch_dropout_shared, XF.drop_seeds(1)[0])
+
     def forward(self, img, labels):
         if self.pos_embedding.is_cuda and os.environ.get("XVIT_FLAT_WEIGHTS", "1") != "0":
             self._sync_flat_weights()
@@ -372,8 +392,10 @@ class ModelCross(EpochStatsMixin, _Base):
             raise ValueError(f"expected {self.num_modalities} modalities, got {img.shape[1]}")
         if img.is_cuda and torch.is_grad_enabled():
             XF.arena_begin(img.device)                   # the backward's small zeroed vectors: one fill per step (functional._zeros)
+        keep = self._draw_token_keep(img) if self.training and self.patch_dropout > 0.0 else None
+        self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
         tokens = XF.PatchEmbedFn.apply(img, self.patch_to_embedding.weight, self.patch_to_embedding.bias,
-                                       self.cls_token, self.pos_embedding, self.patch_size, _p(self, self.dropout))
+                                       self.cls_token, self.pos_embedding, self.patch_size, _p(self, self.dropout), False, keep)
         x = list(tokens)
         for k, blk in enumerate(self.transformer):                       # nn.Sequential of MultiScaleBlocks (model_cross.py:171)
             last = k == len(self.transformer) - 1                        # only x[m][:, 0] of the last block is read below (model_cross.py:203) ...

@@ -10,6 +10,7 @@ are re-cast whenever a parameter's version changes (i.e. after every optimizer s
 from __future__ import annotations
 
 import contextvars
+import math
 import os
 import weakref
 
@@ -765,14 +766,30 @@ class CrossFusionFn(Function):
 # ------------------------------------------------------------------------------------------
 
 
+def patch_keep_count(P, p):
+    """How many of the P patch tokens a sequence keeps at patch-dropout rate p: K = floor(P (1 - p)), at least 1, rounded down to a
+    multiple of 64 where that leaves 64 or more — the sequence length N = K + 1 then has the 64 m + 1 shape the attention kernels'
+    CLS-peel form takes."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"patch_keep_count: the rate must be in [0, 1), got {p}")
+    K = max(1, int(math.floor(P * (1.0 - p))))
+    return K - K % 64 if K >= 64 else K
+
+
 class PatchEmbedFn(Function):
-    """img [B, M, 1, D, H, W] -> tokens fp32 [M, B, N, d] = cat(cls, patches W^T + b) + pos."""
+    """img [B, M, 1, D, H, W] -> tokens fp32 [M, B, N, d] = cat(cls, patches W^T + b) + pos.
+    keep = (keep_idx int32 [M*B, K], slot int32 [M*B, P]) (patch dropout, ops.token_select_draw): the tokens of the kept patches only,
+    [M, B, K + 1, d], through a stored patch matrix of the kept rows; the volume gets no gradient on that path.  The backward reads
+    slot: the caller leaves it as it is until then (ModelCross allocates the pair per forward)."""
 
     @staticmethod
-    def forward(ctx, img, w, b, cls, pos, patch, p=0.0, concat=False):
+    def forward(ctx, img, w, b, cls, pos, patch, p=0.0, concat=False, keep=None):
         Bn, M = img.shape[0], img.shape[1]
         d, pd = w.shape
         w_s = SHADOWS.get(w)
+        ctx.slot = None
+        if keep is not None:
+            return PatchEmbedFn._forward_selected(ctx, img, w_s, b, cls, pos, patch, p, concat, keep)
         # a bf16 volume tensor feeds the GEMM's loaders directly (no [rows, pd] patch matrix in HBM: -2 GB of traffic and
         # -1 GB resident per step at configs[1]); other inputs (fp32 volumes, ModelVIT's concatenated sequence, small or odd
         # geometries) go through the patchify kernel, which also converts
@@ -809,11 +826,50 @@ class PatchEmbedFn(Function):
         return tuple(x.reshape(M, Bn, N, d).unbind(0))
 
     @staticmethod
+    def _forward_selected(ctx, img, w_s, b, cls, pos, patch, p, concat, keep):
+        """Patch dropout: patchify_select -> NT GEMM (+ bias) -> embed_select_fwd -> the embedding dropout.  The fused gather GEMM is not
+        used: its loaders walk whole volumes."""
+        if concat:
+            raise RuntimeError("PatchEmbedFn: keep (patch dropout) is offered for ModelCross's per-modality sequences only, not for concat=True")
+        rec = ATTN_RECORDER.get()
+        if ctx.needs_input_grad[0] or (rec is not None and getattr(rec, "input_grad", False)):
+            raise RuntimeError("PatchEmbedFn: input-volume gradients are not available under patch dropout (keep is set): "
+                               "use eval() mode, which keeps every token, for attributions")
+        keep_idx, slot = keep
+        Bn, M = img.shape[0], img.shape[1]
+        d, pd = w_s.shape
+        K, P = keep_idx.shape[1], slot.shape[1]
+        if P != (img.shape[3] // patch[0]) * (img.shape[4] // patch[1]) * (img.shape[5] // patch[2]) or pos.numel() != (P + 1) * d:
+            raise RuntimeError(f"PatchEmbedFn: keep was drawn for {P} patches per sequence, which is not this volume's patch grid")
+        N = K + 1
+        patches = ops.patchify_select(img.contiguous(), patch, keep_idx).reshape(-1, pd)       # [M*B*N, pd], row 0 of each sequence = 0
+        x = torch.empty(M * Bn * N, d, dtype=torch.float32, device=img.device)
+        ops.gemm(ops.NT, patches, w_s, x, bias=b)
+        ops.embed_select_fwd(x, cls.detach().reshape(d), pos.detach().reshape(P + 1, d), keep_idx)
+        seed = drop_seeds(1)[0] if p > 0.0 else 0
+        if p > 0.0:
+            ops.dropout(x, p, seed, out=x)
+        ctx.meta = (M, Bn, N, d, p, seed, None)
+        ctx.vol = (tuple(img.shape), img.dtype, patch, concat)
+        ctx.slot = slot                       # `keep` arrives as a tuple, so slot is no Function input and cannot go through save_for_backward
+        ctx.save_for_backward(patches, w_s)
+        return tuple(x.reshape(M, Bn, N, d).unbind(0))
+
+    @staticmethod
     def backward(ctx, *dxs):
         M, Bn, N, d, p, seed, fused_patch = ctx.meta
         patches, w_s = ctx.saved_tensors
         dev = patches.device
-        dpos = _zeros(N * d, patches, (N, d))
+        slot = ctx.slot                      # patch dropout: N = K + 1 rows per sequence, dpos keeps all P + 1
+        Np = N if slot is None else slot.shape[1] + 1
+
+        def embed_bwd(g2, seqs, s0):         # dpos / dcls += the token gradients of sequences s0 .. s0 + seqs - 1
+            if slot is None:
+                ops.embed_bwd(g2, dpos, dcls, seqs, N, d)
+            else:
+                ops.embed_select_bwd(g2, slot[s0:s0 + seqs], dpos, dcls, N - 1)
+
+        dpos = _zeros(Np * d, patches, (Np, d))
         dcls = _zeros(d, patches)
         if len(dxs) == 1 or p > 0.0:         # single sequence (ModelVIT), or dropout (its mask is keyed by the index in the stacked tensor)
             dx = dxs[0] if len(dxs) == 1 else torch.stack([_f32c(g) for g in dxs])
@@ -821,13 +877,13 @@ class PatchEmbedFn(Function):
             if p > 0.0:
                 dx2 = ops.dropout(dx2, p, seed)
             dxb = ops.cast_bf16(dx2)
-            ops.embed_bwd(dx2, dpos, dcls, M * Bn, N, d)
+            embed_bwd(dx2, M * Bn, 0)
         else:                                # per-modality gradients: cast each into its slice of ONE bf16 operand, no stacking copy
             dxb = torch.empty(M * Bn * N, d, dtype=torch.bfloat16, device=dev)
             for m, g in enumerate(dxs):
                 g2 = _f32c(g).reshape(Bn * N, d)
                 ops.cast_bf16(g2, dxb[m * Bn * N:(m + 1) * Bn * N])
-                ops.embed_bwd(g2, dpos, dcls, Bn, N, d)      # accumulates into dpos / dcls
+                embed_bwd(g2, Bn, m * Bn)      # accumulates into dpos / dcls
         if fused_patch is not None:
             dW = ops.patch_embed_wgrad(patches, fused_patch, dxb, cls_rows=1, out=_grad_out(w_s, tuple(w_s.shape), dev))     # contraction over the patch rows only
         else:
@@ -842,7 +898,7 @@ class PatchEmbedFn(Function):
             else:
                 dimg = _input_grad(dxb, w_s, shape, patch, concat, dtype)
         _join_wgrads(dev)
-        return dimg, dW, db, dcls.reshape(1, 1, d), dpos.reshape(1, N, d), None, None, None
+        return dimg, dW, db, dcls.reshape(1, 1, d), dpos.reshape(1, Np, d), None, None, None, None
 
 
 _PATCH_GRAD_CHUNK_BYTES = 1 << 30   # the fallback's fp32 patch-gradient matrix per batch chunk (each batch entry of its GEMM stays below 2 GiB)

@@ -617,6 +617,63 @@ def embed_bwd(dx, dpos, dcls, MB, N, d):
     _run("embed_bwd", float(MB) * N * d * 4, "byte", lambda: _lib.load().xvit_embed_bwd(_ptr(dx), _ptr(dpos), _ptr(dcls), MB, N, d, _stream()), "xvit_embed_bwd")
 
 
+def _i32c(t, shape, what):
+    assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"{what}: need a contiguous int32 tensor of shape {tuple(shape)}"
+    return t
+
+
+def token_select_draw(keep_idx, slot, B, shared, seed):
+    """Patch dropout's draw (xvit_token_select_draw): fills keep_idx int32 [S, K] (kept patch indices of every sequence, ascending) and
+    slot int32 [S, P] (position of a kept patch in keep_idx, -1 = dropped); S = M * B, `shared`: one draw per sample for all modalities.
+    Runs on the current stream without a host read-back; the dropout epoch (set_dropout_epoch) is mixed into `seed` at run time."""
+    S, K = keep_idx.shape
+    P = slot.shape[1]
+    _i32c(keep_idx, (S, K), "keep_idx"), _i32c(slot, (S, P), "slot")
+    _run("token_select_draw", float(S) * (P + K) * 4, "byte",
+         lambda: _lib.load().xvit_token_select_draw(_ptr(keep_idx), _ptr(slot), S, int(B), P, K, int(bool(shared)), int(seed), _stream()), "xvit_token_select_draw")
+    return keep_idx, slot
+
+
+def patchify_select(img, patch, keep_idx, out=None):
+    """img [B, M, 1, D, H, W] fp32|bf16 contiguous, keep_idx int32 [M*B, K] -> bf16 [M, B*(K+1), pd]: the rows of
+    patchify(img, patch, pad_cls_row=True) that keep_idx names (a zero row in front of every sequence), only the kept voxels read."""
+    assert img.dim() == 6 and img.shape[2] == 1 and img.is_contiguous()
+    B, M, _, D, H, W = img.shape
+    dp, hp, wp = patch
+    pd = dp * hp * wp
+    K = keep_idx.shape[1]
+    _i32c(keep_idx, (M * B, K), "keep_idx")
+    out = out if out is not None else torch.empty(M, B * (K + 1), pd, dtype=torch.bfloat16, device=img.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, B * (K + 1), pd)
+    _run("patchify_select", M * B * K * pd * (img.element_size() + 2.0), "byte",
+         lambda: _lib.load().xvit_patchify_select(_ptr(img), _dt(img), _ptr(out), _ptr(keep_idx), B, M, D, H, W, dp, hp, wp, K, _stream()), "xvit_patchify_select")
+    return out
+
+
+def embed_select_fwd(x, cls, pos, keep_idx):
+    """In place on x fp32 [S*(K+1), d] (patches W^T + b): + pos[1 + kept patch] on the patch rows, cls + pos[0] on the CLS rows; pos [P+1, d]."""
+    S, K = keep_idx.shape
+    d = x.shape[1]
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] == S * (K + 1)
+    assert cls.dtype == torch.float32 and cls.numel() == d and cls.is_contiguous() and pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[1] == d
+    _i32c(keep_idx, (S, K), "keep_idx")
+    _run("embed_select_fwd", float(x.numel()) * 12, "byte",
+         lambda: _lib.load().xvit_embed_select_fwd(_ptr(x), _ptr(cls), _ptr(pos), _ptr(keep_idx), S, K, d, _stream()), "xvit_embed_select_fwd")
+    return x
+
+
+def embed_select_bwd(dx, slot, dpos, dcls, K):
+    """dpos [P+1, d] and dcls [d] += the token gradient dx fp32 [S*(K+1), d] summed over the sequences in order, each pos row from the
+    sequences that kept its patch (slot int32 [S, P]); fixed order, no atomics."""
+    S, P = slot.shape
+    d = dx.shape[1]
+    assert dx.dtype == torch.float32 and dx.is_contiguous() and dx.shape[0] == S * (K + 1)
+    assert dpos.dtype == torch.float32 and dpos.is_contiguous() and tuple(dpos.shape) == (P + 1, d) and dcls.dtype == torch.float32 and dcls.numel() == d
+    _i32c(slot, (S, P), "slot")
+    _run("embed_select_bwd", float(dx.numel()) * 4, "byte",
+         lambda: _lib.load().xvit_embed_select_bwd(_ptr(dx), _ptr(slot), _ptr(dpos), _ptr(dcls), S, P, int(K), d, _stream()), "xvit_embed_select_bwd")
+
+
 def cast_bf16(src, out=None):
     """fp32 -> bf16 (contiguous)."""
     assert src.dtype == torch.float32 and src.is_contiguous()

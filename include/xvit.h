@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 310 /* 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 311 /* 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -445,6 +445,35 @@ int xvit_volume_stats(const void* src, int src_dtype, int nvol, int64_t nvox, co
 int xvit_cls_row_fwd(const float* cls, const float* pos, float* x, int MB, int N, int d, xvit_stream_t stream);
 /* dpos[n,:] += sum_{mb} dx[mb,n,:];  dcls += sum_{mb} dx[mb,0,:] */
 int xvit_embed_bwd(const float* dx, float* dpos, float* dcls, int MB, int N, int d, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Patch dropout (csrc/token_select.hip): in training, every sequence keeps a random subset of K of its P patch tokens, plus CLS.
+ * S = M * B sequences, sequence s = m * B + b; a patch index is the token t of xvit_patchify, (h * Wn + w) * Dn + d.
+ *
+ * xvit_token_select_draw: patch p of sequence s gets the key hash32(seed', u * P + p), where seed' is the seed mixed with the dropout epoch
+ * (xvit_set_dropout_epoch, read at run time: a captured step draws a new subset at every replay) and u = s, or s mod B with `shared` so
+ * that every modality of a sample keeps the same patches.  Kept are the K patches with the smallest (key, p): equal 32-bit keys go to the
+ * smaller p.  keep_idx [S, K]: the kept patch indices in ascending order; slot [S, P]: the position 0 .. K - 1 of a kept patch in
+ * keep_idx, -1 for a dropped one.  One workgroup per sequence with the keys in LDS, hence P <= XVIT_TOKEN_SELECT_MAX_P; K < 1, K > P and
+ * a longer P are refused.  No host read-back.
+ *
+ * xvit_patchify_select: out [M, B * (K + 1), dp*hp*wp] bf16, the rows of the zero-padded patch matrix of xvit_patchify (one zero row in
+ * front of every sequence) that keep_idx names: row 0 of a sequence is zero, row 1 + j is patch keep_idx[s][j].  Only kept voxels are
+ * read; img [B, M, 1, D, H, W] fp32 or bf16, converted as by xvit_patchify.  8 voxels per thread where wp % 8 == 0 and img and out are
+ * 16-byte aligned; any other patch width or alignment takes the one-voxel-per-thread kernel (same result, slower).
+ *
+ * xvit_embed_select_fwd: x fp32 [S * (K + 1), d] holds patches W^T + b;  x[s, 1 + j, :] += pos[1 + keep_idx[s][j], :] and
+ * x[s, 0, :] = cls + pos[0, :].  pos is the full [P + 1, d] table.  d % 4 == 0.
+ *
+ * xvit_embed_select_bwd: for every pos row 1 + p, acc = 0, then acc += dx[s, 1 + slot[s][p], :] for s = 0 .. S - 1 in this order wherever
+ * slot[s][p] >= 0, then dpos[1 + p, :] += acc (a row no sequence kept is left alone); dpos[0, :] and dcls both += the sum of the CLS rows
+ * dx[s, 0, :] in the same order.  No atomics: bit-reproducible.  dx fp32 [S * (K + 1), d], dpos [P + 1, d], dcls [d]; d % 4 == 0. */
+#define XVIT_TOKEN_SELECT_MAX_P 8192
+int xvit_token_select_draw(int32_t* keep_idx, int32_t* slot, int S, int B, int P, int K, int shared, uint64_t seed, xvit_stream_t stream);
+int xvit_patchify_select(const void* img, int img_dtype, void* out_bf16, const int32_t* keep_idx, int B, int M, int D, int H, int W, int dp, int hp, int wp,
+                         int K, xvit_stream_t stream);
+int xvit_embed_select_fwd(float* x, const float* cls, const float* pos, const int32_t* keep_idx, int S, int K, int d, xvit_stream_t stream);
+int xvit_embed_select_bwd(const float* dx, const int32_t* slot, float* dpos, float* dcls, int S, int P, int K, int d, xvit_stream_t stream);
 
 /* ---- elementwise / reductions --------------------------------------------------------- */
 int xvit_cast_f32_bf16(const float* src, void* dst_bf16, int64_t n, xvit_stream_t stream);
