@@ -55,6 +55,7 @@ class NormConfig(C.Structure):
 STATS_NSTAT = 8                                        # XVIT_STATS_NSTAT
 STATS_WINDOW_LO, STATS_WINDOW_BINS = 32768, 32768      # XVIT_STATS_WINDOW_*: the keys the histogram kernel counts in LDS
 NORM_STATS_ONLY, NORM_ZSCORE, NORM_WINDOW = 0, 1, 2    # XVIT_NORM_*
+MAE_MAX_PD = 8192                                      # XVIT_MAE_MAX_PD: the largest patch (voxels) xvit_mae_loss_fwd holds in LDS
 TOKEN_SELECT_MAX_P = 8192                              # XVIT_TOKEN_SELECT_MAX_P: the longest sequence xvit_token_select_draw ranks in LDS
 
 
@@ -93,6 +94,13 @@ SIGNATURES = {
     "xvit_patchify_select": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "xvit_embed_select_fwd": [vp, vp, vp, vp, i32, i32, i32, vp],
     "xvit_embed_select_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "xvit_token_select_complement": [vp, vp, vp, i32, i32, i32, vp],
+    "xvit_mae_unshuffle_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "xvit_mae_unshuffle_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "xvit_token_rows_gather": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "xvit_token_rows_scatter": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "xvit_mae_loss_fwd": [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "xvit_mae_loss_bwd": [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "xvit_cast_f32_bf16": [vp, vp, i64, vp],
     "xvit_add_cast_f32_bf16": [vp, vp, vp, vp, i64, vp],
     "xvit_rows_combine": [vp, i32, i64, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp],

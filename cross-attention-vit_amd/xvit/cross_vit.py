@@ -374,16 +374,33 @@ class ModelCross(EpochStatsMixin, _Base):
         grp.refresh(force=XF.SHADOWS.force)
         XF.SHADOWS.force = False
 
-    def _draw_token_keep(self, img):
+    def _draw_token_keep(self, img, rate=None, shared=None):
         """Patch dropout: draw, on the current stream and without a host read-back, which K of the P patches each of the M * B sequences
         keeps -> (keep_idx int32 [M*B, K], slot int32 [M*B, P]).  The pair is allocated by every forward, like the activations: under
         capture it lives in the graph's own pool, so a replay redraws into memory that no eager step of another batch can move or free.
-        The seed comes from the dropout seed stream."""
+        The seed comes from the dropout seed stream.  rate / shared: another rate or sharing than the model's own patch dropout
+        (masked pretraining draws its mask here)."""
         B, M, P = img.shape[0], self.num_modalities, self.pos_embedding.shape[1] - 1
-        K = XF.patch_keep_count(P, self.patch_dropout)
+        K = XF.patch_keep_count(P, self.patch_dropout if rate is None else float(rate))
         keep_idx = torch.empty(M * B, K, dtype=torch.int32, device=img.device)
         slot = torch.empty(M * B, P, dtype=torch.int32, device=img.device)
-        return XF.ops.token_select_draw(keep_idx, slot, B, self.patch_dropout_shared, XF.drop_seeds(1)[0])
+        return XF.ops.token_select_draw(keep_idx, slot, B, self.patch_dropout_shared if shared is None else bool(shared), XF.drop_seeds(1)[0])
+
+    def forward_tokens(self, img, keep=None):
+        """The encoder without its heads: the list of M token tensors [B, N, d] behind the last MultiScaleBlock (N = K + 1 under
+        keep = (keep_idx, slot), else P + 1).  Every block returns all its tokens; the flat weight buffer is the caller's business."""
+        if img.shape[1] != self.num_modalities:
+            raise ValueError(f"expected {self.num_modalities} modalities, got {img.shape[1]}")
+        self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
+        x = list(XF.PatchEmbedFn.apply(img, self.patch_to_embedding.weight, self.patch_to_embedding.bias,
+                                       self.cls_token, self.pos_embedding, self.patch_size, _p(self, self.dropout), False, keep))
+        for k, blk in enumerate(self.transformer):
+            last = k == len(self.transformer) - 1
+            observed = bool(blk._forward_hooks) or bool(self.transformer._forward_hooks)
+            nxt = None if last else self.transformer[k + 1]
+            sole = not observed and (last or all(len(b) > 0 for b in nxt.blocks))      # as in forward: one consumer per output
+            x = blk(x, cls_only=False, exclusive=sole)
+        return x
 
     def forward(self, img, labels):
         if self.pos_embedding.is_cuda and os.environ.get("XVIT_FLAT_WEIGHTS", "1") != "0":

@@ -901,7 +901,74 @@ class PatchEmbedFn(Function):
         return dimg, dW, db, dcls.reshape(1, 1, d), dpos.reshape(1, Np, d), None, None, None, None
 
 
-_PATCH_GRAD_CHUNK_BYTES = 1 << 30   # the fallback's fp32 patch-gradient matrix per batch chunk (each batch entry of its GEMM stays below 2 GiB)
+# ------------------------------------------------------------------------------------------
+# masked-volume pretraining (xvit/mae.py; csrc/mae.hip): tokens back on the full grid, the dropped rows, the loss
+# ------------------------------------------------------------------------------------------
+
+
+class MaeUnshuffleFn(Function):
+    """(xe fp32 [S, K+1, dd], mask_token [1, 1, dd], dpos [1, P+1, dd], dmod [M, 1, dd], keep = (keep_idx, slot)) -> y fp32 [S, P+1, dd]:
+    y[s, 1 + p] = the encoder token of patch p where sequence s kept it, else the mask token, + dpos[1 + p] + dmod[m]; row 0 is the CLS row.
+    The backward reads keep only: nothing of the forward is saved."""
+
+    @staticmethod
+    def forward(ctx, xe, mask_token, dpos, dmod, keep):
+        keep_idx, slot = keep
+        M, dd = dmod.shape[0], xe.shape[-1]
+        ctx.keep, ctx.M = keep, M
+        return ops.mae_unshuffle_fwd(_f32c(xe), mask_token.detach().reshape(dd), dpos.detach().reshape(-1, dd), dmod.detach().reshape(M, dd), slot)
+
+    @staticmethod
+    def backward(ctx, dy):
+        keep_idx, slot = ctx.keep
+        M = ctx.M
+        dxe, dmask, ddpos_m = ops.mae_unshuffle_bwd(_f32c(dy), keep_idx, slot, M)
+        dd = dxe.shape[-1]
+        ddpos = ddpos_m[0]
+        for m in range(1, M):                    # m ascending
+            ddpos = ddpos + ddpos_m[m]
+        ddmod = torch.stack([ops.colsum(ddpos_m[m]) for m in range(M)])
+        return dxe, dmask.reshape(1, 1, dd), ddpos.reshape(1, -1, dd), ddmod.reshape(M, 1, dd), None
+
+
+class TokenRowsGatherFn(Function):
+    """(x fp32 [S, P+1, dd], drop = (drop_idx [S, Rm], mslot [S, P])) -> fp32 [S*Rm, dd], the rows of the dropped patches in drop_idx order; the
+    backward writes every row of dx once (zeros for the CLS row and the kept patches)."""
+
+    @staticmethod
+    def forward(ctx, x, drop):
+        ctx.drop = drop
+        return ops.token_rows_gather(_f32c(x), drop[0])
+
+    @staticmethod
+    def backward(ctx, dg):
+        drop_idx, mslot = ctx.drop
+        return ops.token_rows_scatter(_f32c(dg), mslot, drop_idx.shape[1]), None
+
+
+class MaskedPatchLossFn(Function):
+    """(pred [S*Rm, pd] bf16 | fp32, img [B, M, 1, D, H, W], drop_idx [S, Rm], patch, norm_pix) -> (loss fp32 scalar, loss_seq [S], stats [S*Rm, 2]):
+    the mean squared error of the predicted dropped patches against the volume's own (per-patch normalised) voxels.  loss_seq and stats carry
+    no gradient.  The backward recomputes the target from the volume and takes the upstream scalar from device memory."""
+
+    @staticmethod
+    def forward(ctx, pred, img, drop_idx, patch, norm_pix=True):
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError("MaskedPatchLossFn: the volume is the target and gets no gradient")
+        pred2 = pred if pred.is_contiguous() else pred.contiguous()
+        loss, loss_seq, _, stats = ops.mae_loss_fwd(pred2, drop_idx, img, patch, norm_pix)
+        ctx.save_for_backward(pred2, img, drop_idx, stats)
+        ctx.patch = tuple(patch)
+        ctx.mark_non_differentiable(loss_seq, stats)
+        return loss.reshape(()), loss_seq, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dseq, _dstats):
+        pred, img, drop_idx, stats = ctx.saved_tensors
+        return ops.mae_loss_bwd(pred, drop_idx, img, ctx.patch, stats, _f32c(dloss).reshape(1)), None, None, None, None
+
+
+_PATCH_GRAD_CHUNK_BYTES = 1 << 30  # the fallback's fp32 patch-gradient matrix per batch chunk (each batch entry of its GEMM stays below 2 GiB)
 
 
 def _input_grad(dxb, w_s, shape, patch, concat, dtype):

@@ -43,9 +43,10 @@ from . import functional as XF
 
 
 def _has_dropout(model) -> bool:
-    """Any active rate on the path (the module facades keep their rates in nn.Dropout children, like the reference), patch dropout included:
-    its draw reads the same device-side epoch, so every replay keeps a new subset of the patch tokens."""
-    return any((isinstance(m, torch.nn.Dropout) and m.p > 0) or getattr(m, "patch_dropout", 0.0) > 0 for m in model.modules())
+    """Any active rate on the path (the module facades keep their rates in nn.Dropout children, like the reference), patch dropout and the
+    mask ratio of masked pretraining included: their draw reads the same device-side epoch, so every replay keeps a new subset of the patch
+    tokens."""
+    return any((isinstance(m, torch.nn.Dropout) and m.p > 0) or getattr(m, "patch_dropout", 0.0) > 0 or getattr(m, "mask_ratio", 0.0) > 0 for m in model.modules())
 
 
 class GraphedStep:

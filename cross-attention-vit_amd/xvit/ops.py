@@ -674,6 +674,122 @@ def embed_select_bwd(dx, slot, dpos, dcls, K):
          lambda: _lib.load().xvit_embed_select_bwd(_ptr(dx), _ptr(slot), _ptr(dpos), _ptr(dcls), S, P, int(K), d, _stream()), "xvit_embed_select_bwd")
 
 
+def token_select_complement(slot, K, drop_idx=None, mslot=None):
+    """The dropped side of a draw (xvit_token_select_complement): slot int32 [S, P] with K kept entries per row -> drop_idx int32 [S, P - K]
+    (dropped patch indices, ascending) and mslot int32 [S, P] (position of a dropped patch in drop_idx, -1 = kept)."""
+    S, P = slot.shape
+    K = int(K)
+    _i32c(slot, (S, P), "slot")
+    drop_idx = drop_idx if drop_idx is not None else torch.empty(S, max(P - K, 0), dtype=torch.int32, device=slot.device)
+    mslot = mslot if mslot is not None else torch.empty(S, P, dtype=torch.int32, device=slot.device)
+    _i32c(drop_idx, (S, P - K), "drop_idx"), _i32c(mslot, (S, P), "mslot")
+    _run("token_select_complement", float(S) * (3 * P - K) * 4, "byte",
+         lambda: _lib.load().xvit_token_select_complement(_ptr(slot), _ptr(drop_idx), _ptr(mslot), S, P, K, _stream()), "xvit_token_select_complement")
+    return drop_idx, mslot
+
+
+def _f32v(t, shape, what):
+    assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"{what}: need a contiguous fp32 tensor of shape {tuple(shape)}"
+    return t
+
+
+def mae_unshuffle_fwd(xe, mask_token, dpos, dmod, slot, out=None):
+    """xe fp32 [S, K+1, dd], mask_token [dd], dpos [P+1, dd], dmod [M, dd], slot int32 [S, P] -> y fp32 [S, P+1, dd]: the encoder tokens back
+    on the full grid, the mask token in the dropped places, + decoder position and modality embeddings (xvit_mae_unshuffle_fwd)."""
+    S, K1, dd = xe.shape
+    P, M = slot.shape[1], dmod.shape[0]
+    assert S % M == 0, f"mae_unshuffle_fwd: {S} sequences do not divide into {M} modalities"
+    _f32v(xe, (S, K1, dd), "xe"), _f32v(mask_token, (dd,), "mask_token"), _f32v(dpos, (P + 1, dd), "dpos"), _f32v(dmod, (M, dd), "dmod"), _i32c(slot, (S, P), "slot")
+    y = out if out is not None else torch.empty(S, P + 1, dd, dtype=torch.float32, device=xe.device)
+    _f32v(y, (S, P + 1, dd), "y")
+    _run("mae_unshuffle_fwd", float(S) * (P + K1) * dd * 4, "byte",
+         lambda: _lib.load().xvit_mae_unshuffle_fwd(_ptr(xe), _ptr(mask_token), _ptr(dpos), _ptr(dmod), _ptr(slot), _ptr(y), S, S // M, P, K1 - 1, dd, _stream()),
+         "xvit_mae_unshuffle_fwd")
+    return y
+
+
+def mae_unshuffle_bwd(dy, keep_idx, slot, M, out=None):
+    """dy fp32 [S, P+1, dd] -> (dxe [S, K+1, dd], dmask_token [dd], ddpos_m [M, P+1, dd]) in the fixed orders of xvit_mae_unshuffle_bwd.
+    out: (dxe, dmask_token, ddpos_m, scratch [S, dd]) to write into."""
+    S, P1, dd = dy.shape
+    K = keep_idx.shape[1]
+    _f32v(dy, (S, P1, dd), "dy"), _i32c(keep_idx, (S, K), "keep_idx"), _i32c(slot, (S, P1 - 1), "slot")
+    assert S % M == 0
+    if out is None:
+        out = tuple(torch.empty(*shape, dtype=torch.float32, device=dy.device) for shape in ((S, K + 1, dd), (dd,), (M, P1, dd), (S, dd)))
+    dxe, dmask, ddpos_m, part = out
+    _f32v(dxe, (S, K + 1, dd), "dxe"), _f32v(dmask, (dd,), "dmask_token"), _f32v(ddpos_m, (M, P1, dd), "ddpos_m"), _f32v(part, (S, dd), "scratch")
+    _run("mae_unshuffle_bwd", float(S) * (2 * P1 + K + 1) * dd * 4, "byte",
+         lambda: _lib.load().xvit_mae_unshuffle_bwd(_ptr(dy), _ptr(keep_idx), _ptr(slot), _ptr(dxe), _ptr(dmask), _ptr(ddpos_m), _ptr(part), S, S // M, P1 - 1, K, dd, _stream()),
+         "xvit_mae_unshuffle_bwd")
+    return dxe, dmask, ddpos_m
+
+
+def token_rows_gather(x, drop_idx, out=None):
+    """x fp32 [S, P+1, dd], drop_idx int32 [S, Rm] -> g fp32 [S*Rm, dd], g[s Rm + j] = x[s, 1 + drop_idx[s][j]] (xvit_token_rows_gather)."""
+    S, P1, dd = x.shape
+    Rm = drop_idx.shape[1]
+    _f32v(x, (S, P1, dd), "x"), _i32c(drop_idx, (S, Rm), "drop_idx")
+    g = out if out is not None else torch.empty(S * Rm, dd, dtype=torch.float32, device=x.device)
+    _f32v(g, (S * Rm, dd), "g")
+    _run("token_rows_gather", float(S) * Rm * dd * 8, "byte",
+         lambda: _lib.load().xvit_token_rows_gather(_ptr(x), _ptr(drop_idx), _ptr(g), S, P1 - 1, Rm, dd, _stream()), "xvit_token_rows_gather")
+    return g
+
+
+def token_rows_scatter(dg, mslot, Rm, out=None):
+    """The backward of token_rows_gather: dg fp32 [S*Rm, dd], mslot int32 [S, P] -> dx fp32 [S, P+1, dd], every row written once (zeros for the CLS
+    row and the kept patches)."""
+    S, P = mslot.shape
+    dd = dg.shape[1]
+    _f32v(dg, (S * Rm, dd), "dg"), _i32c(mslot, (S, P), "mslot")
+    dx = out if out is not None else torch.empty(S, P + 1, dd, dtype=torch.float32, device=dg.device)
+    _f32v(dx, (S, P + 1, dd), "dx")
+    _run("token_rows_scatter", float(S) * (P + 1 + Rm) * dd * 4, "byte",
+         lambda: _lib.load().xvit_token_rows_scatter(_ptr(dg), _ptr(mslot), _ptr(dx), S, P, int(Rm), dd, _stream()), "xvit_token_rows_scatter")
+    return dx
+
+
+def _mae_loss_geom(pred, drop_idx, img, patch):
+    assert img.dim() == 6 and img.shape[2] == 1 and img.is_contiguous(), "mae loss: need a contiguous volume tensor [B, M, 1, D, H, W]"
+    B, M, _, D, H, W = img.shape
+    dp, hp, wp = patch
+    Rm = drop_idx.shape[1]
+    _i32c(drop_idx, (M * B, Rm), "drop_idx")
+    assert pred.dim() == 2 and pred.is_contiguous() and tuple(pred.shape) == (M * B * Rm, dp * hp * wp), \
+        f"mae loss: pred must be a contiguous [{M * B * Rm}, {dp * hp * wp}] tensor, got {tuple(pred.shape)}"
+    return (B, M, D, H, W, dp, hp, wp, Rm)
+
+
+def mae_loss_fwd(pred, drop_idx, img, patch, norm_pix=True, out=None):
+    """pred [S*Rm, pd] bf16|fp32 against the dropped patches of img [B, M, 1, D, H, W] bf16|fp32 (xvit_mae_loss_fwd; the target matrix is never
+    stored) -> (loss fp32 [1], loss_seq fp32 [S], row_loss fp32 [S*Rm], stats fp32 [S*Rm, 2] = (mean, rstd)); out: that tuple to write into."""
+    geom = _mae_loss_geom(pred, drop_idx, img, patch)
+    B, M, Rm = geom[0], geom[1], geom[8]
+    rows, dev = M * B * Rm, pred.device
+    if out is None:
+        out = tuple(torch.empty(*shape, dtype=torch.float32, device=dev) for shape in ((1,), (M * B,), (rows,), (rows, 2)))
+    loss, loss_seq, row_loss, stats = out
+    _f32v(loss, (1,), "loss"), _f32v(loss_seq, (M * B,), "loss_seq"), _f32v(row_loss, (rows,), "row_loss"), _f32v(stats, (rows, 2), "stats")
+    _run("mae_loss_fwd", float(pred.numel()) * (img.element_size() + pred.element_size()), "byte",
+         lambda: _lib.load().xvit_mae_loss_fwd(_ptr(pred), _dt(pred), _ptr(drop_idx), _ptr(img), _dt(img), int(bool(norm_pix)), _ptr(stats), _ptr(row_loss),
+                                               _ptr(loss_seq), _ptr(loss), *geom, _stream()), "xvit_mae_loss_fwd")
+    return loss, loss_seq, row_loss, stats
+
+
+def mae_loss_bwd(pred, drop_idx, img, patch, stats, g, out=None):
+    """dpred = g 2 (pred - target) / (pd S Rm) in pred's dtype (xvit_mae_loss_bwd); g: one fp32 element on the device (no host read-back)."""
+    geom = _mae_loss_geom(pred, drop_idx, img, patch)
+    _f32v(stats, (pred.shape[0], 2), "stats")
+    assert g.dtype == torch.float32 and g.numel() == 1
+    dpred = out if out is not None else torch.empty_like(pred)
+    assert dpred.dtype == pred.dtype and dpred.shape == pred.shape and dpred.is_contiguous()
+    _run("mae_loss_bwd", float(pred.numel()) * (img.element_size() + 2 * pred.element_size()), "byte",
+         lambda: _lib.load().xvit_mae_loss_bwd(_ptr(pred), _dt(pred), _ptr(drop_idx), _ptr(img), _dt(img), _ptr(stats), _ptr(g), _ptr(dpred), *geom, _stream()),
+         "xvit_mae_loss_bwd")
+    return dpred
+
+
 def cast_bf16(src, out=None):
     """fp32 -> bf16 (contiguous)."""
     assert src.dtype == torch.float32 and src.is_contiguous()

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 311 /* 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 312 /* 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -474,6 +474,65 @@ int xvit_patchify_select(const void* img, int img_dtype, void* out_bf16, const i
                          int K, xvit_stream_t stream);
 int xvit_embed_select_fwd(float* x, const float* cls, const float* pos, const int32_t* keep_idx, int S, int K, int d, xvit_stream_t stream);
 int xvit_embed_select_bwd(const float* dx, const int32_t* slot, float* dpos, float* dcls, int S, int P, int K, int d, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Masked-volume pretraining (csrc/mae.hip; MAE, He et al. 2022) on top of patch dropout: the encoder runs on the K kept patches of every
+ * sequence, a decoder on the full grid with a mask token in the P - K = Rm dropped places, and the prediction of the dropped patches is
+ * scored against the volume.  S = M * B sequences, s = m * B + b, patch indices as above.  No entry point uses atomics; every sum has the
+ * one order written here, so results are the same bits at every run.  Nothing is read back to the host.
+ *
+ * xvit_token_select_complement: from slot [S, P] (xvit_token_select_draw) -> drop_idx int32 [S, Rm], the dropped patch indices of every
+ * sequence in ascending order, and mslot int32 [S, P], the position of a dropped patch inside drop_idx, -1 for a kept one.  One workgroup
+ * per sequence (ballot prefix per wave, wave totals through LDS), P <= XVIT_TOKEN_SELECT_MAX_P, 1 <= K < P.  A slot row that does not have
+ * exactly K kept entries is the caller's error; nothing outside drop_idx and mslot is written then: with more dropped entries than Rm the
+ * first Rm (ascending) are listed and the others read -1 (kept) in mslot, with fewer the tail of drop_idx is -1.  The kernels below read a
+ * row index outside its range as "no row" (zeros, or the mask token), never out of bounds.
+ *
+ * xvit_mae_unshuffle_fwd: xe fp32 [S, K + 1, dd] (CLS row first, then the kept tokens in keep_idx order), mask_token [dd], dpos [P + 1, dd],
+ * dmod [M, dd] -> y fp32 [S, P + 1, dd]:
+ *     y[s, 0]     = (xe[s, 0] + dpos[0]) + dmod[m]
+ *     y[s, 1 + p] = ((slot[s][p] >= 0 ? xe[s, 1 + slot[s][p]] : mask_token) + dpos[1 + p]) + dmod[m]
+ * with exactly this association: two fp32 additions per element.  16-byte accesses: dd % 4 == 0, 16-byte aligned pointers.
+ *
+ * xvit_mae_unshuffle_bwd: from dy fp32 [S, P + 1, dd]
+ *     dxe [S, K + 1, dd]      dxe[s, 0] = dy[s, 0], dxe[s, 1 + j] = dy[s, 1 + keep_idx[s][j]]: every row written exactly once
+ *     ddpos_m [M, P + 1, dd]  ddpos_m[m, n] = dy[(m, 0), n] + dy[(m, 1), n] + ... (b ascending, from 0)
+ *     dmask_part [S, dd]      dmask_part[s] = the sum of dy[s, 1 + p] over the dropped p, ascending, from 0   (caller-owned scratch)
+ *     dmask_token [dd]        dmask_part[0] + dmask_part[1] + ... (s ascending, from 0): s ascending, inside a sequence p ascending
+ * One thread per (row, 4 features) walks its sequences in order.  The host finishes ddpos = sum over m ascending of ddpos_m[m] and
+ * ddmod[m] = xvit_colsum(ddpos_m[m]).
+ *
+ * xvit_token_rows_gather: g[s * Rm + j, :] = x[s, 1 + drop_idx[s][j], :]; x fp32 [S, P + 1, dd], g fp32 [S * Rm, dd].
+ * xvit_token_rows_scatter (its backward): dx[s, 1 + p, :] = mslot[s][p] >= 0 ? dg[s * Rm + mslot[s][p], :] : 0 and dx[s, 0, :] = 0; every
+ * row of dx is written once: no memset, no accumulation.  dd % 4 == 0, 16-byte aligned pointers, 1 <= Rm < P.
+ *
+ * xvit_mae_loss_fwd: pred [S * Rm, pd] (bf16 | fp32), pd = dp * hp * wp; row r = s * Rm + j predicts patch drop_idx[s][j] of volume (b, m) of
+ * img [B, M, 1, D, H, W] (bf16 | fp32), in the token and feature order of xvit_patchify (t = (h Wn + w) Dn + d, f = (p1 hp + p2) wp + p3).
+ * The target is never stored: one workgroup per row holds the patch's voxels in LDS (pd <= XVIT_MAE_MAX_PD).  With norm_pix the target is
+ * (v - mean) * rstd, mean = sum v / pd, rstd = 1 / sqrt(var + 1e-6), var = sum (v - mean)^2 / (pd - 1) (unbiased, two passes: mean first,
+ * then the centred squares); without, the target is v and stats = (0, 1).  Outputs: stats fp32 [S * Rm, 2] = (mean, rstd);
+ * row_loss fp32 [S * Rm] = sum_f (pred - target)^2 / pd; then one workgroup forms loss_seq [S], loss_seq[s] = (row_loss[s Rm] + ... +
+ * row_loss[s Rm + Rm - 1], ascending from 0) / Rm, and loss [1] = (loss_seq[0] + ... + loss_seq[S - 1], ascending from 0) / S, the mean
+ * over all S * Rm rows.  Sums inside a row: thread-strided partial sums, then the lanes and waves in a fixed order.  8 voxels per access
+ * where wp % 8 == 0 and img and pred are 16-byte aligned, else one voxel per access (same switch as xvit_patchify_select).
+ * A drop_idx entry outside the grid scores 0 with stats (0, 1).
+ *
+ * xvit_mae_loss_bwd: dpred[r, f] = g * 2 (pred[r, f] - target[r, f]) / (pd * S * Rm) in pred's dtype; g is the upstream scalar, read from
+ * DEVICE memory; the target is recomputed from the volume and stats.
+ * Argument errors (nothing launched): null or misaligned pointers, bad sizes or dtypes, Rm outside 1 .. P - 1, pd > XVIT_MAE_MAX_PD,
+ * norm_pix with pd < 2. */
+#define XVIT_MAE_MAX_PD 8192
+int xvit_token_select_complement(const int32_t* slot, int32_t* drop_idx, int32_t* mslot, int S, int P, int K, xvit_stream_t stream);
+int xvit_mae_unshuffle_fwd(const float* xe, const float* mask_token, const float* dpos, const float* dmod, const int32_t* slot, float* y, int S, int B, int P,
+                           int K, int dd, xvit_stream_t stream);
+int xvit_mae_unshuffle_bwd(const float* dy, const int32_t* keep_idx, const int32_t* slot, float* dxe, float* dmask_token, float* ddpos_m, float* dmask_part,
+                           int S, int B, int P, int K, int dd, xvit_stream_t stream);
+int xvit_token_rows_gather(const float* x, const int32_t* drop_idx, float* g, int S, int P, int Rm, int dd, xvit_stream_t stream);
+int xvit_token_rows_scatter(const float* dg, const int32_t* mslot, float* dx, int S, int P, int Rm, int dd, xvit_stream_t stream);
+int xvit_mae_loss_fwd(const void* pred, int pred_dtype, const int32_t* drop_idx, const void* img, int img_dtype, int norm_pix, float* stats, float* row_loss,
+                      float* loss_seq, float* loss, int B, int M, int D, int H, int W, int dp, int hp, int wp, int Rm, xvit_stream_t stream);
+int xvit_mae_loss_bwd(const void* pred, int pred_dtype, const int32_t* drop_idx, const void* img, int img_dtype, const float* stats, const float* g,
+                      void* dpred, int B, int M, int D, int H, int W, int dp, int hp, int wp, int Rm, xvit_stream_t stream);
 
 /* ---- elementwise / reductions --------------------------------------------------------- */
 int xvit_cast_f32_bf16(const float* src, void* dst_bf16, int64_t n, xvit_stream_t stream);
