@@ -9,6 +9,7 @@ own nn.Module signatures (vsahni3/cross-attention-ViT: model_cross.py, model.py)
     xvit.interpret.input_attributions(model, img)    # voxel attributions: gradient, grad x input, integrated gradients (eval mode)
     xvit.augment.VolumeAugment(img_size)(raw)        # device-side pad / crop + random affine + intensity augmentation of raw volumes
     xvit.MaskedVolumeModel(config)                   # masked-volume (MAE) pretraining of a ModelCross encoder
+    config.mixup_alpha / config.cutmix_alpha         # Mixup / CutMix with a soft-target loss in ModelCross.train() (fine-tuning)
 """
 from . import _lib  # noqa: F401
 from .functional import invalidate_shadows  # noqa: F401

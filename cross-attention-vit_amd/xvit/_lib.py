@@ -59,6 +59,17 @@ MAE_MAX_PD = 8192                                      # XVIT_MAE_MAX_PD: the la
 TOKEN_SELECT_MAX_P = 8192                              # XVIT_TOKEN_SELECT_MAX_P: the longest sequence xvit_token_select_draw ranks in LDS
 
 
+class MixConfig(C.Structure):
+    """struct xvit_mix_config (include/xvit.h)."""
+    _fields_ = [("mixup_alpha", f32), ("cutmix_alpha", f32), ("prob", f32), ("switch_prob", f32), ("per_sample", i32)]
+
+
+MIX_NPARAM = 16                                        # XVIT_MIX_NPARAM: floats per record of the Mixup / CutMix table
+MIX_MODE, MIX_PARTNER, MIX_LAM, MIX_OML, MIX_BOX, MIX_LAM0 = 0, 1, 2, 3, 4, 10    # XVIT_MIX_*: the record's fields
+MIX_MODE_MIXUP, MIX_MODE_CUTMIX = 1, 2                 # XVIT_MIX_MODE_*
+MIX_DRAW_STRIDE = 256                                  # XVIT_MIX_DRAW_STRIDE: hash indices per decision block of xvit_mix_draw
+
+
 # name -> argtypes; every function returns int except the two noted below
 SIGNATURES = {
     "xvit_gemm": [C.POINTER(GemmArgs), vp],
@@ -109,6 +120,9 @@ SIGNATURES = {
     "xvit_cu_trace": [vp, i32, i32, vp],
     "xvit_binary_metrics_step": [vp, i64, vp, i32, i32, vp, vp],
     "xvit_mean_ce": [vp, vp, f32, vp, vp, vp, i32, i32, i32, vp],
+    "xvit_mix_draw": [C.POINTER(MixConfig), vp, i32, i32, i32, i32, u64, vp],
+    "xvit_mix_apply": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i64, i64, vp],
+    "xvit_mean_ce_mix": [vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp],
     "xvit_resize_pad_crop_i16": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_augment_draw": [C.POINTER(AugmentConfig), vp, i32, i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp],
     "xvit_augment_apply": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],

@@ -359,6 +359,19 @@ class ModelCross(EpochStatsMixin, _Base):
         # int32 [M, B, K]: the patch indices the last forward kept (None: it kept them all).  The tensor a capture leaves here is the
         # graph's own and follows its replays; any later forward call replaces the attribute, not that tensor
         self.last_token_keep = None
+        # Mixup / CutMix (not in the reference; off unless the config carries a positive alpha): in train() every sample's volumes and label
+        # are mixed with a partner's, the loss takes the two-label target; eval() mixes nothing
+        self.mixup_alpha, self.cutmix_alpha = float(getattr(config, "mixup_alpha", 0.0)), float(getattr(config, "cutmix_alpha", 0.0))
+        self.mix_prob, self.mix_switch_prob = float(getattr(config, "mix_prob", 1.0)), float(getattr(config, "mix_switch_prob", 0.5))
+        self.mix_per_sample = bool(getattr(config, "mix_per_sample", False))
+        for k in ("mixup_alpha", "cutmix_alpha"):
+            if not (0.0 <= getattr(self, k) < float("inf")):
+                raise ValueError(f"{k} must be finite and >= 0, got {getattr(self, k)}")
+        for k in ("mix_prob", "mix_switch_prob"):
+            if not 0.0 <= getattr(self, k) <= 1.0:
+                raise ValueError(f"{k} must be in [0, 1], got {getattr(self, k)}")
+        # fp32 [B, 16]: the records of the last training forward (None: it mixed nothing); a capture's tensor is the graph's own, as above
+        self.last_mix = None
         self.initialize_model()
 
     def _sync_flat_weights(self):
@@ -386,9 +399,19 @@ class ModelCross(EpochStatsMixin, _Base):
         slot = torch.empty(M * B, P, dtype=torch.int32, device=img.device)
         return XF.ops.token_select_draw(keep_idx, slot, B, self.patch_dropout_shared if shared is None else bool(shared), XF.drop_seeds(1)[0])
 
+    def _draw_mix(self, img):
+        """Mixup / CutMix: draw, on the current stream and without a host read-back, one record per sample -> table fp32 [B, 16]
+        (include/xvit.h).  Allocated by every forward, like keep_idx: under capture it lives in the graph's own pool and every replay
+        redraws into it.  The seed comes from the dropout seed stream."""
+        from ._lib import MIX_NPARAM, MixConfig
+        table = torch.empty(img.shape[0], MIX_NPARAM, dtype=torch.float32, device=img.device)
+        cfg = MixConfig(self.mixup_alpha, self.cutmix_alpha, self.mix_prob, self.mix_switch_prob, int(self.mix_per_sample))
+        return XF.ops.mix_draw(cfg, table, tuple(img.shape[3:]), XF.drop_seeds(1)[0])
+
     def forward_tokens(self, img, keep=None):
         """The encoder without its heads: the list of M token tensors [B, N, d] behind the last MultiScaleBlock (N = K + 1 under
-        keep = (keep_idx, slot), else P + 1).  Every block returns all its tokens; the flat weight buffer is the caller's business."""
+        keep = (keep_idx, slot), else P + 1).  Every block returns all its tokens; the flat weight buffer is the caller's business.
+        Mixup / CutMix never applies here: masked pretraining scores the volume itself."""
         if img.shape[1] != self.num_modalities:
             raise ValueError(f"expected {self.num_modalities} modalities, got {img.shape[1]}")
         self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
@@ -411,6 +434,10 @@ class ModelCross(EpochStatsMixin, _Base):
             XF.arena_begin(img.device)                   # the backward's small zeroed vectors: one fill per step (functional._zeros)
         keep = self._draw_token_keep(img) if self.training and self.patch_dropout > 0.0 else None
         self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
+        mix = self._draw_mix(img) if self.training and (self.mixup_alpha > 0.0 or self.cutmix_alpha > 0.0) else None   # its seed: after the token draw's
+        self.last_mix = mix
+        if mix is not None:
+            img = XF.mix_volumes(img, mix)
         tokens = XF.PatchEmbedFn.apply(img, self.patch_to_embedding.weight, self.patch_to_embedding.bias,
                                        self.cls_token, self.pos_embedding, self.patch_size, _p(self, self.dropout), False, keep)
         x = list(tokens)
@@ -429,6 +456,8 @@ class ModelCross(EpochStatsMixin, _Base):
             per_mod = self.transformer[-1]._parallel(heads, list(x), kind="fusion")
         else:
             per_mod = [h() for h in heads]
+        if mix is not None:
+            return XF.MeanMixCrossEntropyFn.apply(torch.stack(per_mod), labels, mix, self.label_smoothing)
         logits, loss = XF.MeanCrossEntropyFn.apply(torch.stack(per_mod), labels, self.label_smoothing)
         return logits, loss
 

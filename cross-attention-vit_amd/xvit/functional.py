@@ -1068,6 +1068,37 @@ class MeanCrossEntropyFn(Function):
         return g, None, None
 
 
+class MeanMixCrossEntropyFn(Function):
+    """MeanCrossEntropyFn under Mixup / CutMix: (logits_m [M,B,C], labels, table fp32 [B, 16]) -> (mean logits [B,C], CE loss against
+    the soft target lam smooth(y_b) + oml smooth(y_partner[b]) of the records (ops.mix_draw, or hand-made))."""
+
+    @staticmethod
+    def forward(ctx, logits_m, labels, table, smoothing):
+        logits, loss, dl = ops.mean_ce_mix(_f32c(logits_m), labels.to(torch.int64).contiguous(), table, float(smoothing))
+        ctx.save_for_backward(dl)
+        ctx.M = logits_m.shape[0]
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss):
+        (dl,) = ctx.saved_tensors
+        g = dl * dloss
+        if dlogits is not None:
+            g = g + (dlogits / ctx.M).unsqueeze(0)
+        return g, None, None, None
+
+
+def mix_volumes(img, table):
+    """Mixup / CutMix on the volumes: img [B, M, 1, D, H, W] mixed through the records table fp32 [B, 16] -> a new tensor
+    (ops.mix_apply).  The mix has no backward: a volume that requires grad is refused."""
+    if img.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("mix_volumes: input-volume gradients are not available under mixing (Mixup / CutMix): "
+                           "use eval() mode, which mixes nothing, for attributions")
+    if img.dim() == 6 and tuple(img.stride()[3:]) != (img.shape[4] * img.shape[5], img.shape[5], 1):
+        img = img.contiguous()               # the kernel takes any batch / modality stride, but whole volumes
+    return ops.mix_apply(img, table)
+
+
 # ------------------------------------------------------------------------------------------
 # fine-grained Functions for the stand-alone module facades (PreNorm / Attention / FeedForward /
 # CrossAttention / Mlp / MultiHeadAttention used outside their parent block)

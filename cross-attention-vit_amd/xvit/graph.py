@@ -45,8 +45,9 @@ from . import functional as XF
 def _has_dropout(model) -> bool:
     """Any active rate on the path (the module facades keep their rates in nn.Dropout children, like the reference), patch dropout and the
     mask ratio of masked pretraining included: their draw reads the same device-side epoch, so every replay keeps a new subset of the patch
-    tokens."""
-    return any((isinstance(m, torch.nn.Dropout) and m.p > 0) or getattr(m, "patch_dropout", 0.0) > 0 or getattr(m, "mask_ratio", 0.0) > 0 for m in model.modules())
+    tokens.  A positive Mixup / CutMix alpha counts too: every replay draws a new record table."""
+    return any((isinstance(m, torch.nn.Dropout) and m.p > 0) or getattr(m, "patch_dropout", 0.0) > 0 or getattr(m, "mask_ratio", 0.0) > 0
+               or getattr(m, "mixup_alpha", 0.0) > 0 or getattr(m, "cutmix_alpha", 0.0) > 0 for m in model.modules())
 
 
 class GraphedStep:

@@ -898,6 +898,56 @@ def mean_ce(logits_m, labels, smoothing):
     return logits, loss, dl
 
 
+def _mix_table(table, B, what):
+    if not (table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (B, _lib.MIX_NPARAM)):
+        raise RuntimeError(f"{what}: the record table is a contiguous fp32 tensor of shape ({B}, {_lib.MIX_NPARAM}), got {table.dtype} {tuple(table.shape)}")
+    return table
+
+
+def mix_draw(config, table, vol_size, seed):
+    """xvit_mix_draw (include/xvit.h): fill table fp32 [B, 16] with one Mixup / CutMix record per sample drawn from `config`
+    (_lib.MixConfig) and `seed`; vol_size = (D, H, W) of the volumes the CutMix boxes are cut from.  Runs on the current stream without a
+    host read-back; the dropout epoch (set_dropout_epoch) is mixed into `seed` at run time."""
+    B = table.shape[0]
+    _mix_table(table, B, "mix_draw")
+    D, H, W = vol_size
+    _run("mix_draw", table.numel() * 4.0, "byte",
+         lambda: _lib.load().xvit_mix_draw(C.byref(config), _ptr(table), B, int(D), int(H), int(W), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "xvit_mix_draw")
+    return table
+
+
+def mix_apply(img, table, out=None):
+    """xvit_mix_apply (include/xvit.h): img [B, M, 1, D, H, W] (bf16 or fp32; every volume contiguous, batch and modality strides free)
+    mixed through table fp32 [B, 16] -> a new contiguous tensor of img's shape and dtype.  Out of place: `out` may not overlap img."""
+    assert img.dim() == 6 and img.shape[2] == 1, f"mix_apply: need [B, M, 1, D, H, W], got {tuple(img.shape)}"
+    B, M, _, D, H, W = img.shape
+    if tuple(img.stride()[3:]) != (H * W, W, 1):
+        raise RuntimeError(f"mix_apply: every volume must be contiguous, got strides {img.stride()}")
+    _mix_table(table, B, "mix_apply")
+    out = out if out is not None else torch.empty(img.shape, dtype=img.dtype, device=img.device)
+    if not (out.dtype == img.dtype and out.is_contiguous() and out.shape == img.shape):
+        raise RuntimeError("mix_apply: out must be contiguous, of img's shape and dtype")
+    # one read and one write per voxel; a mixup record reads its partner's volume on top, but which records are mixup ones only the device knows
+    _run("mix_apply", img.numel() * float(img.element_size()) * 2.0, "byte",
+         lambda: _lib.load().xvit_mix_apply(_ptr(img), _ptr(out), _dt(img), _ptr(table), B, M, D, H, W, img.stride(0), img.stride(1), _stream()), "xvit_mix_apply")
+    return out
+
+
+def mean_ce_mix(logits_m, labels, table, smoothing):
+    """xvit_mean_ce_mix: mean_ce with the soft target lam smooth(y_b) + oml smooth(y_partner[b]) read from table fp32 [B, 16]."""
+    M, B, Cn = logits_m.shape
+    if table is None:
+        raise RuntimeError("mean_ce_mix: a record table is required (mean_ce is the loss without mixing)")
+    _mix_table(table, B, "mean_ce_mix")
+    logits = torch.empty(B, Cn, dtype=torch.float32, device=logits_m.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits_m.device)
+    dl = torch.empty_like(logits_m)
+    _run("mean_ce_mix", (2.0 * logits_m.numel() + logits.numel() + table.numel()) * 4.0 + B * 8.0, "byte",
+         lambda: _lib.load().xvit_mean_ce_mix(_ptr(logits_m), _ptr(labels), _ptr(table), smoothing, _ptr(logits), _ptr(loss), _ptr(dl), M, B, Cn, _stream()),
+         "xvit_mean_ce_mix")
+    return logits, loss, dl
+
+
 def resize_pad_crop_i16(vol, img_size, pad_value=-1.0):
     """int16 [B, M, Ds, Hs, Ws] (NIfTI voxels, on the GPU) -> bf16 [B, M, 1, D, H, W]: the reference's
     ResizeWithPadOrCropd(img_size, constant_values=-1) + float cast (dataset_ucsf.py:84-88,152-158) in one pass."""

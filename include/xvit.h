@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 312 /* 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 313 /* 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -533,6 +533,69 @@ int xvit_mae_loss_fwd(const void* pred, int pred_dtype, const int32_t* drop_idx,
                       float* loss_seq, float* loss, int B, int M, int D, int H, int W, int dp, int hp, int wp, int Rm, xvit_stream_t stream);
 int xvit_mae_loss_bwd(const void* pred, int pred_dtype, const int32_t* drop_idx, const void* img, int img_dtype, const float* stats, const float* g,
                       void* dpred, int B, int M, int D, int H, int W, int dp, int hp, int wp, int Rm, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mixup / CutMix (csrc/mix.hip; Zhang et al. 2018, Yun et al. 2019): the label regulariser of ViT fine-tuning.  Every sample b of a batch
+ * is mixed with a partner sample, voxels and labels alike.  Two kernels with a table between them, as in the augmenting input stage: the
+ * draw turns (config, seed) into table[B, XVIT_MIX_NPARAM] (fp32, one readable record per sample), the apply kernel and the loss are pure
+ * functions of their inputs and that table.  A table may be written by hand.  The record:
+ *     [XVIT_MIX_MODE]        0 none, XVIT_MIX_MODE_MIXUP (1), XVIT_MIX_MODE_CUTMIX (2)
+ *     [XVIT_MIX_PARTNER]     index of the other sample, an integer stored as a float
+ *     [XVIT_MIX_LAM]         weight of the sample's own label and, for mixup, of its own voxels
+ *     [XVIT_MIX_OML]         1 - lam (fp32 subtraction of the stored lam)
+ *     [XVIT_MIX_BOX .. + 5]  d0, d1, h0, h1, w0, w1: the half-open CutMix box, integers stored exactly as floats (read clamped to the volume)
+ *     [XVIT_MIX_LAM0]        the raw Beta draw (for the reader only)
+ *     [11 .. 15]             zero
+ * A record is a plain copy of the sample's own volume with the sample's own label as the target, and its partner is never read, when its
+ * mode is neither 1 nor 2, when its partner is not an integer in [0, B), or when lam == 1.
+ *
+ * xvit_mix_draw: one thread per record, in fp64, nothing read back.  seed' = the seed mixed with the dropout epoch (xvit_set_dropout_epoch,
+ * read at run time: a captured step draws a new table at every replay).  Uniform i of decision block r is
+ * (hash32(seed', r * XVIT_MIX_DRAW_STRIDE + i) + 0.5) / 2^32; block b decides for sample b under per_sample, block 0 for the whole batch
+ * otherwise.  In a block: i = 0 mixes if u < prob; i = 1 picks CutMix if u < switch_prob (only when both alphas are positive, else the
+ * positive one decides); i = 2, 3, 4 the box centre floor(u * size) along D, H, W; i = 8 + g the U^(1 / alpha) boost of gamma draw g (alpha <
+ * 1: Gamma(alpha) = Gamma(alpha + 1) U^(1 / alpha)); i = 16 + 64 g + 4 k + (0, 1, 2): round k < 16 of gamma draw g, two uniforms for the
+ * Box-Muller normal x = sqrt(-2 ln u) cos(2 pi u') and one for the acceptance ln u'' < x^2 / 2 + d - d v + d ln v, v = (1 + x / sqrt(9 d))^3 > 0,
+ * d = alpha - 1 / 3 (Marsaglia-Tsang).  lam0 = G0 / (G0 + G1), or 0.5 if a gamma draw accepted none of its rounds.  Block B, i = 0: the shift
+ * s = 1 + floor(u * (B - 1)) of the batch; partner[b] = (b + s) mod B, so nobody is paired with themself; B = 1 gives mode 0.  Mixup:
+ * lam = lam0.  CutMix: extents floor(size * r), r = cbrt(1 - lam0); the box starts at centre - extent / 2 (integer division), is `extent`
+ * long and is then clipped to the volume; lam = 1 - box voxels / (D H W).  One box and one lam per sample, for all its modalities.
+ * Refused: null pointers, a table not 16-byte aligned, B outside 1 .. 2^24 - 1, a volume of 2^31 voxels or more, a negative or non-finite
+ * alpha, a probability outside [0, 1].
+ *
+ * xvit_mix_apply: dst [B, M, D H W] contiguous = src mixed through the table; src element (b, m, v) at b * stride_b + m * stride_m + v
+ * (strides in elements, each volume contiguous); dtype XVIT_BF16 or XVIT_F32 for both.  Mixup: fmaf(lam, own, oml * partner) in fp32,
+ * rounded once to dtype.  CutMix: the partner's voxel inside the box, the own voxel outside, copied bit for bit, every voxel read from
+ * exactly one of the two.  Out of place: a dst that overlaps the source range is refused.  16 bytes per lane where W and both strides
+ * are multiples of 16 bytes of elements and src and dst are 16-byte aligned, else one voxel per lane (same result, slower).  No atomics.
+ *
+ * xvit_mean_ce_mix: xvit_mean_ce with the target lam * smooth(y_b) + oml * smooth(y_partner[b]), smooth(y) = (1 - eps) onehot(y) + eps / C,
+ * lam, oml and partner read from the table on the device; a copy record (see above) has the own label's target.  Same operations in the
+ * same order as xvit_mean_ce: a table whose records all have lam = 1 gives its logits, loss and dlogits_m bit for bit.  A NULL table is
+ * refused.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_MIX_NPARAM 16
+#define XVIT_MIX_MODE 0
+#define XVIT_MIX_PARTNER 1
+#define XVIT_MIX_LAM 2
+#define XVIT_MIX_OML 3
+#define XVIT_MIX_BOX 4
+#define XVIT_MIX_LAM0 10
+#define XVIT_MIX_MODE_MIXUP 1
+#define XVIT_MIX_MODE_CUTMIX 2
+#define XVIT_MIX_DRAW_STRIDE 256
+typedef struct xvit_mix_config {
+  float mixup_alpha;  /* Beta(alpha, alpha) of mixup; 0: no mixup */
+  float cutmix_alpha; /* Beta(alpha, alpha) of CutMix; 0: no CutMix */
+  float prob;         /* a batch (a sample under per_sample) is mixed with this probability */
+  float switch_prob;  /* with both alphas positive: CutMix with this probability, else mixup */
+  int32_t per_sample; /* 0: one mode, lam0 and box for the batch; 1: drawn per sample */
+} xvit_mix_config;
+int xvit_mix_draw(const xvit_mix_config* config, float* table, int B, int D, int H, int W, uint64_t seed, xvit_stream_t stream);
+int xvit_mix_apply(const void* src, void* dst, int dtype, const float* table, int B, int M, int D, int H, int W, int64_t stride_b, int64_t stride_m,
+                   xvit_stream_t stream);
+int xvit_mean_ce_mix(const float* logits_m, const int64_t* labels, const float* table, float label_smoothing, float* logits, float* loss, float* dlogits_m,
+                     int M, int B, int C, xvit_stream_t stream);
 
 /* ---- elementwise / reductions --------------------------------------------------------- */
 int xvit_cast_f32_bf16(const float* src, void* dst_bf16, int64_t n, xvit_stream_t stream);
