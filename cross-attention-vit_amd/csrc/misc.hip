@@ -520,6 +520,108 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict_
   }
 }
 
+// AdamW with a per-tensor rate and decay and a fused weight average (xvit_adamw_step / xvit_adamw_step_dev): adam_kernel's geometry and
+// tables plus one xvit_adamw_extra row per tensor.  The 16-byte path additionally needs the average, when there is one, 16-byte aligned.
+__device__ __forceinline__ bool adamw_vec_ok(const AdamTensor& t, const xvit_adamw_extra& x) {
+  return adam_vec_ok(t) && (reinterpret_cast<uintptr_t>(x.ema) & 15) == 0;
+}
+
+// DECOUPLED: p *= 1 - lr_t wd_t first (torch.optim.AdamW: the raw rate, not lr / bc1), then Adam on g * grad_scale.  Otherwise the
+// coupled update of adam_kernel with the tensor's own rate and decay.  The average e += w (p' - e) and the bf16 copy are formed from the
+// p' just stored, in the same registers.  The step count the warm-up reads is the one the prologue already advanced.
+template <bool FROM_RECORD, bool DECOUPLED>
+__global__ __launch_bounds__(256) void adamw_kernel(const AdamTensor* __restrict__ table, const xvit_adamw_extra* __restrict__ extras,
+                                                    const int2* __restrict__ chunks, float lr, float lr_over_bc1, float beta1, float beta2, float eps,
+                                                    float inv_sqrt_bc2, float grad_scale, float ema_w, int ema_warmup,
+                                                    const xvit_adam_state* __restrict__ st) {
+  if constexpr (FROM_RECORD) {
+    if (st->skip) return;
+    lr = st->lr;
+    lr_over_bc1 = st->lr_over_bc1;
+    inv_sqrt_bc2 = st->inv_sqrt_bc2;
+    grad_scale = st->clip_coef;
+    float d = ema_w;                      // arrives as ema_decay
+    if (ema_warmup) {
+      const float s = (float)st->step;
+      d = fminf(d, (1.0f + s) / (10.0f + s));
+    }
+    ema_w = 1.0f - d;
+  }
+  const int2 ch = chunks[blockIdx.x];
+  const AdamTensor t = table[ch.x];
+  const xvit_adamw_extra x = extras[ch.x];
+  const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
+  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
+  const bool vec = adamw_vec_ok(t, x);
+  const float a = lr_over_bc1 * x.lr_scale, lr_t = lr * x.lr_scale, wd = x.weight_decay;
+  float* __restrict__ const ema = x.ema;
+  auto upd = [&](float& p, float g, float& m, float& v) {
+    if constexpr (DECOUPLED) {
+      p *= 1.0f - lr_t * wd;
+      g = g * grad_scale;
+    } else {
+      g = g * grad_scale + wd * p;
+    }
+    m = beta1 * m + (1.0f - beta1) * g;
+    v = beta2 * v + (1.0f - beta2) * g * g;
+    p -= a * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
+  };
+  auto scalar = [&](int64_t i) {
+    upd(t.p[i], t.g[i], t.m[i], t.v[i]);
+    const float p = t.p[i];
+    if (ema) { const float e = ema[i]; ema[i] = e + ema_w * (p - e); }
+    if (t.shadow) t.shadow[i] = f2bf(p);
+  };
+  if (vec) {
+    for (int64_t i = begin + threadIdx.x * 4; i + 3 < end; i += 256 * 4) {
+      f32x4 p = *(f32x4*)(t.p + i), m = *(f32x4*)(t.m + i), v = *(f32x4*)(t.v + i), e = {0.f, 0.f, 0.f, 0.f};
+      const f32x4 g = *(const f32x4*)(t.g + i);
+      if (ema) e = *(f32x4*)(ema + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float pe = p[k], me = m[k], ve = v[k];
+        upd(pe, g[k], me, ve);
+        p[k] = pe; m[k] = me; v[k] = ve;
+        e[k] = e[k] + ema_w * (pe - e[k]);
+      }
+      *(f32x4*)(t.p + i) = p; *(f32x4*)(t.m + i) = m; *(f32x4*)(t.v + i) = v;
+      if (ema) *(f32x4*)(ema + i) = e;
+      if (t.shadow) *(bf16x4*)(t.shadow + i) = to_bf16x4(p);
+    }
+    const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
+    for (int64_t i = tail + threadIdx.x; i < end; i += 256) scalar(i);
+  } else {
+    for (int64_t i = begin + threadIdx.x; i < end; i += 256) scalar(i);
+  }
+}
+
+// Exchanges p and the average element by element and writes bf16 of the new p: copies only, so twice is the identity.
+__global__ __launch_bounds__(256) void ema_swap_kernel(const AdamTensor* __restrict__ table, const xvit_adamw_extra* __restrict__ extras,
+                                                       const int2* __restrict__ chunks) {
+  const int2 ch = chunks[blockIdx.x];
+  const AdamTensor t = table[ch.x];
+  const xvit_adamw_extra x = extras[ch.x];
+  if (!x.ema) return;
+  const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
+  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
+  auto scalar = [&](int64_t i) {
+    const float p = t.p[i], e = x.ema[i];
+    t.p[i] = e; x.ema[i] = p;
+    if (t.shadow) t.shadow[i] = f2bf(e);
+  };
+  if (adamw_vec_ok(t, x)) {
+    for (int64_t i = begin + threadIdx.x * 4; i + 3 < end; i += 256 * 4) {
+      const f32x4 p = *(f32x4*)(t.p + i), e = *(f32x4*)(x.ema + i);
+      *(f32x4*)(t.p + i) = e; *(f32x4*)(x.ema + i) = p;
+      if (t.shadow) *(bf16x4*)(t.shadow + i) = to_bf16x4(e);
+    }
+    const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
+    for (int64_t i = tail + threadIdx.x; i < end; i += 256) scalar(i);
+  } else {
+    for (int64_t i = begin + threadIdx.x; i < end; i += 256) scalar(i);
+  }
+}
+
 // Sum of g*g over one 16384-element chunk per block, written with ONE plain store to partials[blockIdx.x]: no float atomics, so the
 // norm is bit-identical from run to run.  Summation order per chunk (all fp32, the products fused into the adds): 16-byte path: four
 // accumulators per thread, 16 sequential adds each (one more for a tail element), 2 levels to join them; scalar path: 64 sequential
@@ -622,6 +724,44 @@ extern "C" int xvit_adam_step_dev(const void* table_dev, const void* chunks_dev,
   hipLaunchKernelGGL(xvit::adam_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev,
                      0.f, beta1, beta2, eps, weight_decay, 0.f, 0.f, state_dev);
   return xvit::check_launch("xvit_adam_step_dev");
+}
+
+extern "C" int xvit_adamw_step(const void* table_dev, const xvit_adamw_extra* extras_dev, const void* chunks_dev, int n_chunks, float lr, float beta1,
+                               float beta2, float eps, int step, float grad_scale, int decoupled, float ema_weight, xvit_stream_t stream) {
+  XVIT_REQUIRE(table_dev && extras_dev && chunks_dev, "xvit_adamw_step: null table, extras or chunk list");
+  XVIT_REQUIRE(n_chunks > 0 && step >= 1, "xvit_adamw_step: n_chunks=%d must be positive and step=%d at least 1", n_chunks, step);
+  XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adamw_step: bad hyper-parameters");
+  XVIT_REQUIRE(ema_weight >= 0.f && ema_weight <= 1.f, "xvit_adamw_step: ema_weight=%g must lie in [0, 1]", (double)ema_weight);
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  const float L = (float)(lr / bc1), I = (float)(1.0 / sqrt(bc2));
+#define XVIT_ADAMW_LAUNCH(DEC)                                                                                                                        \
+  hipLaunchKernelGGL((xvit::adamw_kernel<false, DEC>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, extras_dev, \
+                     (const int2*)chunks_dev, lr, L, beta1, beta2, eps, I, grad_scale, ema_weight, 0, (const xvit_adam_state*)nullptr)
+  if (decoupled) XVIT_ADAMW_LAUNCH(true); else XVIT_ADAMW_LAUNCH(false);
+#undef XVIT_ADAMW_LAUNCH
+  return xvit::check_launch("xvit_adamw_step");
+}
+
+extern "C" int xvit_adamw_step_dev(const void* table_dev, const xvit_adamw_extra* extras_dev, const void* chunks_dev, int n_chunks,
+                                   const xvit_adam_state* state_dev, float beta1, float beta2, float eps, int decoupled, float ema_decay, int ema_warmup,
+                                   xvit_stream_t stream) {
+  XVIT_REQUIRE(table_dev && extras_dev && chunks_dev && state_dev, "xvit_adamw_step_dev: null table, extras, chunk list or state record");
+  XVIT_REQUIRE(n_chunks > 0, "xvit_adamw_step_dev: n_chunks=%d must be positive", n_chunks);
+  XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adamw_step_dev: bad hyper-parameters");
+  XVIT_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "xvit_adamw_step_dev: ema_decay=%g must lie in [0, 1)", (double)ema_decay);
+#define XVIT_ADAMW_LAUNCH(DEC)                                                                                                                       \
+  hipLaunchKernelGGL((xvit::adamw_kernel<true, DEC>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, extras_dev, \
+                     (const int2*)chunks_dev, 0.f, 0.f, beta1, beta2, eps, 0.f, 0.f, ema_decay, ema_warmup, state_dev)
+  if (decoupled) XVIT_ADAMW_LAUNCH(true); else XVIT_ADAMW_LAUNCH(false);
+#undef XVIT_ADAMW_LAUNCH
+  return xvit::check_launch("xvit_adamw_step_dev");
+}
+
+extern "C" int xvit_ema_swap(const void* table_dev, const xvit_adamw_extra* extras_dev, const void* chunks_dev, int n_chunks, xvit_stream_t stream) {
+  XVIT_REQUIRE(table_dev && extras_dev && chunks_dev, "xvit_ema_swap: null table, extras or chunk list");
+  XVIT_REQUIRE(n_chunks > 0, "xvit_ema_swap: n_chunks=%d must be positive", n_chunks);
+  hipLaunchKernelGGL(xvit::ema_swap_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, extras_dev, (const int2*)chunks_dev);
+  return xvit::check_launch("xvit_ema_swap");
 }
 
 // ------------------------------------------------------------------------------------------

@@ -133,6 +133,9 @@ SIGNATURES = {
     "xvit_grad_sqnorm_partials": [vp, vp, i32, vp, vp],
     "xvit_adam_prologue": [vp, i32, vp, f32, f32, f32, i32, vp],
     "xvit_adam_step_dev": [vp, vp, i32, vp, f32, f32, f32, f32, vp],
+    "xvit_adamw_step": [vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, i32, f32, vp],
+    "xvit_adamw_step_dev": [vp, vp, vp, i32, vp, f32, f32, f32, i32, f32, i32, vp],
+    "xvit_ema_swap": [vp, vp, vp, i32, vp],
     "xvit_grad_pack_bf16": [C.POINTER(GradSegment), i32, vp, i64, f32, vp],
     "xvit_grad_unpack_bf16": [vp, vp, i64, f32, vp],
 }

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 313 /* 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 314 /* 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -677,6 +677,37 @@ int xvit_adam_prologue(const float* partials_dev, int n_partials, xvit_adam_stat
                        int skip_nonfinite, xvit_stream_t stream);
 int xvit_adam_step_dev(const void* table_dev, const void* chunks_dev, int n_chunks, const xvit_adam_state* state_dev, float beta1, float beta2,
                        float eps, float weight_decay, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * AdamW with a rate and a decay per tensor and a fused exponential moving average of the weights.  table_dev / chunks_dev are the tables
+ * of xvit_adam_step (so xvit_grad_sqnorm_partials and xvit_adam_prologue run unchanged on them); extras_dev is a device array with one
+ * xvit_adamw_extra per row of table_dev:
+ *   lr_scale      the tensor's rate is lr * lr_scale (layer-wise learning-rate decay);  a = (lr / bc1) * lr_scale, lr_t = lr * lr_scale in fp32
+ *   weight_decay  the tensor's decay wd_t
+ *   ema           fp32 average of p (n elements), or NULL: this tensor keeps none
+ * Update order per element, all fp32:
+ *   decoupled != 0 (torch.optim.AdamW):  p *= 1 - lr_t * wd_t  (first, with the raw rate, not lr / bc1);  g^ = g * grad_scale
+ *   decoupled == 0 (torch.optim.Adam):   g^ = g * grad_scale + wd_t * p
+ *   m = beta1 m + (1 - beta1) g^;  v = beta2 v + (1 - beta2) g^ g^;  p -= a * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ *   ema += w * (p - ema) with the p just stored;  shadow_bf16 = bf16(p)
+ * xvit_adamw_step: w = ema_weight, in [0, 1].  xvit_adamw_step_dev reads lr, the bias corrections, clip_coef (the gradient scale) and
+ *   `skip` from *state_dev as xvit_adam_step_dev does (a skipped step writes nothing, the average included), and forms
+ *   w = 1 - ema_decay, or with ema_warmup != 0  w = 1 - min(ema_decay, (1 + t) / (10 + t)),  t = (float)state->step, the count the
+ *   prologue already advanced (1 at the first step).  ema_decay in [0, 1).
+ * xvit_ema_swap: exchanges p and ema element by element for every tensor that has an average and writes shadow_bf16 = bf16(new p);
+ *   copies only, so a second call restores every bit.  Tensors with ema = NULL and chunks the list does not name are left alone.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct xvit_adamw_extra {
+  float* ema;          /* or NULL */
+  float lr_scale;
+  float weight_decay;
+} xvit_adamw_extra;    /* 16 bytes */
+int xvit_adamw_step(const void* table_dev, const xvit_adamw_extra* extras_dev, const void* chunks_dev, int n_chunks, float lr, float beta1,
+                    float beta2, float eps, int step, float grad_scale, int decoupled, float ema_weight, xvit_stream_t stream);
+int xvit_adamw_step_dev(const void* table_dev, const xvit_adamw_extra* extras_dev, const void* chunks_dev, int n_chunks,
+                        const xvit_adam_state* state_dev, float beta1, float beta2, float eps, int decoupled, float ema_decay, int ema_warmup,
+                        xvit_stream_t stream);
+int xvit_ema_swap(const void* table_dev, const xvit_adamw_extra* extras_dev, const void* chunks_dev, int n_chunks, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * bf16 wire format of the data-parallel gradient reducer (xvit/ddp.py, comm_dtype=torch.bfloat16; the counterpart of DDP's

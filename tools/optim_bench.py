@@ -6,6 +6,9 @@ clock and host drift hit both; one JSON line per variant.  Run each mode under i
     python tools/optim_bench.py step  [iters] [rounds]   # FusedAdam.step(): host wall time of the call and GPU time
     python tools/optim_bench.py clip  [iters] [rounds]   # clip_grad_norm_ + FusedAdam.step()  vs  FusedAdam(max_grad_norm=...)
     python tools/optim_bench.py graph [iters] [rounds]   # batch 8: GraphedStep + eager opt.step()  vs  GraphedStep(optimizer=opt)
+    python tools/optim_bench.py adamw [iters] [rounds]   # FusedAdamW without an average  vs  FusedAdam at equal settings (eager and capturable)
+    python tools/optim_bench.py ema   [iters] [rounds]   # FusedAdamW(ema_decay=...)  vs  FusedAdam.step() + torch._foreach_lerp_ over the same tensors
+    python tools/optim_bench.py layers [iters] [rounds]  # batch 8, GraphedStep on layer_decay_groups: FusedAdamW (one launch set)  vs  FusedAdam (one per group)
 
 host_ms: time.perf_counter around the call(s), no synchronisation inside (what the Python thread pays per step);
 gpu_ms: device events around the same calls;  wall_ms: a block of iterations ending in a synchronise, per iteration."""
@@ -23,7 +26,7 @@ sys.path.insert(0, ROOT)
 import xvit  # noqa: E402
 from bench import base_config  # noqa: E402
 from xvit.graph import GraphedStep  # noqa: E402
-from xvit.optim import FusedAdam  # noqa: E402
+from xvit.optim import FusedAdam, FusedAdamW, layer_decay_groups  # noqa: E402
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "step"
 nums = [int(a) for a in sys.argv[2:] if a.isdigit()]
@@ -52,8 +55,8 @@ def backward(model):
     loss.backward()
 
 
-def measure(variants):
-    """variants: {name: callable}.  Rounds of `iters` calls each, interleaved; per call host time and event time, per block wall time."""
+def measure(variants, extra=None):
+    """variants: {name: callable}; extra: {name: dict} merged into the variant's JSON line.  Rounds of `iters` calls each, interleaved; per call host time and event time, per block wall time."""
     res = {k: {"host": [], "gpu": [], "wall": []} for k in variants}
     for fn in variants.values():                          # warm-up: every variant, every shape
         for _ in range(3):
@@ -79,7 +82,9 @@ def measure(variants):
                           "iters": iters, "rounds": rounds,
                           "host_ms_median": round(statistics.median(r["host"]), 4), "gpu_ms_median": round(statistics.median(r["gpu"]), 4),
                           "wall_ms_per_iter_median": round(statistics.median(r["wall"]), 4),
-                          "wall_ms_per_iter_min_max": [round(min(r["wall"]), 4), round(max(r["wall"]), 4)]}), flush=True)
+                          "wall_ms_per_iter_min_max": [round(min(r["wall"]), 4), round(max(r["wall"]), 4)],
+                          "gpu_ms_round_medians": [round(statistics.median(r["gpu"][i * iters:(i + 1) * iters]), 4) for i in range(rounds)],
+                          **((extra or {}).get(name, {}))}), flush=True)
 
 
 model = make_model()
@@ -116,5 +121,45 @@ elif mode == "graph":
 
     measure({"GraphedStep + eager FusedAdam.step()": graph_then_eager_step, "GraphedStep(optimizer=FusedAdam(capturable))": lambda: step_b(img, labels),
              "GraphedStep(optimizer=FusedAdam(capturable, max_grad_norm=1))": lambda: step_c(img, labels)})
+elif mode == "adamw":
+    backward(model)
+    params = list(model.parameters())
+    n = sum(p.numel() for p in params)
+    kw = dict(lr=1e-5, weight_decay=0.05)
+    adam, adamw = FusedAdam(params, **kw), FusedAdamW(params, **kw)
+    adam_c, adamw_c = FusedAdam(params, capturable=True, **kw), FusedAdamW(params, capturable=True, **kw)
+    measure({"FusedAdam.step()": adam.step, "FusedAdamW.step()": adamw.step, "FusedAdam(capturable=True).step()": adam_c.step,
+             "FusedAdamW(capturable=True).step()": adamw_c.step}, {k: {"bytes_per_step_GB": round(26 * n / 1e9, 3)} for k in ("FusedAdam(capturable=True).step()", "FusedAdamW(capturable=True).step()")})
+elif mode == "ema":
+    backward(model)
+    params = list(model.parameters())
+    n = sum(p.numel() for p in params)
+    kw = dict(lr=1e-5, weight_decay=0.05)
+    adam, adam_c = FusedAdam(params, **kw), FusedAdam(params, capturable=True, **kw)
+    fused, fused_c = FusedAdamW(params, ema_decay=0.9999, **kw), FusedAdamW(params, ema_decay=0.9999, capturable=True, **kw)
+    shadow = [p.detach().clone() for p in params]
+    datas = [p.detach() for p in params]
+
+    def adam_then_lerp(opt):
+        def fn():
+            opt.step()
+            torch._foreach_lerp_(shadow, datas, 1.0 - 0.9999)
+        return fn
+
+    measure({"FusedAdam.step() + _foreach_lerp_": adam_then_lerp(adam), "FusedAdamW(ema_decay).step()": fused.step,
+             "FusedAdam(capturable=True).step() + _foreach_lerp_": adam_then_lerp(adam_c), "FusedAdamW(ema_decay, capturable=True).step()": fused_c.step},
+            {"FusedAdam.step() + _foreach_lerp_": {"bytes_per_step_GB": round(38 * n / 1e9, 3)}, "FusedAdamW(ema_decay).step()": {"bytes_per_step_GB": round(34 * n / 1e9, 3)},
+             "FusedAdam(capturable=True).step() + _foreach_lerp_": {"bytes_per_step_GB": round(38 * n / 1e9, 3)},
+             "FusedAdamW(ema_decay, capturable=True).step()": {"bytes_per_step_GB": round(34 * n / 1e9, 3)}})
+elif mode == "layers":
+    model_b = make_model()
+    opt_a = FusedAdamW(layer_decay_groups(model, 0.75, 0.05), lr=1e-5, capturable=True)
+    step_a = GraphedStep(model, img, labels, optimizer=opt_a)
+    opt_b = FusedAdam(layer_decay_groups(model_b, 0.75, 0.05), lr=1e-5, capturable=True)      # ignores lr_scale: only the launch structure is compared
+    step_b = GraphedStep(model_b, img, labels, optimizer=opt_b)
+    measure({"GraphedStep(optimizer=FusedAdamW(layer_decay_groups))": lambda: step_a(img, labels),
+             "GraphedStep(optimizer=FusedAdam(layer_decay_groups))": lambda: step_b(img, labels)},
+            {"GraphedStep(optimizer=FusedAdamW(layer_decay_groups))": {"groups": len(opt_a.param_groups), "optimizer_launches": 2 * len(opt_a._entries)},
+             "GraphedStep(optimizer=FusedAdam(layer_decay_groups))": {"groups": len(opt_b.param_groups), "optimizer_launches": 2 * len(opt_b._entries)}})
 else:
-    raise SystemExit(f"unknown mode {mode!r}: step | clip | graph")
+    raise SystemExit(f"unknown mode {mode!r}: step | clip | graph | adamw | ema | layers")
