@@ -464,162 +464,133 @@ namespace xvit {
 struct AdamTensor { float* p; const float* g; float* m; float* v; bf16* shadow; int64_t n; };
 constexpr int ADAM_CHUNK = 16384;   // elements per block
 
-// 16-byte accesses for every array of the tensor (the chunk start is a multiple of 16384 elements, so the base decides)
-__device__ __forceinline__ bool adam_vec_ok(const AdamTensor& t) {
-  return ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
-           reinterpret_cast<uintptr_t>(t.v)) & 15) == 0 && (!t.shadow || (reinterpret_cast<uintptr_t>(t.shadow) & 7) == 0);
-}
-
-// FROM_RECORD = false: step size, bias correction and gradient scale arrive by value (xvit_adam_step).  true: they are read from the
-// device-resident record the step prologue wrote (xvit_adam_step_dev), so a captured launch follows the step count, the learning rate
-// and the clip coefficient of each replay; a step the prologue flagged as skipped returns before touching anything.
-template <bool FROM_RECORD>
-__global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict__ table, const int2* __restrict__ chunks, float lr_over_bc1,
-                                                   float beta1, float beta2, float eps, float wd, float inv_sqrt_bc2, float grad_scale,
-                                                   const xvit_adam_state* __restrict__ st) {
-  if constexpr (FROM_RECORD) {
-    if (st->skip) return;
-    lr_over_bc1 = st->lr_over_bc1;
-    inv_sqrt_bc2 = st->inv_sqrt_bc2;
-    grad_scale = st->clip_coef;
-  }
+// The chunk of this block: its tensor's row of the table, with EXTRAS its row of the extras table (zeros otherwise), and the elements
+// [begin, end) of that tensor.  Both rows are fetched before either is used: one scalar-load round trip per block, not two.
+struct AdamChunk { AdamTensor t; xvit_adamw_extra x; int64_t begin, end; };
+template <bool EXTRAS>
+__device__ __forceinline__ AdamChunk adam_chunk(const AdamTensor* __restrict__ table, const xvit_adamw_extra* __restrict__ extras,
+                                                const int2* __restrict__ chunks) {
   const int2 ch = chunks[blockIdx.x];
   const AdamTensor t = table[ch.x];
+  xvit_adamw_extra x = {nullptr, 0.f, 0.f};
+  if constexpr (EXTRAS) x = extras[ch.x];
   const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
-  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
-  const bool vec = adam_vec_ok(t);
-  auto upd = [&](float& p, float g, float& m, float& v) {
-    g = g * grad_scale + wd * p;
-    m = beta1 * m + (1.0f - beta1) * g;
-    v = beta2 * v + (1.0f - beta2) * g * g;
-    p -= lr_over_bc1 * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
-  };
+  return {t, x, begin, begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n};
+}
+
+// 16-byte accesses for every array of the tensor, the average included when there is one (the chunk start is a multiple of 16384
+// elements, so the base decides)
+__device__ __forceinline__ bool adam_vec_ok(const AdamTensor& t, const float* ema = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) | reinterpret_cast<uintptr_t>(t.v) |
+           reinterpret_cast<uintptr_t>(ema)) & 15) == 0 && (!t.shadow || (reinterpret_cast<uintptr_t>(t.shadow) & 7) == 0);
+}
+
+// The element loops of one chunk.  vec: quad(i) on every whole group of four elements, 16 bytes per array and lane, then scalar(i) on
+// the up to three left over; otherwise scalar(i) throughout.
+template <class Quad, class Scalar>
+__device__ __forceinline__ void adam_walk(const AdamChunk& c, bool vec, Quad quad, Scalar scalar) {
   if (vec) {
-    for (int64_t i = begin + threadIdx.x * 4; i + 3 < end; i += 256 * 4) {
-      f32x4 p = *(f32x4*)(t.p + i), m = *(f32x4*)(t.m + i), v = *(f32x4*)(t.v + i);
-      const f32x4 g = *(const f32x4*)(t.g + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {   // vector elements cannot bind to references: go through scalars
-        float pe = p[e], me = m[e], ve = v[e];
-        upd(pe, g[e], me, ve);
-        p[e] = pe; m[e] = me; v[e] = ve;
-      }
-      *(f32x4*)(t.p + i) = p; *(f32x4*)(t.m + i) = m; *(f32x4*)(t.v + i) = v;
-      if (t.shadow) *(bf16x4*)(t.shadow + i) = to_bf16x4(p);
-    }
-    const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
-    for (int64_t i = tail + threadIdx.x; i < end; i += 256) {
-      upd(t.p[i], t.g[i], t.m[i], t.v[i]);
-      if (t.shadow) t.shadow[i] = f2bf(t.p[i]);
-    }
+    for (int64_t i = c.begin + threadIdx.x * 4; i + 3 < c.end; i += 256 * 4) quad(i);
+    const int64_t tail = c.begin + ((c.end - c.begin) & ~(int64_t)3);
+    for (int64_t i = tail + threadIdx.x; i < c.end; i += 256) scalar(i);
   } else {
-    for (int64_t i = begin + threadIdx.x; i < end; i += 256) {
-      upd(t.p[i], t.g[i], t.m[i], t.v[i]);
-      if (t.shadow) t.shadow[i] = f2bf(t.p[i]);
-    }
+    for (int64_t i = c.begin + threadIdx.x; i < c.end; i += 256) scalar(i);
   }
 }
 
-// AdamW with a per-tensor rate and decay and a fused weight average (xvit_adamw_step / xvit_adamw_step_dev): adam_kernel's geometry and
-// tables plus one xvit_adamw_extra row per tensor.  The 16-byte path additionally needs the average, when there is one, 16-byte aligned.
-__device__ __forceinline__ bool adamw_vec_ok(const AdamTensor& t, const xvit_adamw_extra& x) {
-  return adam_vec_ok(t) && (reinterpret_cast<uintptr_t>(x.ema) & 15) == 0;
-}
+// ADAM_PLAIN (xvit_adam_step / xvit_adam_step_dev): one rate for the launch, group-wide decay `wd` by value, L2 decay added to the
+// gradient; no extras table, no average.  The other two (xvit_adamw_step / xvit_adamw_step_dev) read one xvit_adamw_extra row per
+// tensor: its own rate scale and decay and, when non-null, a weight average updated in the same pass (the 16-byte path then needs it
+// 16-byte aligned too).  ADAM_COUPLED is the plain update with those; ADAM_DECOUPLED does p *= 1 - lr_t wd_t first (torch.optim.AdamW:
+// the raw rate, not lr / bc1), then Adam on g * grad_scale.
+enum AdamMode { ADAM_PLAIN, ADAM_COUPLED, ADAM_DECOUPLED };
 
-// DECOUPLED: p *= 1 - lr_t wd_t first (torch.optim.AdamW: the raw rate, not lr / bc1), then Adam on g * grad_scale.  Otherwise the
-// coupled update of adam_kernel with the tensor's own rate and decay.  The average e += w (p' - e) and the bf16 copy are formed from the
-// p' just stored, in the same registers.  The step count the warm-up reads is the one the prologue already advanced.
-template <bool FROM_RECORD, bool DECOUPLED>
-__global__ __launch_bounds__(256) void adamw_kernel(const AdamTensor* __restrict__ table, const xvit_adamw_extra* __restrict__ extras,
-                                                    const int2* __restrict__ chunks, float lr, float lr_over_bc1, float beta1, float beta2, float eps,
-                                                    float inv_sqrt_bc2, float grad_scale, float ema_w, int ema_warmup,
-                                                    const xvit_adam_state* __restrict__ st) {
+// FROM_RECORD = false: rate, bias corrections, gradient scale and the average's weight arrive by value.  true: they are read from the
+// device-resident record the step prologue wrote, so a captured launch follows the step count, the learning rate and the clip
+// coefficient of each replay; a step the prologue flagged as skipped returns before touching anything.  The average e += w (p' - e)
+// and the bf16 copy are formed from the p' just stored, in the same registers.  The step count the warm-up reads is the one the
+// prologue already advanced.
+template <bool FROM_RECORD, AdamMode MODE>
+__global__ __launch_bounds__(256) void adam_kernel(const AdamTensor* __restrict__ table, const xvit_adamw_extra* __restrict__ extras,
+                                                   const int2* __restrict__ chunks, float lr, float lr_over_bc1, float beta1, float beta2, float eps,
+                                                   float wd, float inv_sqrt_bc2, float grad_scale, float ema_w, int ema_warmup,
+                                                   const xvit_adam_state* __restrict__ st) {
+  constexpr bool EXTRAS = MODE != ADAM_PLAIN;
   if constexpr (FROM_RECORD) {
     if (st->skip) return;
-    lr = st->lr;
     lr_over_bc1 = st->lr_over_bc1;
     inv_sqrt_bc2 = st->inv_sqrt_bc2;
     grad_scale = st->clip_coef;
-    float d = ema_w;                      // arrives as ema_decay
-    if (ema_warmup) {
-      const float s = (float)st->step;
-      d = fminf(d, (1.0f + s) / (10.0f + s));
+    if constexpr (EXTRAS) {
+      lr = st->lr;
+      float d = ema_w;                      // arrives as ema_decay
+      if (ema_warmup) {
+        const float s = (float)st->step;
+        d = fminf(d, (1.0f + s) / (10.0f + s));
+      }
+      ema_w = 1.0f - d;
     }
-    ema_w = 1.0f - d;
   }
-  const int2 ch = chunks[blockIdx.x];
-  const AdamTensor t = table[ch.x];
-  const xvit_adamw_extra x = extras[ch.x];
-  const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
-  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
-  const bool vec = adamw_vec_ok(t, x);
-  const float a = lr_over_bc1 * x.lr_scale, lr_t = lr * x.lr_scale, wd = x.weight_decay;
-  float* __restrict__ const ema = x.ema;
+  const AdamChunk c = adam_chunk<EXTRAS>(table, extras, chunks);
+  const AdamTensor& t = c.t;
+  float a = lr_over_bc1, lr_t = lr;
+  float* __restrict__ const ema = c.x.ema;
+  if constexpr (EXTRAS) {
+    a = lr_over_bc1 * c.x.lr_scale; lr_t = lr * c.x.lr_scale; wd = c.x.weight_decay;
+  }
   auto upd = [&](float& p, float g, float& m, float& v) {
-    if constexpr (DECOUPLED) {
+    if constexpr (MODE == ADAM_DECOUPLED) {
       p *= 1.0f - lr_t * wd;
       g = g * grad_scale;
     } else {
-      g = g * grad_scale + wd * p;
-    }
+      g = fmaf(g, grad_scale, wd * p);   // g * grad_scale + wd * p with the contraction spelled out: left to the compiler, the 16-byte path of
+    }                                    // the folded kernel fused the other product, one rounding apart from what these entry points always gave
     m = beta1 * m + (1.0f - beta1) * g;
     v = beta2 * v + (1.0f - beta2) * g * g;
     p -= a * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
   };
-  auto scalar = [&](int64_t i) {
-    upd(t.p[i], t.g[i], t.m[i], t.v[i]);
-    const float p = t.p[i];
-    if (ema) { const float e = ema[i]; ema[i] = e + ema_w * (p - e); }
-    if (t.shadow) t.shadow[i] = f2bf(p);
-  };
-  if (vec) {
-    for (int64_t i = begin + threadIdx.x * 4; i + 3 < end; i += 256 * 4) {
+  adam_walk(c, adam_vec_ok(t, ema),
+    [&](int64_t i) {
       f32x4 p = *(f32x4*)(t.p + i), m = *(f32x4*)(t.m + i), v = *(f32x4*)(t.v + i), e = {0.f, 0.f, 0.f, 0.f};
       const f32x4 g = *(const f32x4*)(t.g + i);
-      if (ema) e = *(f32x4*)(ema + i);
+      if constexpr (EXTRAS) { if (ema) e = *(f32x4*)(ema + i); }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < 4; ++k) {   // vector elements cannot bind to references: go through scalars
         float pe = p[k], me = m[k], ve = v[k];
         upd(pe, g[k], me, ve);
         p[k] = pe; m[k] = me; v[k] = ve;
-        e[k] = e[k] + ema_w * (pe - e[k]);
+        if constexpr (EXTRAS) e[k] = e[k] + ema_w * (pe - e[k]);
       }
       *(f32x4*)(t.p + i) = p; *(f32x4*)(t.m + i) = m; *(f32x4*)(t.v + i) = v;
-      if (ema) *(f32x4*)(ema + i) = e;
+      if constexpr (EXTRAS) { if (ema) *(f32x4*)(ema + i) = e; }
       if (t.shadow) *(bf16x4*)(t.shadow + i) = to_bf16x4(p);
-    }
-    const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
-    for (int64_t i = tail + threadIdx.x; i < end; i += 256) scalar(i);
-  } else {
-    for (int64_t i = begin + threadIdx.x; i < end; i += 256) scalar(i);
-  }
+    },
+    [&](int64_t i) {
+      upd(t.p[i], t.g[i], t.m[i], t.v[i]);
+      const float p = t.p[i];
+      if constexpr (EXTRAS) { if (ema) { const float e = ema[i]; ema[i] = e + ema_w * (p - e); } }
+      if (t.shadow) t.shadow[i] = f2bf(p);
+    });
 }
 
 // Exchanges p and the average element by element and writes bf16 of the new p: copies only, so twice is the identity.
 __global__ __launch_bounds__(256) void ema_swap_kernel(const AdamTensor* __restrict__ table, const xvit_adamw_extra* __restrict__ extras,
                                                        const int2* __restrict__ chunks) {
-  const int2 ch = chunks[blockIdx.x];
-  const AdamTensor t = table[ch.x];
-  const xvit_adamw_extra x = extras[ch.x];
-  if (!x.ema) return;
-  const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
-  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
-  auto scalar = [&](int64_t i) {
-    const float p = t.p[i], e = x.ema[i];
-    t.p[i] = e; x.ema[i] = p;
-    if (t.shadow) t.shadow[i] = f2bf(e);
-  };
-  if (adamw_vec_ok(t, x)) {
-    for (int64_t i = begin + threadIdx.x * 4; i + 3 < end; i += 256 * 4) {
-      const f32x4 p = *(f32x4*)(t.p + i), e = *(f32x4*)(x.ema + i);
-      *(f32x4*)(t.p + i) = e; *(f32x4*)(x.ema + i) = p;
+  const AdamChunk c = adam_chunk<true>(table, extras, chunks);
+  const AdamTensor& t = c.t;
+  float* const ema = c.x.ema;
+  if (!ema) return;
+  adam_walk(c, adam_vec_ok(t, ema),
+    [&](int64_t i) {
+      const f32x4 p = *(f32x4*)(t.p + i), e = *(f32x4*)(ema + i);
+      *(f32x4*)(t.p + i) = e; *(f32x4*)(ema + i) = p;
       if (t.shadow) *(bf16x4*)(t.shadow + i) = to_bf16x4(e);
-    }
-    const int64_t tail = begin + ((end - begin) & ~(int64_t)3);
-    for (int64_t i = tail + threadIdx.x; i < end; i += 256) scalar(i);
-  } else {
-    for (int64_t i = begin + threadIdx.x; i < end; i += 256) scalar(i);
-  }
+    },
+    [&](int64_t i) {
+      const float p = t.p[i], e = ema[i];
+      t.p[i] = e; ema[i] = p;
+      if (t.shadow) t.shadow[i] = f2bf(e);
+    });
 }
 
 // Sum of g*g over one 16384-element chunk per block, written with ONE plain store to partials[blockIdx.x]: no float atomics, so the
@@ -629,10 +600,9 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(const AdamTensor* __restr
 // error is at most the roundings on the longest path: (64 + 6 + 2) * 2^-24 = 4.3e-6 (scalar), (17 + 2 + 6 + 2) * 2^-24 = 1.6e-6 (16-byte).
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const AdamTensor* __restrict__ table, const int2* __restrict__ chunks, float* __restrict__ partials) {
   __shared__ float wave_part[4];
-  const int2 ch = chunks[blockIdx.x];
-  const AdamTensor t = table[ch.x];
-  const int64_t begin = (int64_t)ch.y * ADAM_CHUNK;
-  const int64_t end = begin + ADAM_CHUNK < t.n ? begin + ADAM_CHUNK : t.n;
+  const AdamChunk c = adam_chunk<false>(table, nullptr, chunks);
+  const AdamTensor& t = c.t;
+  const int64_t begin = c.begin, end = c.end;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   if (adam_vec_ok(t)) {
 #pragma unroll 4
@@ -686,6 +656,23 @@ __global__ __launch_bounds__(256) void adam_prologue_kernel(const float* __restr
   st->lr_over_bc1 = (float)((double)st->lr / bc1);
   st->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
 }
+
+// adam_kernel's by-value arguments, in its order.  With a record (st) the kernel reads lr, lr_over_bc1, inv_sqrt_bc2 and grad_scale from it
+// and takes ema_w as the average's DECAY; ADAM_PLAIN uses neither lr, ema_w nor ema_warmup, the other modes take wd from the extras.
+struct AdamScalars { float lr, lr_over_bc1, beta1, beta2, eps, wd, inv_sqrt_bc2, grad_scale, ema_w; int ema_warmup; };
+
+static void adam_launch(AdamMode mode, const void* table, const xvit_adamw_extra* extras, const void* chunks, int n_chunks, const AdamScalars& a,
+                        const xvit_adam_state* st, xvit_stream_t stream) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamTensor*)table, extras, (const int2*)chunks, a.lr, a.lr_over_bc1,
+                       a.beta1, a.beta2, a.eps, a.wd, a.inv_sqrt_bc2, a.grad_scale, a.ema_w, a.ema_warmup, st);
+  };
+  switch (mode) {
+    case ADAM_PLAIN:     st ? go(adam_kernel<true, ADAM_PLAIN>)     : go(adam_kernel<false, ADAM_PLAIN>);     break;
+    case ADAM_COUPLED:   st ? go(adam_kernel<true, ADAM_COUPLED>)   : go(adam_kernel<false, ADAM_COUPLED>);   break;
+    case ADAM_DECOUPLED: st ? go(adam_kernel<true, ADAM_DECOUPLED>) : go(adam_kernel<false, ADAM_DECOUPLED>); break;
+  }
+}
 }  // namespace xvit
 
 extern "C" int xvit_adam_step(const void* table_dev, const void* chunks_dev, int n_chunks, float lr, float beta1, float beta2, float eps,
@@ -693,8 +680,8 @@ extern "C" int xvit_adam_step(const void* table_dev, const void* chunks_dev, int
   XVIT_REQUIRE(table_dev && chunks_dev && n_chunks > 0 && step >= 1, "xvit_adam_step: bad arguments");
   XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adam_step: bad hyper-parameters");
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  hipLaunchKernelGGL(xvit::adam_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev,
-                     (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale, (const xvit_adam_state*)nullptr);
+  xvit::adam_launch(xvit::ADAM_PLAIN, table_dev, nullptr, chunks_dev, n_chunks,
+                    {0.f, (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale, 0.f, 0}, nullptr, stream);
   return xvit::check_launch("xvit_adam_step");
 }
 
@@ -721,8 +708,7 @@ extern "C" int xvit_adam_step_dev(const void* table_dev, const void* chunks_dev,
   XVIT_REQUIRE(table_dev && chunks_dev && state_dev, "xvit_adam_step_dev: null table, chunk list or state record");
   XVIT_REQUIRE(n_chunks > 0, "xvit_adam_step_dev: n_chunks=%d must be positive", n_chunks);
   XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adam_step_dev: bad hyper-parameters");
-  hipLaunchKernelGGL(xvit::adam_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, (const int2*)chunks_dev,
-                     0.f, beta1, beta2, eps, weight_decay, 0.f, 0.f, state_dev);
+  xvit::adam_launch(xvit::ADAM_PLAIN, table_dev, nullptr, chunks_dev, n_chunks, {0.f, 0.f, beta1, beta2, eps, weight_decay, 0.f, 0.f, 0.f, 0}, state_dev, stream);
   return xvit::check_launch("xvit_adam_step_dev");
 }
 
@@ -733,12 +719,8 @@ extern "C" int xvit_adamw_step(const void* table_dev, const xvit_adamw_extra* ex
   XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adamw_step: bad hyper-parameters");
   XVIT_REQUIRE(ema_weight >= 0.f && ema_weight <= 1.f, "xvit_adamw_step: ema_weight=%g must lie in [0, 1]", (double)ema_weight);
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float L = (float)(lr / bc1), I = (float)(1.0 / sqrt(bc2));
-#define XVIT_ADAMW_LAUNCH(DEC)                                                                                                                        \
-  hipLaunchKernelGGL((xvit::adamw_kernel<false, DEC>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, extras_dev, \
-                     (const int2*)chunks_dev, lr, L, beta1, beta2, eps, I, grad_scale, ema_weight, 0, (const xvit_adam_state*)nullptr)
-  if (decoupled) XVIT_ADAMW_LAUNCH(true); else XVIT_ADAMW_LAUNCH(false);
-#undef XVIT_ADAMW_LAUNCH
+  xvit::adam_launch(decoupled ? xvit::ADAM_DECOUPLED : xvit::ADAM_COUPLED, table_dev, extras_dev, chunks_dev, n_chunks,
+                    {lr, (float)(lr / bc1), beta1, beta2, eps, 0.f, (float)(1.0 / sqrt(bc2)), grad_scale, ema_weight, 0}, nullptr, stream);
   return xvit::check_launch("xvit_adamw_step");
 }
 
@@ -749,11 +731,8 @@ extern "C" int xvit_adamw_step_dev(const void* table_dev, const xvit_adamw_extra
   XVIT_REQUIRE(n_chunks > 0, "xvit_adamw_step_dev: n_chunks=%d must be positive", n_chunks);
   XVIT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "xvit_adamw_step_dev: bad hyper-parameters");
   XVIT_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "xvit_adamw_step_dev: ema_decay=%g must lie in [0, 1)", (double)ema_decay);
-#define XVIT_ADAMW_LAUNCH(DEC)                                                                                                                       \
-  hipLaunchKernelGGL((xvit::adamw_kernel<true, DEC>), dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const xvit::AdamTensor*)table_dev, extras_dev, \
-                     (const int2*)chunks_dev, 0.f, 0.f, beta1, beta2, eps, 0.f, 0.f, ema_decay, ema_warmup, state_dev)
-  if (decoupled) XVIT_ADAMW_LAUNCH(true); else XVIT_ADAMW_LAUNCH(false);
-#undef XVIT_ADAMW_LAUNCH
+  xvit::adam_launch(decoupled ? xvit::ADAM_DECOUPLED : xvit::ADAM_COUPLED, table_dev, extras_dev, chunks_dev, n_chunks,
+                    {0.f, 0.f, beta1, beta2, eps, 0.f, 0.f, 0.f, ema_decay, ema_warmup}, state_dev, stream);
   return xvit::check_launch("xvit_adamw_step_dev");
 }
 

@@ -26,6 +26,11 @@ torch scheduler works; betas, eps, weight decay and max_grad_norm are frozen int
 
 `skip_nonfinite=True` (needs `capturable=True`: only a device-side step count can stand still without a synchronisation): a step whose
 gradient norm is inf or NaN changes no parameter, no moment and not the step count; `opt.skipped_steps` counts them on the device.
+
+Both classes run one skeleton.  A step works on LAUNCH SETS (`_Set`): the tensors that go into one table, their chunk list, their offset
+into the norm partials and one device record.  FusedAdam makes one set per parameter group, FusedAdamW one per (betas, eps, step count)
+across groups; a subclass says how tensors are keyed into sets (`_set_key`), what a set carries beside its table and chunk list and
+which rate its record gets (`_fill`), and which entry point steps it (`_launch_step`).  Everything else stands once, in FusedAdam.
 """
 from __future__ import annotations
 
@@ -46,14 +51,45 @@ _REC_DTYPE = np.dtype([("step", "<i8"), ("skipped", "<i8"), ("lr", "<f4"), ("gra
                        ("inv_sqrt_bc2", "<f4"), ("skip", "<i4"), ("reserved", "<i4", (2,))])
 _F_LR, _F_NORM = 4, 5          # fp32 word index of lr / grad_norm
 assert _REC_DTYPE.itemsize == 8 * _REC_WORDS
+# struct xvit_adamw_extra (include/xvit.h): one row per row of the tensor table
+_EXTRA_DTYPE = np.dtype([("ema", "<u8"), ("lr_scale", "<f4"), ("weight_decay", "<f4")])
+assert _EXTRA_DTYPE.itemsize == 16
 
 
-class _Entry:
-    """The static launch arguments of one parameter group in capturable mode."""
-    __slots__ = ("gi", "params", "idx", "table", "chunks", "n_chunks", "off", "p_ptrs", "g_ptrs", "rec", "lr_view", "lr")
+class _Set:
+    """One launch set.  Host side: the tensors (each with its group index `gis` and its index in that group `idx`), their table rows
+    and chunk list, the step count they share.  Device side, once uploaded: `table`, `chunk_t`, the record at `rec_ptr`, and whatever
+    the optimizer's `_fill` adds.  Eager mode builds the sets anew every step; capturable mode keeps them (`p_ptrs`, `g_ptrs`, `lr`,
+    `lr_view` are what check_addresses() and sync_lr() compare against)."""
+    __slots__ = ("step", "steps", "params", "gis", "idx", "rows", "chunks", "keep", "n_chunks", "off", "table", "chunk_t", "rec_ptr", "lr", "lr_view",
+                 "p_ptrs", "g_ptrs", "groups", "extras", "extras_host", "seen")
+
+    def __init__(self):
+        self.steps, self.params, self.gis, self.idx, self.rows, self.chunks, self.keep = set(), [], [], [], [], [], []
+        self.extras = None
+
+    def add(self, row, p, gi=None, i=None):
+        """Append one tensor: its table row (FusedAdam._row) and one (row index, chunk index) pair per CHUNK elements."""
+        t = len(self.rows)
+        self.chunks.extend((t, c) for c in range((row[5] + CHUNK - 1) // CHUNK))
+        self.rows.append(row); self.params.append(p); self.gis.append(gi); self.idx.append(i)
+
+    def upload(self, dev, non_blocking):
+        self.n_chunks = len(self.chunks)
+        self.table = _upload(np.asarray(self.rows, dtype=np.int64), dev, non_blocking)
+        self.chunk_t = _upload(np.asarray(self.chunks, dtype=np.int32), dev, non_blocking)
+
+
+def _upload(a, dev, non_blocking):
+    """A host array on the device; a structured one (records, extras) as rows of int64 words."""
+    if a.dtype.names:
+        a = a.view(np.int64).reshape(len(a), -1)
+    return torch.from_numpy(a).to(dev, non_blocking=non_blocking)
 
 
 class FusedAdam(torch.optim.Optimizer):
+    _SET = "parameter group"          # what one launch set is, in messages
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *, max_grad_norm=None, capturable=False,
                  skip_nonfinite=False):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
@@ -67,21 +103,13 @@ class FusedAdam(torch.optim.Optimizer):
         self.capturable = bool(capturable)
         self.skip_nonfinite = bool(skip_nonfinite)
         self.lr_copies = 0            # how many times sync_lr() wrote a learning rate to the device
-        self._entries = None          # capturable mode: built by prepare()
+        self._entries = None          # capturable mode: the launch sets, built by prepare()
         self._records = self._partials = self._last_norm = None
         self._touched, self._unshadowed = [], []
 
     @staticmethod
-    def _shadow_of(p):
-        for grp in XF.SHADOWS.groups:
-            i = grp.index.get(id(p))
-            if i is not None and grp.params[i] is p and grp.intact():
-                return grp, grp.view16[i]
-        return None, None
-
-    @staticmethod
-    def _validate(p):
-        if not p.is_cuda or p.dtype != torch.float32 or p.grad.dtype != torch.float32 or p.grad.is_sparse:
+    def _validate(p, g):
+        if not p.is_cuda or p.dtype != torch.float32 or g.dtype != torch.float32 or g.is_sparse:
             raise RuntimeError("xvit FusedAdam: parameters and gradients must be dense fp32 tensors on the GPU")
         if not p.is_contiguous():
             raise RuntimeError("xvit FusedAdam: non-contiguous parameter")
@@ -109,10 +137,39 @@ class FusedAdam(torch.optim.Optimizer):
         """Number of steps skip_nonfinite dropped: 0-dim int64 device tensor (capturable mode after the first step), else None."""
         return None if self._entries is None else self._records[0, 1]
 
-    def _describe(self, e, i):
-        names = self.param_groups[e.gi].get("param_names")
-        p = e.params[i]
-        return f"parameter {e.idx[i]} of group {e.gi}" + (f" ({names[e.idx[i]]})" if names else "") + f", shape {tuple(p.shape)}"
+    def _describe(self, s, i):
+        gi, idx, p = s.gis[i], s.idx[i], s.params[i]
+        names = self.param_groups[gi].get("param_names")
+        return f"parameter {idx} of group {gi}" + (f" ({names[idx]})" if names else "") + f", shape {tuple(p.shape)}"
+
+    def _one_step(self, s, steps, found):
+        """The step count a capturable launch set keeps in its one record; `found` words the refusal when its tensors disagree."""
+        if len(steps) != 1:
+            raise ValueError(f"xvit {type(self).__name__}(capturable=True) keeps one step count per {self._SET}; {found} steps {sorted(steps)} in the "
+                             f"{self._SET} over group(s) {sorted(set(s.gis))}")
+        return next(iter(steps))
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # what a subclass replaces
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _set_key(self, gi, group, step):
+        """Tensors with equal keys share a launch set (eager mode splits further by step count, which the host keeps per parameter)."""
+        return gi
+
+    def _fill(self, s, dev, eager):
+        """After the table and the chunk list: the rate the set's record (or by-value launch) carries, and any further device table."""
+        s.lr = float(self.param_groups[s.gis[0]]["lr"])
+
+    def _launch_step(self, lib, s, by_value, stream):
+        """The update of one set: numbers by value (eager without a norm: step count s.step + 1) or from the record at s.rec_ptr."""
+        group = self.param_groups[s.gis[0]]
+        b1, b2 = group["betas"]
+        if by_value:
+            _lib.check(lib.xvit_adam_step(s.table.data_ptr(), s.chunk_t.data_ptr(), s.n_chunks, s.lr, b1, b2, group["eps"], group["weight_decay"], s.step + 1,
+                                          1.0, stream), "xvit_adam_step")
+        else:
+            _lib.check(lib.xvit_adam_step_dev(s.table.data_ptr(), s.chunk_t.data_ptr(), s.n_chunks, s.rec_ptr, b1, b2, group["eps"], group["weight_decay"],
+                                              stream), "xvit_adam_step_dev")
 
     # ------------------------------------------------------------------------------------------------------------------------
     # host bookkeeping after the kernels wrote the parameters
@@ -129,138 +186,136 @@ class FusedAdam(torch.optim.Optimizer):
         XF.SHADOWS.drop(self._unshadowed)
         self._opt_called = True       # what torch's lr_scheduler checks before its first step(): a replayed step counts as one
 
-    # ------------------------------------------------------------------------------------------------------------------------
-    # eager mode: tables per step, as the step count is kept per parameter on the host
-    # ------------------------------------------------------------------------------------------------------------------------
-    def _step_eager(self, lib):
-        touched, unshadowed, launches = {}, [], []
-        for group in self.param_groups:
-            buckets, keep = {}, []          # step count -> (rows, chunks): torch keeps the step per parameter
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                self._validate(p)
-                st = self._state_of(p)
-                st["step"] += 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                grp, sh = self._shadow_of(p)
-                if grp is not None:
-                    touched[id(grp)] = grp
-                else:
-                    unshadowed.append(p)
-                keep.append(g)
-                rows, chunks = buckets.setdefault(st["step"], ([], []))
-                t = len(rows)
-                rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                             sh.data_ptr() if sh is not None else 0, p.numel()))
-                chunks.extend((t, c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
-            launches.extend((group, step, rows, chunks, keep) for step, (rows, chunks) in buckets.items())
-        if self.max_grad_norm is None:
-            for group, step, rows, chunks, _ in launches:
-                b1, b2 = group["betas"]
-                dev = group["params"][0].device
-                table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev, non_blocking=True)
-                chunk_t = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev, non_blocking=True)
-                _lib.check(lib.xvit_adam_step(table.data_ptr(), chunk_t.data_ptr(), len(chunks), float(group["lr"]), b1, b2, group["eps"],
-                                              group["weight_decay"], step, 1.0, torch.cuda.current_stream().cuda_stream), "xvit_adam_step")
-                table.record_stream(torch.cuda.current_stream()); chunk_t.record_stream(torch.cuda.current_stream())
-        elif launches:
-            # norm over ALL groups and step buckets -> one prologue per bucket (its own step count and learning rate) -> Adam
-            dev = launches[0][0]["params"][0].device
-            cur = torch.cuda.current_stream()
-            rec = np.zeros(len(launches), dtype=_REC_DTYPE)
-            rec["step"] = [step - 1 for _, step, _, _, _ in launches]          # the prologue advances it
-            rec["lr"] = [group["lr"] for group, _, _, _, _ in launches]
-            records = torch.from_numpy(rec.view(np.int64).reshape(-1, _REC_WORDS)).to(dev, non_blocking=True)
-            total = sum(len(chunks) for _, _, _, chunks, _ in launches)
-            partials = torch.empty(total, dtype=torch.float32, device=dev)
-            tables, off = [], 0
-            for _, _, rows, chunks, _ in launches:
-                table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev, non_blocking=True)
-                chunk_t = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev, non_blocking=True)
-                _lib.check(lib.xvit_grad_sqnorm_partials(table.data_ptr(), chunk_t.data_ptr(), len(chunks), partials.data_ptr() + 4 * off,
-                                                         cur.cuda_stream), "xvit_grad_sqnorm_partials")
-                tables.append((table, chunk_t))
-                off += len(chunks)
-            for k, ((group, _, _, chunks, _), (table, chunk_t)) in enumerate(zip(launches, tables)):
-                b1, b2 = group["betas"]
-                state_ptr = records.data_ptr() + 8 * _REC_WORDS * k
-                _lib.check(lib.xvit_adam_prologue(partials.data_ptr(), total, state_ptr, self.max_grad_norm, b1, b2, 0, cur.cuda_stream), "xvit_adam_prologue")
-                _lib.check(lib.xvit_adam_step_dev(table.data_ptr(), chunk_t.data_ptr(), len(chunks), state_ptr, b1, b2, group["eps"],
-                                                  group["weight_decay"], cur.cuda_stream), "xvit_adam_step_dev")
-                table.record_stream(cur); chunk_t.record_stream(cur)
-            records.record_stream(cur); partials.record_stream(cur)
-            self._last_norm = records[0].view(torch.float32)[_F_NORM]
+    def _mark(self, marks):
+        touched, unshadowed = marks
         self._touched = [weakref.ref(g) for g in touched.values()]
         self._unshadowed = unshadowed
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # launch sets: the walk, the tables, the records, the launches
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _row(self, p, g, marks=None):
+        """The table row of p (struct AdamTensor in csrc/misc.hip): p, g, both moments, the bf16 operand copy an intact flat weight group
+        keeps of p (0: none) and numel.  `marks` = ({}, []) collects what mark_updated() needs: the flat groups written, and the
+        parameters that have no such copy."""
+        st = self.state[p]
+        sh = 0
+        for grp in XF.SHADOWS.groups:
+            i = grp.index.get(id(p))
+            if i is not None and grp.params[i] is p and grp.intact():
+                sh = grp.view16[i].data_ptr()
+                if marks is not None:
+                    marks[0][id(grp)] = grp
+                break
+        else:
+            if marks is not None:
+                marks[1].append(p)
+        return (p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), sh, p.numel())
+
+    def _collect(self, eager):
+        """Every parameter that has a gradient, keyed into launch sets (first-seen order) and uploaded.  Eager: advances the host step
+        counts and takes a contiguous copy of a strided gradient (the set keeps it alive).  Capturable: refuses one, and a set whose
+        tensors sit at different step counts."""
+        sets, marks = {}, ({}, [])
+        for gi, group in enumerate(self.param_groups):
+            by_step = {}                    # step count -> the set this group's tensors at that count go to: one key per count, not per tensor
+            for i, p in enumerate(group["params"]):
+                g = p.grad
+                if g is None:
+                    continue
+                self._validate(p, g)
+                st = self._state_of(p)
+                step = int(st["step"])
+                s = by_step.get(step)
+                if s is None:
+                    key = self._set_key(gi, group, step)
+                    s = by_step[step] = sets.setdefault((key, step) if eager else key, _Set())
+                    s.steps.add(step)
+                if not g.is_contiguous():
+                    if not eager:
+                        raise RuntimeError(f"xvit {type(self).__name__}(capturable=True): non-contiguous gradient")
+                    g = g.contiguous()
+                    s.keep.append(g)
+                if eager:
+                    st["step"] = step + 1
+                s.add(self._row(p, g, marks), p, gi, i)
+        sets, off = list(sets.values()), 0
+        for s in sets:
+            s.step = self._one_step(s, s.steps, "it finds parameters at")
+            dev = s.params[0].device
+            s.upload(dev, eager)
+            s.off = off
+            off += s.n_chunks
+            self._fill(s, dev, eager)
+        self._mark(marks)
+        return sets
+
+    def _device_state(self, sets, non_blocking):
+        """-> (one record per set, holding its step count and rate; one norm partial per chunk of all sets, or None without a norm)."""
+        dev = sets[0].table.device
+        rec = np.zeros(len(sets), dtype=_REC_DTYPE)
+        rec["step"] = [s.step for s in sets]          # the prologue advances it
+        rec["lr"] = [s.lr for s in sets]
+        records = _upload(rec, dev, non_blocking)
+        for k, s in enumerate(sets):
+            s.rec_ptr = records.data_ptr() + 8 * _REC_WORDS * k
+        partials = torch.empty(sum(s.n_chunks for s in sets), dtype=torch.float32, device=dev) if self._needs_norm else None
+        return records, partials
+
+    def _launch(self, lib, sets, partials, stream, by_value=False):
+        """The launches of one step: the norm partials of every set (when a norm is taken), then per set one prologue, which turns ALL
+        partials into norm and clip coefficient and advances the set's record, and the update.  by_value: the update alone."""
+        if partials is not None:
+            for s in sets:
+                _lib.check(lib.xvit_grad_sqnorm_partials(s.table.data_ptr(), s.chunk_t.data_ptr(), s.n_chunks, partials.data_ptr() + 4 * s.off, stream),
+                           "xvit_grad_sqnorm_partials")
+        part, n_part = (partials.data_ptr(), partials.numel()) if partials is not None else (None, 0)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else math.inf
+        for s in sets:
+            if not by_value:
+                b1, b2 = self.param_groups[s.gis[0]]["betas"]
+                _lib.check(lib.xvit_adam_prologue(part, n_part, s.rec_ptr, max_norm, b1, b2, int(self.skip_nonfinite), stream), "xvit_adam_prologue")
+            self._launch_step(lib, s, by_value, stream)
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    # eager mode: sets per step, as the step count is kept per parameter on the host
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _step_eager(self, lib):
+        sets = self._collect(eager=True)
+        if sets:
+            cur = torch.cuda.current_stream()
+            records, partials = self._device_state(sets, True) if self._needs_norm else (None, None)
+            self._launch(lib, sets, partials, cur.cuda_stream, by_value=records is None)
+            for s in sets:
+                for t in (s.table, s.chunk_t, s.extras):
+                    if t is not None:
+                        t.record_stream(cur)
+            if records is not None:
+                records.record_stream(cur); partials.record_stream(cur)
+                self._last_norm = records[0].view(torch.float32)[_F_NORM]
         self.mark_updated()
 
     # ------------------------------------------------------------------------------------------------------------------------
     # capturable mode: everything built once
     # ------------------------------------------------------------------------------------------------------------------------
-    def _rows_of(self, e):
-        rows = []
-        for p in e.params:
-            st = self.state[p]
-            _, sh = self._shadow_of(p)
-            rows.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                         sh.data_ptr() if sh is not None else 0, p.numel()))
-        return rows
-
     @torch.no_grad()
     def prepare(self):
-        """capturable=True: build the device tables, chunk lists, norm partials and state records from the parameters that have a
-        gradient NOW (allocation + host-to-device copies: not capturable, so call it, or take one eager step, before a capture).
-        Later calls do nothing."""
+        """capturable=True: build the device tables, chunk lists, norm partials and state records of every launch set from the
+        parameters that have a gradient NOW (allocation + host-to-device copies: not capturable, so call it, or take one eager step,
+        before a capture).  Later calls do nothing."""
+        name = type(self).__name__
         if not self.capturable:
-            raise RuntimeError("xvit FusedAdam.prepare: only for capturable=True")
+            raise RuntimeError(f"xvit {name}.prepare: only for capturable=True")
         if self._entries is not None:
             return
-        entries, touched, unshadowed, off = [], {}, [], 0
-        for gi, group in enumerate(self.param_groups):
-            e = _Entry()
-            e.gi, e.params, e.idx = gi, [], []
-            chunks, steps = [], set()
-            for i, p in enumerate(group["params"]):
-                if p.grad is None:
-                    continue
-                self._validate(p)
-                if not p.grad.is_contiguous():
-                    raise RuntimeError("xvit FusedAdam(capturable=True): non-contiguous gradient")
-                steps.add(int(self._state_of(p)["step"]))
-                grp, _ = self._shadow_of(p)
-                if grp is not None:
-                    touched[id(grp)] = grp
-                else:
-                    unshadowed.append(p)
-                chunks.extend((len(e.params), c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
-                e.params.append(p); e.idx.append(i)
-            if not e.params:
-                continue
-            if len(steps) != 1:
-                raise ValueError(f"xvit FusedAdam(capturable=True) keeps one step count per parameter group; group {gi} holds parameters at steps {sorted(steps)}")
-            dev = e.params[0].device
-            e.lr = float(group["lr"])
-            e.n_chunks, e.off = len(chunks), off
-            off += len(chunks)
-            e.chunks = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev)
-            e.table = torch.empty(len(e.params), 6, dtype=torch.int64, device=dev)
-            entries.append((e, steps.pop()))
-        if not entries:
-            raise RuntimeError("xvit FusedAdam.prepare: no parameter has a gradient yet (run one backward, or set the static .grad buffers, first)")
-        rec = np.zeros(len(entries), dtype=_REC_DTYPE)
-        rec["step"] = [step for _, step in entries]
-        rec["lr"] = [e.lr for e, _ in entries]
-        dev = entries[0][0].table.device
-        self._records = torch.from_numpy(rec.view(np.int64).reshape(-1, _REC_WORDS)).to(dev)
-        self._partials = torch.empty(off, dtype=torch.float32, device=dev) if self._needs_norm else None
-        for k, (e, _) in enumerate(entries):
-            e.rec = self._records[k]
-            e.lr_view = e.rec.view(torch.float32)[_F_LR]
-        self._entries = [e for e, _ in entries]
+        sets = self._collect(eager=False)
+        if not sets:
+            raise RuntimeError(f"xvit {name}.prepare: no parameter has a gradient yet (run one backward, or set the static .grad buffers, first)")
+        self._records, self._partials = self._device_state(sets, False)
+        for k, s in enumerate(sets):
+            s.lr_view = self._records[k].view(torch.float32)[_F_LR]
+        self._entries = sets
         self._last_norm = self._records[0].view(torch.float32)[_F_NORM] if self._needs_norm else None
-        self._touched = [weakref.ref(g) for g in touched.values()]
-        self._unshadowed = unshadowed
         self.rebind()
 
     @torch.no_grad()
@@ -268,54 +323,44 @@ class FusedAdam(torch.optim.Optimizer):
         """Re-read the addresses of the parameters, their CURRENT .grad tensors and bf16 copies into the existing device tables (a
         host-to-device copy: outside any capture).  The launches hold only the tables' own addresses, so a graph captured before stays
         valid: xvit.graph.GraphedStep captures the step first and binds the gradient buffers the capture allocated afterwards."""
-        for e in self._entries:
-            for i, p in enumerate(e.params):
+        for s in self._entries:
+            for i, p in enumerate(s.params):
                 if p.grad is None or p.grad.shape != p.shape or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
-                    raise RuntimeError(f"xvit FusedAdam.rebind: {self._describe(e, i)} has no dense contiguous fp32 gradient to bind")
-            rows = self._rows_of(e)
-            e.table.copy_(torch.from_numpy(np.asarray(rows, dtype=np.int64)))
-            e.p_ptrs = [r[0] for r in rows]
-            e.g_ptrs = [r[1] for r in rows]
+                    raise RuntimeError(f"xvit FusedAdam.rebind: {self._describe(s, i)} has no dense contiguous fp32 gradient to bind")
+            s.rows = [self._row(p, p.grad) for p in s.params]
+            s.table.copy_(torch.from_numpy(np.asarray(s.rows, dtype=np.int64)))
+            s.p_ptrs = [r[0] for r in s.rows]
+            s.g_ptrs = [r[1] for r in s.rows]
 
     def check_addresses(self, grads: bool = True):
         """capturable mode: every parameter (and, with grads=True, its .grad) still lives at the address in the device table."""
-        for e in self._entries or ():
-            for i, p in enumerate(e.params):
-                if p.data_ptr() != e.p_ptrs[i]:
-                    raise RuntimeError(f"xvit FusedAdam(capturable=True): the storage of {self._describe(e, i)} moved after the tables were built "
+        for s in self._entries or ():
+            for i, p in enumerate(s.params):
+                if p.data_ptr() != s.p_ptrs[i]:
+                    raise RuntimeError(f"xvit FusedAdam(capturable=True): the storage of {self._describe(s, i)} moved after the tables were built "
                                        "(model.to(...), a re-built flat weight buffer); build a new optimizer")
-                if grads and (p.grad is None or p.grad.data_ptr() != e.g_ptrs[i]):
-                    raise RuntimeError(f"xvit FusedAdam(capturable=True): the gradient of {self._describe(e, i)} is no longer the tensor the device table "
+                if grads and (p.grad is None or p.grad.data_ptr() != s.g_ptrs[i]):
+                    raise RuntimeError(f"xvit FusedAdam(capturable=True): the gradient of {self._describe(s, i)} is no longer the tensor the device table "
                                        "points to (typically zero_grad(set_to_none=True) in an eager loop, which makes backward allocate a new one): "
                                        "use zero_grad(set_to_none=False), or xvit.graph.GraphedStep(..., optimizer=opt), which owns static gradient buffers")
+
+    def _sync_rate(self, s, lr):
+        if lr != s.lr:
+            s.lr_view.fill_(lr)
+            s.lr = lr
+            self.lr_copies += 1
 
     def sync_lr(self):
         """Write group["lr"] into the device record of every group whose rate changed since the last call (one tiny asynchronous fill
         on the current stream, value passed as a kernel argument: no host buffer to keep alive); nothing is issued otherwise.  step()
         calls it in eager mode, GraphedStep before each replay; call it yourself before replaying your own capture of step()."""
-        for e in self._entries or ():
-            lr = float(self.param_groups[e.gi]["lr"])
-            if lr != e.lr:
-                e.lr_view.fill_(lr)
-                e.lr = lr
-                self.lr_copies += 1
+        for s in self._entries or ():
+            self._sync_rate(s, float(self.param_groups[s.gis[0]]["lr"]))
 
     def enqueue(self):
-        """capturable mode: the launches of one step on the current stream and nothing else (no check, no bookkeeping)."""
-        lib = _lib.load()
-        stream = ops._stream()
-        if self._partials is not None:
-            for e in self._entries:
-                _lib.check(lib.xvit_grad_sqnorm_partials(e.table.data_ptr(), e.chunks.data_ptr(), e.n_chunks, self._partials.data_ptr() + 4 * e.off, stream),
-                           "xvit_grad_sqnorm_partials")
-        part, n_part = (self._partials.data_ptr(), self._partials.numel()) if self._partials is not None else (None, 0)
-        max_norm = self.max_grad_norm if self.max_grad_norm is not None else math.inf
-        for e in self._entries:
-            group = self.param_groups[e.gi]
-            b1, b2 = group["betas"]
-            _lib.check(lib.xvit_adam_prologue(part, n_part, e.rec.data_ptr(), max_norm, b1, b2, int(self.skip_nonfinite), stream), "xvit_adam_prologue")
-            _lib.check(lib.xvit_adam_step_dev(e.table.data_ptr(), e.chunks.data_ptr(), e.n_chunks, e.rec.data_ptr(), b1, b2, group["eps"],
-                                              group["weight_decay"], stream), "xvit_adam_step_dev")
+        """capturable mode: the launches of one step on the current stream and nothing else (no check, no bookkeeping): the gradient
+        norm (when one is taken), then one prologue + step pair per launch set."""
+        self._launch(_lib.load(), self._entries, self._partials, ops._stream())
 
     # ------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -339,54 +384,45 @@ class FusedAdam(torch.optim.Optimizer):
     # state_dict: torch's key names in both modes
     # ------------------------------------------------------------------------------------------------------------------------
     def state_dict(self):
-        """exp_avg / exp_avg_sq / step per parameter, as torch.optim.Adam names them.  In capturable mode `step` is read from the
-        device counters here (a synchronisation)."""
+        """exp_avg / exp_avg_sq / step per parameter, as torch.optim.Adam names them (FusedAdamW: and `ema`).  In capturable mode `step`
+        is read from the device counters here (a synchronisation)."""
         if self._entries is not None:
             steps = self._records[:, 0].tolist()
-            for e, step in zip(self._entries, steps):
-                for p in e.params:
+            for s, step in zip(self._entries, steps):
+                for p in s.params:
                     self.state[p]["step"] = int(step)
         return super().state_dict()
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
-        """Accepts a state dict of either mode (or of torch.optim.Adam).  Once the capturable tables exist, the values are copied INTO the
-        existing moment buffers and device counters, so a captured graph stays valid."""
-        old = {p: self.state[p] for e in self._entries or () for p in e.params}
+        """Accepts a state dict of either mode and of either class (or of torch.optim.Adam / AdamW).  Once the capturable tables exist,
+        the values are copied INTO the existing buffers and device counters, so a captured graph stays valid."""
+        old = {p: self.state[p] for s in self._entries or () for p in s.params}
         super().load_state_dict(state_dict)
-        for st in self.state.values():
+        for p, st in list(self.state.items()):
             if "step" in st:
                 st["step"] = int(st["step"])
-        for k, e in enumerate(self._entries or ()):
+            if "exp_avg" in st:
+                self._state_of(p)               # adds what this class keeps beside the moments
+        for k, s in enumerate(self._entries or ()):
             steps = set()
-            for i, p in enumerate(e.params):
+            for i, p in enumerate(s.params):
                 new = self.state.get(p)
                 if not new or "exp_avg" not in new:
-                    raise ValueError(f"xvit FusedAdam.load_state_dict: no state for {self._describe(e, i)}, which the capturable tables hold")
+                    raise ValueError(f"xvit {type(self).__name__}.load_state_dict: no state for {self._describe(s, i)}, which the capturable tables hold")
                 keep = old[p]
-                keep["exp_avg"].copy_(new["exp_avg"])
-                keep["exp_avg_sq"].copy_(new["exp_avg_sq"])
+                for name, buf in keep.items():
+                    if name != "step":
+                        buf.copy_(new[name])
                 keep["step"] = new["step"]
                 steps.add(new["step"])
                 self.state[p] = keep
-            if len(steps) != 1:
-                raise ValueError(f"xvit FusedAdam(capturable=True) keeps one step count per parameter group; the loaded state has steps {sorted(steps)} in group {e.gi}")
-            self._records[k, 0].fill_(steps.pop())
+            self._records[k, 0].fill_(self._one_step(s, steps, "the loaded state has"))
 
 
 # ============================================================================================================================
 # AdamW with layer-wise rates and a fused weight EMA
 # ============================================================================================================================
-# struct xvit_adamw_extra (include/xvit.h): one row per row of the tensor table
-_EXTRA_DTYPE = np.dtype([("ema", "<u8"), ("lr_scale", "<f4"), ("weight_decay", "<f4")])
-assert _EXTRA_DTYPE.itemsize == 16
-
-
-class _Set(_Entry):
-    """The static launch arguments of one launch set in capturable mode: every group that agrees on betas, eps and step count."""
-    __slots__ = ("groups", "gis", "extras", "extras_host", "seen")
-
-
 class _EmaWeights:
     def __init__(self, opt):
         self.opt = opt
@@ -419,6 +455,7 @@ class FusedAdamW(FusedAdam):
     of state_dict() / load_state_dict(); A LOADED STATE WITHOUT `ema` (one of FusedAdam or torch.optim.AdamW) STARTS THE AVERAGE AT THE
     CURRENT p.  `with opt.ema_weights(): ...` exchanges weights and average in place (and back on exit; addresses do not move, so a captured
     graph stays valid); `opt.ema_state_dict(model)` is the average under the model's own state_dict keys."""
+    _SET = "launch set"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, decoupled=True, ema_decay=None, ema_warmup=False,
                  max_grad_norm=None, capturable=False, skip_nonfinite=False):
@@ -452,6 +489,9 @@ class FusedAdamW(FusedAdam):
     def _key(group, step):
         return (float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), int(step))
 
+    def _set_key(self, gi, group, step):
+        return self._key(group, step)
+
     @property
     def launch_sets(self):
         """Number of launch sets: of the device tables in capturable mode once they exist, else of the next eager step."""
@@ -466,6 +506,12 @@ class FusedAdamW(FusedAdam):
         ref = lrs[0] if lrs[0] != 0 else next((x for x in lrs if x != 0), 0.0)
         return ref, [float(np.float32(float(g["lr_scale"]) if x == ref else float(g["lr_scale"]) * x / ref)) for g, x in zip(groups, lrs)]
 
+    def _scales(self, s):
+        """-> (the rate of set s, the fp32 scale of each of its tensors)."""
+        lr, scales = self._rates([self.param_groups[gi] for gi in s.groups])
+        scale_of = dict(zip(s.groups, scales))
+        return lr, np.asarray([scale_of[gi] for gi in s.gis], dtype=np.float32)
+
     def _ema_weight(self, step):
         """The weight the record path forms on the device, in the same fp32 arithmetic."""
         if self.ema_decay is None:
@@ -476,195 +522,50 @@ class FusedAdamW(FusedAdam):
             d = min(d, (np.float32(1) + t) / (np.float32(10) + t))
         return float(np.float32(1) - d)
 
-    def _describe(self, e, i):
-        gi = e.gis[i]
-        names = self.param_groups[gi].get("param_names")
-        p = e.params[i]
-        return f"parameter {e.idx[i]} of group {gi}" + (f" ({names[e.idx[i]]})" if names else "") + f", shape {tuple(p.shape)}"
-
-    @staticmethod
-    def _extras_of(params, states, scales, decays, with_ema):
+    def _extras_of(self, params, scales, decays, with_ema):
         x = np.zeros(len(params), dtype=_EXTRA_DTYPE)
-        x["ema"] = [states[p]["ema"].data_ptr() if with_ema else 0 for p in params]
+        x["ema"] = [self.state[p]["ema"].data_ptr() if with_ema else 0 for p in params]
         x["lr_scale"], x["weight_decay"] = scales, decays
         return x
 
-    @staticmethod
-    def _upload(x, dev):
-        return torch.from_numpy(x.view(np.int64).reshape(-1, 2)).to(dev, non_blocking=True)
+    def _seen(self, s):
+        return tuple((float(self.param_groups[gi]["lr"]), float(self.param_groups[gi]["lr_scale"])) for gi in s.groups)
 
-    # ------------------------------------------------------------------------------------------------------------------------
-    # eager mode
-    # ------------------------------------------------------------------------------------------------------------------------
-    def _step_eager(self, lib):
-        touched, unshadowed, sets = {}, [], {}
-        for gi, group in enumerate(self.param_groups):
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                self._validate(p)
-                st = self._state_of(p)
-                st["step"] += 1
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                grp, sh = self._shadow_of(p)
-                if grp is not None:
-                    touched[id(grp)] = grp
-                else:
-                    unshadowed.append(p)
-                s = sets.setdefault(self._key(group, st["step"]), dict(group=group, step=st["step"], gis=[], params=[], rows=[], chunks=[], keep=[]))
-                t = len(s["rows"])
-                s["rows"].append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), sh.data_ptr() if sh is not None else 0, p.numel()))
-                s["chunks"].extend((t, c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
-                s["gis"].append(gi); s["params"].append(p); s["keep"].append(g)
-        sets = list(sets.values())
-        if not sets:
-            return
-        dev = sets[0]["params"][0].device
-        cur = torch.cuda.current_stream()
-        for s in sets:
-            order = list(dict.fromkeys(s["gis"]))
-            s["lr"], scales = self._rates([self.param_groups[gi] for gi in order])
-            scale_of = dict(zip(order, scales))
-            x = self._extras_of(s["params"], self.state, [scale_of[gi] for gi in s["gis"]], [self.param_groups[gi]["weight_decay"] for gi in s["gis"]],
-                                self.ema_decay is not None)
-            s["table"] = torch.from_numpy(np.asarray(s["rows"], dtype=np.int64)).to(dev, non_blocking=True)
-            s["chunk_t"] = torch.from_numpy(np.asarray(s["chunks"], dtype=np.int32)).to(dev, non_blocking=True)
-            s["extras"] = self._upload(x, dev)
-        if self.max_grad_norm is None:
-            for s in sets:
-                b1, b2 = s["group"]["betas"]
-                _lib.check(lib.xvit_adamw_step(s["table"].data_ptr(), s["extras"].data_ptr(), s["chunk_t"].data_ptr(), len(s["chunks"]), s["lr"], b1, b2,
-                                               s["group"]["eps"], s["step"], 1.0, int(self.decoupled), self._ema_weight(s["step"]), cur.cuda_stream), "xvit_adamw_step")
+    def _fill(self, s, dev, eager):
+        """The xvit_adamw_extra table; capturable mode keeps its host mirror and the rates it was built from, for sync_lr()."""
+        s.groups = list(dict.fromkeys(s.gis))
+        s.lr, scales = self._scales(s)
+        x = self._extras_of(s.params, scales, [self.param_groups[gi]["weight_decay"] for gi in s.gis], self.ema_decay is not None)
+        s.extras = _upload(x, dev, eager)
+        if not eager:
+            s.extras_host, s.seen = x, self._seen(s)
+
+    def _launch_step(self, lib, s, by_value, stream):
+        group = self.param_groups[s.gis[0]]
+        b1, b2 = group["betas"]
+        tables = (s.table.data_ptr(), s.extras.data_ptr(), s.chunk_t.data_ptr(), s.n_chunks)
+        if by_value:
+            _lib.check(lib.xvit_adamw_step(*tables, s.lr, b1, b2, group["eps"], s.step + 1, 1.0, int(self.decoupled), self._ema_weight(s.step + 1), stream),
+                       "xvit_adamw_step")
         else:
-            rec = np.zeros(len(sets), dtype=_REC_DTYPE)
-            rec["step"] = [s["step"] - 1 for s in sets]          # the prologue advances it
-            rec["lr"] = [s["lr"] for s in sets]
-            records = torch.from_numpy(rec.view(np.int64).reshape(-1, _REC_WORDS)).to(dev, non_blocking=True)
-            total = sum(len(s["chunks"]) for s in sets)
-            partials = torch.empty(total, dtype=torch.float32, device=dev)
-            off = 0
-            for s in sets:
-                _lib.check(lib.xvit_grad_sqnorm_partials(s["table"].data_ptr(), s["chunk_t"].data_ptr(), len(s["chunks"]), partials.data_ptr() + 4 * off,
-                                                         cur.cuda_stream), "xvit_grad_sqnorm_partials")
-                off += len(s["chunks"])
-            for k, s in enumerate(sets):
-                b1, b2 = s["group"]["betas"]
-                state_ptr = records.data_ptr() + 8 * _REC_WORDS * k
-                _lib.check(lib.xvit_adam_prologue(partials.data_ptr(), total, state_ptr, self.max_grad_norm, b1, b2, 0, cur.cuda_stream), "xvit_adam_prologue")
-                _lib.check(lib.xvit_adamw_step_dev(s["table"].data_ptr(), s["extras"].data_ptr(), s["chunk_t"].data_ptr(), len(s["chunks"]), state_ptr, b1, b2,
-                                                   s["group"]["eps"], int(self.decoupled), self.ema_decay or 0.0, int(self.ema_warmup), cur.cuda_stream),
-                           "xvit_adamw_step_dev")
-            records.record_stream(cur); partials.record_stream(cur)
-            self._last_norm = records[0].view(torch.float32)[_F_NORM]
-        for s in sets:
-            for t in (s["table"], s["chunk_t"], s["extras"]):
-                t.record_stream(cur)
-        self._touched = [weakref.ref(g) for g in touched.values()]
-        self._unshadowed = unshadowed
-        self.mark_updated()
-
-    # ------------------------------------------------------------------------------------------------------------------------
-    # capturable mode
-    # ------------------------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def prepare(self):
-        """capturable=True: build the device tables of every launch set from the parameters that have a gradient NOW (allocation +
-        host-to-device copies: call it, or take one eager step, before a capture).  Later calls do nothing."""
-        if not self.capturable:
-            raise RuntimeError("xvit FusedAdamW.prepare: only for capturable=True")
-        if self._entries is not None:
-            return
-        sets, touched, unshadowed = {}, {}, []
-        for gi, group in enumerate(self.param_groups):
-            for i, p in enumerate(group["params"]):
-                if p.grad is None:
-                    continue
-                self._validate(p)
-                if not p.grad.is_contiguous():
-                    raise RuntimeError("xvit FusedAdamW(capturable=True): non-contiguous gradient")
-                step = int(self._state_of(p)["step"])
-                grp, _ = self._shadow_of(p)
-                if grp is not None:
-                    touched[id(grp)] = grp
-                else:
-                    unshadowed.append(p)
-                key = self._key(group, step)
-                if key not in sets:
-                    e = sets[key] = _Set()
-                    e.gi, e.params, e.idx, e.gis, e.chunks = gi, [], [], [], []
-                e = sets[key]
-                e.chunks.extend((len(e.params), c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
-                e.params.append(p); e.idx.append(i); e.gis.append(gi)
-        if not sets:
-            raise RuntimeError("xvit FusedAdamW.prepare: no parameter has a gradient yet (run one backward, or set the static .grad buffers, first)")
-        entries, off = list(sets.values()), 0
-        dev = entries[0].params[0].device
-        rec = np.zeros(len(entries), dtype=_REC_DTYPE)
-        for k, (key, e) in enumerate(sets.items()):
-            e.groups = list(dict.fromkeys(e.gis))
-            e.n_chunks, e.off = len(e.chunks), off
-            off += e.n_chunks
-            e.chunks = torch.from_numpy(np.asarray(e.chunks, dtype=np.int32)).to(dev)
-            e.table = torch.empty(len(e.params), 6, dtype=torch.int64, device=dev)
-            e.lr, scales = self._rates([self.param_groups[gi] for gi in e.groups])
-            scale_of = dict(zip(e.groups, scales))
-            e.extras_host = self._extras_of(e.params, self.state, [scale_of[gi] for gi in e.gis], [self.param_groups[gi]["weight_decay"] for gi in e.gis],
-                                            self.ema_decay is not None)
-            e.extras = self._upload(e.extras_host, dev)
-            e.seen = self._seen(e)
-            rec["step"][k], rec["lr"][k] = key[3], e.lr
-        self._records = torch.from_numpy(rec.view(np.int64).reshape(-1, _REC_WORDS)).to(dev)
-        self._partials = torch.empty(off, dtype=torch.float32, device=dev) if self._needs_norm else None
-        for k, e in enumerate(entries):
-            e.rec = self._records[k]
-            e.lr_view = e.rec.view(torch.float32)[_F_LR]
-        self._entries = entries
-        self._last_norm = self._records[0].view(torch.float32)[_F_NORM] if self._needs_norm else None
-        self._touched = [weakref.ref(g) for g in touched.values()]
-        self._unshadowed = unshadowed
-        self.rebind()
-
-    def _seen(self, e):
-        return tuple((float(self.param_groups[gi]["lr"]), float(self.param_groups[gi]["lr_scale"])) for gi in e.groups)
+            _lib.check(lib.xvit_adamw_step_dev(*tables, s.rec_ptr, b1, b2, group["eps"], int(self.decoupled), self.ema_decay or 0.0, int(self.ema_warmup),
+                                               stream), "xvit_adamw_step_dev")
 
     def sync_lr(self):
         """Bring the device in line with group["lr"] / group["lr_scale"]: while the groups of a set share one rate a change is ONE fill of the
         record (`lr_copies`); when they diverge the per-tensor scale column is rewritten with one host-to-device copy of the extras table,
         into the same addresses (`scale_copies`; a copy, so outside any capture).  Nothing is issued when nothing changed."""
-        for e in self._entries or ():
-            seen = self._seen(e)
-            if seen == e.seen:
+        for s in self._entries or ():
+            seen = self._seen(s)
+            if seen == s.seen:
                 continue
-            e.seen = seen
-            lr, scales = self._rates([self.param_groups[gi] for gi in e.groups])
-            if lr != e.lr:
-                e.lr_view.fill_(lr)
-                e.lr = lr
-                self.lr_copies += 1
-            scale_of = dict(zip(e.groups, scales))
-            column = np.asarray([scale_of[gi] for gi in e.gis], dtype=np.float32)
-            if not np.array_equal(column, e.extras_host["lr_scale"]):
-                e.extras_host["lr_scale"] = column
-                e.extras.copy_(torch.from_numpy(e.extras_host.view(np.int64).reshape(-1, 2)))
+            s.seen = seen
+            lr, column = self._scales(s)
+            self._sync_rate(s, lr)
+            if not np.array_equal(column, s.extras_host["lr_scale"]):
+                s.extras_host["lr_scale"] = column
+                s.extras.copy_(torch.from_numpy(s.extras_host.view(np.int64).reshape(-1, 2)))
                 self.scale_copies += 1
-
-    def enqueue(self):
-        """capturable mode: the launches of one step on the current stream and nothing else: the gradient norm (when one is taken), then one
-        prologue + step pair per launch set."""
-        lib = _lib.load()
-        stream = ops._stream()
-        if self._partials is not None:
-            for e in self._entries:
-                _lib.check(lib.xvit_grad_sqnorm_partials(e.table.data_ptr(), e.chunks.data_ptr(), e.n_chunks, self._partials.data_ptr() + 4 * e.off, stream),
-                           "xvit_grad_sqnorm_partials")
-        part, n_part = (self._partials.data_ptr(), self._partials.numel()) if self._partials is not None else (None, 0)
-        max_norm = self.max_grad_norm if self.max_grad_norm is not None else math.inf
-        for e in self._entries:
-            group = self.param_groups[e.gi]
-            b1, b2 = group["betas"]
-            _lib.check(lib.xvit_adam_prologue(part, n_part, e.rec.data_ptr(), max_norm, b1, b2, int(self.skip_nonfinite), stream), "xvit_adam_prologue")
-            _lib.check(lib.xvit_adamw_step_dev(e.table.data_ptr(), e.extras.data_ptr(), e.chunks.data_ptr(), e.n_chunks, e.rec.data_ptr(), b1, b2, group["eps"],
-                                               int(self.decoupled), self.ema_decay or 0.0, int(self.ema_warmup), stream), "xvit_adamw_step_dev")
 
     # ------------------------------------------------------------------------------------------------------------------------
     # the average
@@ -678,31 +579,23 @@ class FusedAdamW(FusedAdam):
         cur = torch.cuda.current_stream()
         if self._entries is not None:
             self.check_addresses(grads=False)
-            for e in self._entries:
-                _lib.check(lib.xvit_ema_swap(e.table.data_ptr(), e.extras.data_ptr(), e.chunks.data_ptr(), e.n_chunks, cur.cuda_stream), "xvit_ema_swap")
-        else:
+            sets = self._entries
+        else:                             # eager: one set of every parameter that has an average, p standing in for the gradient
             params = [p for g in self.param_groups for p in g["params"] if p in self.state and "ema" in self.state[p]]
             if not params:
                 raise RuntimeError("xvit FusedAdamW.ema_weights: no parameter has an average yet (take a step first)")
-            rows, chunks, touched, unshadowed = [], [], {}, []
-            for t, p in enumerate(params):
-                st = self.state[p]
-                grp, sh = self._shadow_of(p)
-                if grp is not None:
-                    touched[id(grp)] = grp
-                else:
-                    unshadowed.append(p)
-                rows.append((p.data_ptr(), p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), sh.data_ptr() if sh is not None else 0, p.numel()))
-                chunks.extend((t, c) for c in range((p.numel() + CHUNK - 1) // CHUNK))
-            dev = params[0].device
-            table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev, non_blocking=True)
-            chunk_t = torch.from_numpy(np.asarray(chunks, dtype=np.int32)).to(dev, non_blocking=True)
-            extras = self._upload(self._extras_of(params, self.state, 1.0, 0.0, True), dev)
-            _lib.check(lib.xvit_ema_swap(table.data_ptr(), extras.data_ptr(), chunk_t.data_ptr(), len(chunks), cur.cuda_stream), "xvit_ema_swap")
-            for t in (table, chunk_t, extras):
-                t.record_stream(cur)
-            self._touched = [weakref.ref(g) for g in touched.values()]
-            self._unshadowed = unshadowed
+            s, marks = _Set(), ({}, [])
+            for p in params:
+                s.add(self._row(p, p, marks), p)
+            s.upload(params[0].device, True)
+            s.extras = _upload(self._extras_of(params, 1.0, 0.0, True), params[0].device, True)
+            self._mark(marks)
+            sets = [s]
+        for s in sets:
+            _lib.check(lib.xvit_ema_swap(s.table.data_ptr(), s.extras.data_ptr(), s.chunk_t.data_ptr(), s.n_chunks, cur.cuda_stream), "xvit_ema_swap")
+            if self._entries is None:
+                for t in (s.table, s.chunk_t, s.extras):
+                    t.record_stream(cur)
         called = getattr(self, "_opt_called", False)
         self.mark_updated()
         self._opt_called = called     # an exchange is not a step
@@ -732,35 +625,13 @@ class FusedAdamW(FusedAdam):
     # ------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def load_state_dict(self, state_dict):
-        """Accepts a state dict of either mode, of FusedAdam or of torch.optim.Adam / AdamW.  Once the capturable tables exist the values are
-        copied INTO the existing moment and average buffers and device counters.  A state without `ema` starts the average at the current p.
-        As with every torch optimizer the saved groups' hyper-parameters replace the current ones; a saved group that has no `lr_scale` keeps the
-        one this optimizer was built with."""
-        old = {p: self.state[p] for e in self._entries or () for p in e.params}
+        """As FusedAdam.load_state_dict; a state without `ema` starts the average at the current p.  As with every torch optimizer the saved
+        groups' hyper-parameters replace the current ones; a saved group that has no `lr_scale` (FusedAdam, torch.optim.AdamW) keeps the one
+        this optimizer was built with."""
         scales = [g["lr_scale"] for g in self.param_groups]
-        torch.optim.Optimizer.load_state_dict(self, state_dict)
+        super().load_state_dict(state_dict)
         for group, s in zip(self.param_groups, scales):
-            group.setdefault("lr_scale", s)        # a saved group without one (FusedAdam, torch.optim.AdamW) keeps the constructed scale
-        for p, st in self.state.items():
-            if "step" in st:
-                st["step"] = int(st["step"])
-            if self.ema_decay is not None and "exp_avg" in st and "ema" not in st:
-                st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
-        for k, e in enumerate(self._entries or ()):
-            steps = set()
-            for i, p in enumerate(e.params):
-                new = self.state.get(p)
-                if not new or "exp_avg" not in new:
-                    raise ValueError(f"xvit FusedAdamW.load_state_dict: no state for {self._describe(e, i)}, which the capturable tables hold")
-                keep = old[p]
-                for name in ("exp_avg", "exp_avg_sq") + (("ema",) if self.ema_decay is not None else ()):
-                    keep[name].copy_(new[name])
-                keep["step"] = new["step"]
-                steps.add(new["step"])
-                self.state[p] = keep
-            if len(steps) != 1:
-                raise ValueError(f"xvit FusedAdamW(capturable=True) keeps one step count per launch set; the loaded state has steps {sorted(steps)} in one set")
-            self._records[k, 0].fill_(steps.pop())
+            group.setdefault("lr_scale", s)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Oracle, float32 mirror, launchers and gate for the AdamW kernels (csrc/misc.hip: adamw_kernel<FROM_RECORD, DECOUPLED>, ema_swap_kernel;
+"""Oracle, float32 mirror, launchers and gate for the AdamW kernels (csrc/misc.hip: adam_kernel<FROM_RECORD, ADAM_COUPLED | ADAM_DECOUPLED>, ema_swap_kernel;
 xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap), in the manner of _optim_check.py, whose arenas, sentinels, NaN guards behind g,
 `where`, SIZES, operands and bounds are reused.
 
@@ -6,7 +6,7 @@ Arenas.  One more arena kind, `e` (the average), laid out like p / m / v with se
 ema = NULL), "all", "alternate" (tensors 0, 2, 4, ... have one).  A tensor without an average still owns its slot of the `e` arena, which
 then holds the sentinel throughout and is compared as a guard: an average written for the neighbour of a null-ema tensor shows there.
 Placements: those of _optim_check with the average 16-byte aligned, and "ema 4 bytes off", which must select the scalar path (with an
-average; without one the pointer is NULL and the 16-byte path stays).  `vec_ok` mirrors adamw_vec_ok and every launch asserts it.
+average; without one the pointer is NULL and the 16-byte path stays).  `vec_ok` mirrors adam_vec_ok(t, ema) and every launch asserts it.
 
 Per-tensor numbers.  Every tensor t has its own lr_scale s_t and weight decay wd_t (`HyperW.scales`, `.wds`, cycled over the tensors, 0
 among both).  Uniform per tensor, formed in fp32: a = fl(L s_t), lr_t = fl(lr s_t) with L = lr / bc1 as the host computes it in double.
@@ -59,7 +59,7 @@ EMA_MODES = ("none", "all", "alternate")
 
 
 def vec_ok(p, g, m, v, sh, ema):
-    """adamw_vec_ok on byte addresses (sh / ema = 0: none)."""
+    """adam_vec_ok(t, ema) on byte addresses (sh / ema = 0: none)."""
     return X.vec_ok(p, g, m, v, sh) and (ema & 15) == 0
 
 
@@ -254,7 +254,7 @@ FAULTS = ("decay applied after the update", "decay with lr / bc1", "lr_scale lef
 
 
 def adamw_mirror(case, h, fault=None):
-    """adamw_kernel in float32 on the CPU (every product and sum rounded on its own) -> p', m', v', e' (fp32)."""
+    """adam_kernel<., ADAM_COUPLED | ADAM_DECOUPLED> in float32 on the CPU (every product and sum rounded on its own) -> p', m', v', e' (fp32)."""
     o = X.adam_operands(case.tier, case.sizes)
     t = lambda x: torch.tensor(x, dtype=torch.float32)   # noqa: E731
     p, g, m, v = o["p"], o["g"], o["m"], o["v"]
@@ -387,7 +387,7 @@ def device_case(case, h):
     rows = case.table(base)
     ex = case.extras(base["e"], h)
     paths = [vec_ok(*r[:5], int(x["ema"])) for r, x in zip(rows, ex)]
-    assert paths == case.vec_t, f"{case}: the mirror of adamw_vec_ok picks {paths} (True: 16-byte path), the placement was built for {case.vec_t}"
+    assert paths == case.vec_t, f"{case}: the mirror of adam_vec_ok(t, ema) picks {paths} (True: 16-byte path), the placement was built for {case.vec_t}"
     d["table"] = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
     d["extras"] = torch.from_numpy(ex.view(np.int64).reshape(-1, 2).copy()).to(dev)
     d["chunks"] = torch.from_numpy(np.asarray(case.chunks, dtype=np.int32).reshape(-1, 2)).to(dev)

@@ -1,5 +1,5 @@
 """Oracle, launchers, launch-geometry mirror and gate for the fused Adam kernels, the gradient-norm partials and the step prologue
-(csrc/misc.hip: adam_kernel<false|true>, grad_sqnorm_kernel, adam_prologue_kernel), for the dropout mask (csrc/xvit_common.h hash32 /
+(csrc/misc.hip: adam_kernel<false|true, ADAM_PLAIN>, grad_sqnorm_kernel, adam_prologue_kernel), for the dropout mask (csrc/xvit_common.h hash32 /
 draw24 / Dropout::keep, xvit_dropout) and for the casts and the row bookkeeping (xvit_cast_f32_bf16, xvit_add_cast_f32_bf16,
 xvit_rows_combine).
 

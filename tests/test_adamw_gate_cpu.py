@@ -1,4 +1,4 @@
-"""The gate of the AdamW checks (tests/_adamw_check.py) has teeth, on the CPU: the float32 mirror of adamw_kernel stays inside every stated
+"""The gate of the AdamW checks (tests/_adamw_check.py) has teeth, on the CPU: the float32 mirror of adam_kernel's per-tensor modes stays inside every stated
 bound over the inputs the GPU tests use and sets the constants table of the docstring, and every planted fault is caught.
 
   fault                                                  caught by

@@ -1,7 +1,7 @@
 """GPU: xvit_adamw_step, xvit_adamw_step_dev and xvit_ema_swap element by element (oracle, bounds and arenas: tests/_adamw_check.py).
 
-Against the existing kernel: coupled, every lr_scale 1, one decay, no average must leave the arenas bit-identical to xvit_adam_step /
-xvit_adam_step_dev.  Against the oracle: every placement x {coupled, decoupled} x {no average, all, every other tensor} x every
+Against the plain mode of the same template (adam_kernel<., ADAM_PLAIN>): ADAM_COUPLED with every lr_scale 1, one decay and no average must
+leave the arenas bit-identical to xvit_adam_step / xvit_adam_step_dev, which guards the extras table and the mode dispatch.  Against the oracle: every placement x {coupled, decoupled} x {no average, all, every other tensor} x every
 hyper-parameter set of both tiers (52 launches per case), natural and shuffled chunk lists in turn."""
 import itertools
 import math
