@@ -17,7 +17,7 @@ from .model import Block, Encoder, Mlp, MultiHeadAttention  # noqa: F401
 from .modelv3 import ModelVIT, Transformer  # noqa: F401
 from .model_cross import (Attention, CrossAttention, CrossAttentionBlock, FeedForward, ModelCross,  # noqa: F401
                           MultiScaleBlock, PreNorm, SelfAttentionBlock)
-from .metrics import BinaryEpochMetrics  # noqa: F401
+from .metrics import BinaryEpochMetrics, EpochMetrics  # noqa: F401
 from . import interpret  # noqa: F401   (attention maps and rollout: xvit.interpret.attention_maps)
 from . import augment  # noqa: F401     (the augmenting input stage: xvit.augment.VolumeAugment)
 from .augment import AugmentParams, VolumeAugment  # noqa: F401

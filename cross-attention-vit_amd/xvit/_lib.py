@@ -57,6 +57,13 @@ STATS_WINDOW_LO, STATS_WINDOW_BINS = 32768, 32768      # XVIT_STATS_WINDOW_*: th
 NORM_STATS_ONLY, NORM_ZSCORE, NORM_WINDOW = 0, 1, 2    # XVIT_NORM_*
 MAE_MAX_PD = 8192                                      # XVIT_MAE_MAX_PD: the largest patch (voxels) xvit_mae_loss_fwd holds in LDS
 TOKEN_SELECT_MAX_P = 8192                              # XVIT_TOKEN_SELECT_MAX_P: the longest sequence xvit_token_select_draw ranks in LDS
+EPOCH_MAX_C, EPOCH_MAX_B = 64, 8192                    # XVIT_EPOCH_MAX_C, XVIT_EPOCH_MAX_B: the limits of xvit_epoch_metrics_update
+EPOCH_STATE_HEAD = 8                                   # XVIT_EPOCH_STATE_HEAD: int64 counters in front of the C x C confusion
+EPOCH_STORED, EPOCH_SEEN, EPOCH_STEPS, EPOCH_IGNORED, EPOCH_NONFINITE, EPOCH_OVERFLOW = 0, 1, 2, 3, 4, 5   # XVIT_EPOCH_*: the counters
+EPOCH_RANK_PASS = 1024                                 # XVIT_EPOCH_RANK_PASS: sorted elements per pass of xvit_epoch_rank_stats' walk
+EPOCH_RANK_MAX_N = 65535                               # XVIT_EPOCH_RANK_MAX_N: the largest epoch with bootstrap replicates
+EPOCH_RANK_NSTAT = 3                                   # XVIT_EPOCH_RANK_NSTAT
+EPOCH_RANK_U2, EPOCH_RANK_WPOS, EPOCH_RANK_WNEG = 0, 1, 2   # XVIT_EPOCH_RANK_*
 
 
 class MixConfig(C.Structure):
@@ -119,6 +126,8 @@ SIGNATURES = {
     "xvit_dropout": [vp, vp, i32, i64, f32, u64, vp],
     "xvit_cu_trace": [vp, i32, i32, vp],
     "xvit_binary_metrics_step": [vp, i64, vp, i32, i32, vp, vp],
+    "xvit_epoch_metrics_update": [vp, i64, vp, i32, i32, vp, vp, vp, i64, vp, vp],
+    "xvit_epoch_rank_stats": [vp, vp, vp, vp, i64, vp, i64, i32, i32, u64, vp, vp, vp, vp],
     "xvit_mean_ce": [vp, vp, f32, vp, vp, vp, i32, i32, i32, vp],
     "xvit_mix_draw": [C.POINTER(MixConfig), vp, i32, i32, i32, i32, u64, vp],
     "xvit_mix_apply": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i64, i64, vp],
@@ -141,7 +150,7 @@ SIGNATURES = {
 }
 EXPORTS = sorted(list(SIGNATURES) + ["xvit_version", "xvit_last_error_string", "xvit_gemm_workspace_bytes", "xvit_linear_f32_workspace_bytes",
                                     "xvit_colsum_workspace_bytes", "xvit_layernorm_bwd_workspace_bytes", "xvit_patch_embed_wgrad_workspace_bytes", "xvit_attn_fp8_workspace_bytes",
-                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes"])
+                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes", "xvit_epoch_rank_stats_max_n"])
 
 _lib = None
 
@@ -174,6 +183,8 @@ def load() -> C.CDLL:
         lib.xvit_patch_embed_wgrad_workspace_bytes.restype = C.c_int64
         lib.xvit_volume_stats_workspace_bytes.argtypes = [i32]
         lib.xvit_volume_stats_workspace_bytes.restype = C.c_int64
+        lib.xvit_epoch_rank_stats_max_n.argtypes = []
+        lib.xvit_epoch_rank_stats_max_n.restype = C.c_int64
         lib.xvit_version.restype = C.c_int
         lib.xvit_last_error_string.restype = C.c_char_p
         _lib = lib

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as XF
-from .metrics import EpochStatsMixin
+from .metrics import EpochStatsMixin, epoch_metrics_config
 
 try:  # the reference derives ModelCross from lightning.LightningModule (model_cross.py:152)
     import lightning as _L  # type: ignore
@@ -356,6 +356,9 @@ class ModelCross(EpochStatsMixin, _Base):
         self.patch_dropout_shared = bool(getattr(config, "patch_dropout_shared", False))
         if not 0.0 <= self.patch_dropout < 1.0:
             raise ValueError(f"patch_dropout must be in [0, 1), got {self.patch_dropout}")
+        # epoch statistics (metrics.EpochStatsMixin): "reference" = the reference's means of per-step values for two classes, "pooled" = the
+        # pooled epoch values of EpochMetrics, with epoch_metrics_bootstrap replicates; more than two classes are always pooled
+        self.epoch_metrics, self.epoch_metrics_bootstrap = epoch_metrics_config(config)
         # int32 [M, B, K]: the patch indices the last forward kept (None: it kept them all).  The tensor a capture leaves here is the
         # graph's own and follows its replays; any later forward call replaces the attribute, not that tensor
         self.last_token_keep = None

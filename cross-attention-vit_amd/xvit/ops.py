@@ -1023,3 +1023,46 @@ def volume_stats(src, config, stats, workspace, params=None):
             raise TypeError(str(e)) from None
         raise
     return stats
+
+
+def epoch_metrics_update(logits, labels, scores, labels32, preds, state):
+    """xvit_epoch_metrics_update (include/xvit.h): append the step's softmax rows, labels and argmax to the epoch buffers at the device-side
+    cursor state[0] and fold it into the integer confusion matrix behind the state head.  logits fp32 [B, C] (rows contiguous), labels
+    int64 [B]; scores fp32 [cap, C], labels32 / preds int32 [cap], state int64 [EPOCH_STATE_HEAD + C * C].  One launch, no host read."""
+    B, Cn = logits.shape
+    cap = scores.shape[0]
+    assert logits.dtype == torch.float32 and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == B
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape[1] == Cn
+    assert labels32.dtype == torch.int32 and preds.dtype == torch.int32 and labels32.is_contiguous() and preds.is_contiguous()
+    assert labels32.numel() == cap and preds.numel() == cap
+    assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() == _lib.EPOCH_STATE_HEAD + Cn * Cn
+    _run("epoch_metrics_update", B * Cn * 8.0, "byte",
+         lambda: _lib.load().xvit_epoch_metrics_update(_ptr(logits), _rows2d(logits), _ptr(labels), B, Cn, _ptr(scores), _ptr(labels32), _ptr(preds), cap,
+                                                       _ptr(state), _stream()),
+         "xvit_epoch_metrics_update")
+
+
+def epoch_rank_stats_max_n() -> int:
+    """xvit_epoch_rank_stats_max_n: the largest epoch (samples) xvit_epoch_rank_stats takes with bootstrap replicates."""
+    return int(_lib.load().xvit_epoch_rank_stats_max_n())
+
+
+def epoch_rank_stats(scores, labels32, preds, perm, n_dev, n_max, R, seed):
+    """xvit_epoch_rank_stats (include/xvit.h): for replicate 0 (every sample once) and R bootstrap replicates, per class: the tie-aware
+    pair count u2, the positive / negative weight, the average precision and the confusion row.  perm int64 [C, >= n_max]: per class the
+    samples in descending score order; n_dev: a one-element int64 device tensor (or view) holding the sample count, n_max its host bound.
+    Returns (ranks int64 [R + 1, C, 3], ap fp64 [R + 1, C], conf int64 [R + 1, C, C])."""
+    Cn = scores.shape[1]
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and labels32.dtype == torch.int32 and preds.dtype == torch.int32
+    assert labels32.is_contiguous() and preds.is_contiguous() and min(scores.shape[0], labels32.numel(), preds.numel()) >= n_max
+    assert perm.dtype == torch.int64 and perm.dim() == 2 and perm.shape[0] == Cn and perm.stride(1) == 1 and perm.shape[1] >= n_max
+    assert n_dev.dtype == torch.int64 and n_dev.numel() >= 1
+    dev = scores.device
+    ranks = torch.empty(R + 1, Cn, _lib.EPOCH_RANK_NSTAT, dtype=torch.int64, device=dev)
+    ap = torch.empty(R + 1, Cn, dtype=torch.float64, device=dev)
+    conf = torch.empty(R + 1, Cn, Cn, dtype=torch.int64, device=dev)
+    _run("epoch_rank_stats", (R + 1) * Cn * float(n_max) * 16.0, "byte",
+         lambda: _lib.load().xvit_epoch_rank_stats(_ptr(scores), _ptr(labels32), _ptr(preds), _ptr(perm), perm.stride(0), _ptr(n_dev), int(n_max), Cn, int(R),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ranks), _ptr(ap), _ptr(conf), _stream()),
+         "xvit_epoch_rank_stats")
+    return ranks, ap, conf

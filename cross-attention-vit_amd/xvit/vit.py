@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from . import functional as XF
 from .cross_vit import Attention, FeedForward, PreNorm, _Base, _lin, _p
-from .metrics import EpochStatsMixin
+from .metrics import EpochStatsMixin, epoch_metrics_config
 
 
 class _NoDrop(nn.Module):
@@ -55,6 +55,7 @@ class ModelVIT(EpochStatsMixin, _Base):
         self.patch_size = tuple(config.patch_size)
         for k in ("lr", "weight_decay", "optim_params"):
             setattr(self, k, getattr(config, k))
+        self.epoch_metrics, self.epoch_metrics_bootstrap = epoch_metrics_config(config)      # metrics.EpochStatsMixin
         self.pos_embedding = nn.Parameter(torch.empty(1, P * config.num_modalities + 1, d))
         self.patch_to_embedding = _lin(pd, d)
         self.cls_token = nn.Parameter(torch.empty(1, 1, d))

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 314 /* 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 315 /* 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -626,6 +626,61 @@ int xvit_dropout(const void* x, void* y, int dtype, int64_t n, float p, uint64_t
    so state[6+k] / state[4] is the batch-size-weighted epoch mean Lightning logs for on_epoch=True.  B <= 8192. */
 #define XVIT_METRIC_STATE 16
 int xvit_binary_metrics_step(const float* logits, int64_t ld, const int64_t* labels, int B, int C, double* state, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Pooled epoch metrics for any number of classes (csrc/epoch_metrics.hip).  The entry point above keeps batch-size-weighted means of
+ * per-step values, as the reference logs them; the pair below keeps the epoch's scores on the device and yields the POOLED values a
+ * paper reports (confusion-matrix metrics, one-vs-rest AUROC and average precision over the whole fold) with percentile-bootstrap
+ * replicates, all from integer rank statistics.
+ *
+ * xvit_epoch_metrics_update: one single-workgroup launch per step, no host read, capturable (the cursor lives on the device: every
+ * replay of a captured launch appends).  logits fp32 [B, C] (row stride ld >= C), labels int64 [B]; 2 <= C <= XVIT_EPOCH_MAX_C,
+ * 1 <= B <= XVIT_EPOCH_MAX_B, 1 <= cap < 2^31.  Caller-owned epoch buffers: scores fp32 [cap, C], labels32 int32 [cap], preds int32 [cap],
+ * state int64 [XVIT_EPOCH_STATE_HEAD + C*C] (8-byte aligned, zeroed by the caller at the start of an epoch):
+ *    state[XVIT_EPOCH_STORED]     rows stored so far = the cursor        state[XVIT_EPOCH_SEEN]      rows handed in (sum of B)
+ *    state[XVIT_EPOCH_STEPS]      launches                               state[XVIT_EPOCH_IGNORED]   rows whose label is outside [0, C)
+ *    state[XVIT_EPOCH_NONFINITE]  rows with a NaN or infinite logit      state[XVIT_EPOCH_OVERFLOW]  kept rows that did not fit under cap
+ *    state[XVIT_EPOCH_STATE_HEAD + label*C + pred]                       the confusion counts of the kept rows
+ * Per row, in this order: a label outside [0, C) counts in IGNORED only; otherwise a non-finite logit counts in NONFINITE only; otherwise
+ * the row is KEPT: pred = argmax (first maximum on ties), confusion[label][pred] += 1, and the row is appended at the cursor, in row
+ * order, while the cursor is below cap: scores[c] = expf(l_c - max) / sum_k expf(l_k - max) with the sum taken in class order (for C = 2
+ * the expression of xvit_binary_metrics_step, so saturated probabilities tie as there), labels32 = label, preds = pred.  A kept row past
+ * cap counts in the confusion and in OVERFLOW and is not stored.  Integer counters and a row-order compaction: the buffers after two
+ * updates equal those after one update of the concatenated batch.  All stores are plain vector stores by the one workgroup.
+ *
+ * xvit_epoch_rank_stats: epoch end; grid (R + 1 replicates) x (C classes), one workgroup each.  n = min(*n_dev, n_max) is read on the
+ * device (n_dev: the address of state[XVIT_EPOCH_STORED] or of any int64 count); n_max, the host's bound, sizes the LDS.  perm int64
+ * [C, ldp]: row c lists the samples 0 .. n - 1 in descending order of scores[:, c] (any order among equal scores: the results do not
+ * depend on it; an index outside [0, n) carries no weight and is never dereferenced).
+ *    Replicate 0 weighs every sample once (the point estimate).  Replicate r >= 1 draws n samples with replacement: draw k = 0 .. n - 1
+ *    lands on sample (uint64(hash32(seed + r * 0x9E3779B97F4A7C15, k)) * n) >> 32, hash32 being the dropout hash of xvit_dropout; the seed
+ *    sum wraps at 2^64.  The multiplicities w_r[i] are indexed by sample, so all classes of a replicate share one resample.  They are
+ *    16-bit LDS counters: with R > 0, n_max <= XVIT_EPOCH_RANK_MAX_N = 65 535, which both fits the 160 KiB of LDS and keeps a counter from
+ *    overflowing (a sample can be drawn at most n times); xvit_epoch_rank_stats_max_n returns the limit.  R = 0 has no limit but 2^31 - 1.
+ *    Per (r, c), with "positive" = label c, over the tie groups of the sorted order (gp / gn: the group's positive / negative weight;
+ *    cp / cn: cumulative down to and including the group):
+ *      ranks[r, c, XVIT_EPOCH_RANK_U2]   = sum_groups gp (2 (wneg - cn) + gn)       exact;  AUROC = 0.5 u2 / (wpos wneg)
+ *      ranks[r, c, XVIT_EPOCH_RANK_WPOS], [.., XVIT_EPOCH_RANK_WNEG]                 total positive / negative weight
+ *      ap[r, c]   = (sum_{groups, gp > 0} (double)(gp cp) / (double)(cp + cn)) / wpos   fp64, summed in a fixed order (the same bits at
+ *                   every run and for every order among equal scores); 0 when wpos = 0
+ *      conf[r, c, p] = sum_i w_r[i] [label_i = c] [pred_i = p]                       the replicate's confusion row
+ *    The walk takes XVIT_EPOCH_RANK_PASS sorted elements per pass.  n_max = 0 launches nothing and zeroes the outputs.
+ * Argument errors, raised before any launch: null pointers, C outside 2..64, B outside 1..8192, ld < C, cap < 1 or >= 2^31, R outside 0..65534, n_max < 0 or >= 2^31,
+ * n_max > XVIT_EPOCH_RANK_MAX_N with R > 0, ldp < n_max, misaligned state or outputs.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_EPOCH_MAX_C 64
+#define XVIT_EPOCH_MAX_B 8192
+#define XVIT_EPOCH_STATE_HEAD 8
+enum { XVIT_EPOCH_STORED = 0, XVIT_EPOCH_SEEN = 1, XVIT_EPOCH_STEPS = 2, XVIT_EPOCH_IGNORED = 3, XVIT_EPOCH_NONFINITE = 4, XVIT_EPOCH_OVERFLOW = 5 };
+#define XVIT_EPOCH_RANK_PASS 1024
+#define XVIT_EPOCH_RANK_MAX_N 65535
+#define XVIT_EPOCH_RANK_NSTAT 3
+enum { XVIT_EPOCH_RANK_U2 = 0, XVIT_EPOCH_RANK_WPOS = 1, XVIT_EPOCH_RANK_WNEG = 2 };
+int xvit_epoch_metrics_update(const float* logits, int64_t ld, const int64_t* labels, int B, int C, float* scores, int32_t* labels32, int32_t* preds,
+                              int64_t cap, int64_t* state, xvit_stream_t stream);
+int64_t xvit_epoch_rank_stats_max_n(void);
+int xvit_epoch_rank_stats(const float* scores, const int32_t* labels32, const int32_t* preds, const int64_t* perm, int64_t ldp, const int64_t* n_dev,
+                          int64_t n_max, int C, int R, uint64_t seed, int64_t* ranks, double* ap, int64_t* conf, xvit_stream_t stream);
 
 /* Diagnostic (no reference counterpart): out[2*b] = XCC (XCD) id and out[2*b+1] = HW_ID register of the CU
    that ran workgroup b of an `nblocks`-block launch on `stream`; every block lingers `linger_us` so the
