@@ -8,6 +8,7 @@ own nn.Module signatures (vsahni3/cross-attention-ViT: model_cross.py, model.py)
     xvit.interpret.relevance_maps(model, img)        # class-specific relevance (one backward, eval mode)
     xvit.interpret.input_attributions(model, img)    # voxel attributions: gradient, grad x input, integrated gradients (eval mode)
     xvit.augment.VolumeAugment(img_size)(raw)        # device-side pad / crop + random affine + intensity augmentation of raw volumes
+    xvit.augment.ContrastAugment()(img)              # random Gaussian blur, bias field and gamma on the augmented volumes, one fused kernel
     xvit.MaskedVolumeModel(config)                   # masked-volume (MAE) pretraining of a ModelCross encoder
     config.mixup_alpha / config.cutmix_alpha         # Mixup / CutMix with a soft-target loss in ModelCross.train() (fine-tuning)
 """
@@ -20,5 +21,5 @@ from .model_cross import (Attention, CrossAttention, CrossAttentionBlock, FeedFo
 from .metrics import BinaryEpochMetrics, EpochMetrics  # noqa: F401
 from . import interpret  # noqa: F401   (attention maps and rollout: xvit.interpret.attention_maps)
 from . import augment  # noqa: F401     (the augmenting input stage: xvit.augment.VolumeAugment)
-from .augment import AugmentParams, VolumeAugment  # noqa: F401
+from .augment import AugmentParams, ContrastAugment, ContrastParams, VolumeAugment  # noqa: F401
 from .mae import MaskedVolumeModel  # noqa: F401   (masked-volume pretraining around a ModelCross encoder)

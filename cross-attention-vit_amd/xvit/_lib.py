@@ -47,6 +47,15 @@ class AugmentConfig(C.Structure):
 AUG_NPARAM = 32   # XVIT_AUG_NPARAM
 
 
+class ContrastConfig(C.Structure):
+    """struct xvit_contrast_config (include/xvit.h)."""
+    _fields_ = [("blur_prob", f32), ("blur_sigma_range", f32 * 2), ("blur_isotropic", i32), ("bias_prob", f32), ("bias_coeff", f32),
+                ("gamma_prob", f32), ("log_gamma_range", f32 * 2), ("gamma_window", f32 * 2)]
+
+
+CON_NPARAM, CON_MAX_RADIUS = 32, 6   # XVIT_CON_NPARAM, XVIT_CON_MAX_RADIUS
+
+
 class NormConfig(C.Structure):
     """struct xvit_norm_config (include/xvit.h)."""
     _fields_ = [("mode", i32), ("clip", i32), ("foreground_above", f32), ("q_lo", f32), ("q_hi", f32)]
@@ -135,6 +144,8 @@ SIGNATURES = {
     "xvit_resize_pad_crop_i16": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_augment_draw": [C.POINTER(AugmentConfig), vp, i32, i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp],
     "xvit_augment_apply": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "xvit_contrast_draw": [C.POINTER(ContrastConfig), vp, i32, u64, vp, i32, vp],
+    "xvit_contrast_apply": [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp],
     "xvit_volume_stats": [vp, i32, i32, i64, C.POINTER(NormConfig), vp, vp, vp, i64, vp],
     "xvit_set_option": [C.c_char_p, i32],
     "xvit_set_dropout_epoch": [C.c_void_p],

@@ -9,6 +9,10 @@
     aug.last_stats                   # VolumeStats: n, n_w, mean, std, lo, hi, min, max of every volume's foreground
     xvit.augment.volume_stats(raw)   # the statistics alone
 
+    con = xvit.augment.ContrastAugment(blur_prob=.2, bias_prob=.2, gamma_prob=.3, seed=0)      # a second stage behind the first
+    img = con(aug(raw))              # Gaussian blur, bias field, gamma: one fused kernel, a NEW tensor of the same shape
+    con.last_params                  # ContrastParams: the table this call drew
+
 It stands where the reference's loader runs MONAI's random transforms on CPU workers (dataset_ucsf.py:94-113).  The transform set and its
 ranges are this project's own; parity with MONAI's random stream is not claimed.  All modalities of a sample share one spatial transform
 (they are co-registered scans); intensity transforms are drawn per volume.  pad_value is in SOURCE units: it passes through the intensity
@@ -301,3 +305,158 @@ class VolumeAugment(torch.nn.Module):
         if self.normalize is not None:
             self.last_stats = self._normalise(raw, self.last_params.table)
         return self.apply(raw, self.last_params)
+
+
+# ---------------------------------------------------------------------------------------------------------------- contrast stage
+# slots of a contrast record: enum XVIT_CON_* of include/xvit.h, by name
+CON_NPARAM, CON_MAX_RADIUS = _lib.CON_NPARAM, _lib.CON_MAX_RADIUS
+CON_FLAGS, CON_SIGMA, CON_RADIUS, CON_GAMMA, CON_WINDOW_LO, CON_WINDOW_HI, CON_BIAS = 0, 1, 4, 7, 8, 9, 10
+CON_U_BLUR, CON_U_BIAS, CON_U_GAMMA, CON_BETA = 19, 20, 21, 22
+CON_FLAG_BLUR, CON_FLAG_BIAS, CON_FLAG_GAMMA = 1, 2, 4
+CON_BIAS_TERMS = ("z", "y", "x", "zz", "yy", "xx", "zy", "zx", "yx")     # the order of the nine bias coefficients
+
+
+class ContrastParams:
+    """Named views of a contrast table [B, M, 32] (fp32): flags, sigma, radius, gamma, window, bias, raw draws.  Every attribute but the
+    three booleans is a view: writing through it edits the table."""
+
+    def __init__(self, table: torch.Tensor):
+        if table.dtype != torch.float32 or table.dim() != 3 or table.shape[2] != CON_NPARAM:
+            raise ValueError(f"ContrastParams: need an fp32 [B, M, {CON_NPARAM}] table, got {table.dtype} {tuple(table.shape)}")
+        self.table = table
+
+    @classmethod
+    def identity(cls, B, M, device=None, window=(0.0, 1.0)):
+        """Copy records: flags 0, gamma 1."""
+        t = torch.zeros(B, M, CON_NPARAM, dtype=torch.float32)
+        t[..., CON_GAMMA] = 1.0
+        t[..., CON_WINDOW_LO], t[..., CON_WINDOW_HI] = float(window[0]), float(window[1])
+        return cls(t.to(device) if device is not None else t)
+
+    flags = property(lambda s: s.table[..., CON_FLAGS])
+    sigma = property(lambda s: s.table[..., CON_SIGMA:CON_SIGMA + 3])          # z, y, x
+    radius = property(lambda s: s.table[..., CON_RADIUS:CON_RADIUS + 3])
+    gamma = property(lambda s: s.table[..., CON_GAMMA])
+    window = property(lambda s: s.table[..., CON_WINDOW_LO:CON_WINDOW_HI + 1])
+    bias = property(lambda s: s.table[..., CON_BIAS:CON_BIAS + 9])             # CON_BIAS_TERMS
+    draws = property(lambda s: s.table[..., CON_U_BLUR:CON_U_GAMMA + 1])       # the uniforms behind the blur, bias, gamma decisions
+    beta = property(lambda s: s.table[..., CON_BETA])
+
+    def _flag(self, bit):
+        return (self.table[..., CON_FLAGS].to(torch.int32) & bit).bool()
+
+    blurred = property(lambda s: s._flag(CON_FLAG_BLUR))
+    biased = property(lambda s: s._flag(CON_FLAG_BIAS))
+    gamma_on = property(lambda s: s._flag(CON_FLAG_GAMMA))
+
+    def clone(self):
+        return ContrastParams(self.table.clone())
+
+
+class ContrastAugment(torch.nn.Module):
+    """Random Gaussian blur (per-axis sigma in voxels), smooth multiplicative bias field (order-2 polynomial in the normalised voxel
+    coordinates, exponentiated) and gamma (g = exp(beta), inside gamma_window only), drawn per (sample, modality) and applied in this fixed
+    order by one fused kernel behind VolumeAugment: `con(aug(raw))`, or torch.nn.Sequential(aug, con).  Two launches: the draw into a
+    readable table (last_params) and the apply, which reads the volumes once and writes a NEW tensor once.  Gamma and bias are meant for
+    window-normalised volumes (VolumeAugment(normalize="window") puts the foreground on [0, 1]).  The stage has no backward.
+
+    Call k uses seed + k; eval() returns its input tensor itself (no launch, no table, call index not advanced).  capturable=True keeps k
+    in a device counter, as VolumeAugment does: call the stage once on the batch shape before capturing it."""
+
+    def __init__(self, blur_prob=.2, blur_sigma_range=(.5, 1.5), blur_isotropic=False, bias_prob=.2, bias_coeff=.3, gamma_prob=.3,
+                 log_gamma_range=(-.3, .3), gamma_window=(0.0, 1.0), out_dtype=None, seed=0, capturable=False):
+        super().__init__()
+        who = "ContrastAugment"
+        if out_dtype not in (None, torch.bfloat16, torch.float32):
+            raise ValueError(f"{who}: out_dtype={out_dtype} must be None (the input's), torch.bfloat16 or torch.float32")
+        c = _lib.ContrastConfig()
+        for name, p in (("blur_prob", blur_prob), ("bias_prob", bias_prob), ("gamma_prob", gamma_prob)):
+            p = float(p)
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"{who}: {name}={p} is not a probability")
+            setattr(c, name, p)
+
+        def ordered(name, r):
+            r = tuple(float(v) for v in r)
+            if len(r) != 2 or not r[0] <= r[1] or not all(v - v == 0.0 for v in r):
+                raise ValueError(f"{who}: {name}={r} is reversed or not finite")
+            return r
+
+        c.blur_sigma_range[:] = ordered("blur_sigma_range", blur_sigma_range)
+        if not (c.blur_sigma_range[0] > 0.0 and c.blur_sigma_range[1] <= 2.0):
+            raise ValueError(f"{who}: blur_sigma_range={tuple(blur_sigma_range)} needs 0 < lo <= hi <= 2.0 (the radius ceil(3 sigma) is capped at "
+                             f"{CON_MAX_RADIUS} voxels)")
+        c.blur_isotropic = int(bool(blur_isotropic))
+        c.bias_coeff = float(bias_coeff)
+        if not (c.bias_coeff >= 0.0 and c.bias_coeff - c.bias_coeff == 0.0):
+            raise ValueError(f"{who}: bias_coeff={bias_coeff} must be finite and >= 0")
+        c.log_gamma_range[:] = ordered("log_gamma_range", log_gamma_range)
+        c.gamma_window[:] = ordered("gamma_window", gamma_window)
+        if not c.gamma_window[0] < c.gamma_window[1]:
+            raise ValueError(f"{who}: gamma_window={tuple(gamma_window)} needs lo < hi")
+        self.config = c
+        self.out_dtype, self.seed, self.capturable = out_dtype, int(seed), bool(capturable)
+        self.calls = 0             # host call index (capturable: see call_index)
+        self._counter = None       # capturable: the device call index
+        self._tables = {}          # capturable: one static table per (B, M, device)
+        self.last_params = None
+
+    @property
+    def call_index(self) -> int:
+        """Training calls made so far (capturable: read from the device counter, a host synchronisation)."""
+        return int(self._counter.item()) if self._counter is not None else self.calls
+
+    @staticmethod
+    def _volumes(img):
+        if not isinstance(img, torch.Tensor) or not img.is_cuda:
+            raise RuntimeError("ContrastAugment: the volumes must be a GPU tensor; this stage has no CPU path")
+        if not (img.dim() == 5 or (img.dim() == 6 and img.shape[2] == 1)):
+            raise ValueError(f"ContrastAugment: need [B, M, D, H, W] or [B, M, 1, D, H, W], got {tuple(img.shape)}")
+        if img.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(f"ContrastAugment: {img.dtype} volumes are not supported (bfloat16, float32)")
+        if not img.is_contiguous():
+            raise ValueError("ContrastAugment: the volumes must be contiguous")
+        if img.requires_grad:
+            raise RuntimeError("ContrastAugment: the stage has no backward; detach the volumes")
+        return img
+
+    def _table(self, B, M, device):
+        if not self.capturable:
+            return torch.empty(B, M, CON_NPARAM, dtype=torch.float32, device=device)
+        key = (B, M, device)
+        if key not in self._tables or self._counter is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ContrastAugment(capturable=True): call the stage once on this batch shape before capturing it; "
+                                   "its table and counter must not be allocated inside the graph")
+            self._tables[key] = torch.empty(B, M, CON_NPARAM, dtype=torch.float32, device=device)
+            if self._counter is None:
+                self._counter = torch.zeros(1, dtype=torch.int64, device=device)
+        return self._tables[key]
+
+    def draw(self, B, M, device) -> ContrastParams:
+        """One table for B x M volumes; advances the call index."""
+        table = self._table(B, M, device)
+        if self.capturable:
+            ops.contrast_draw(self.config, table, self.seed, self._counter, advance=True)
+        else:
+            ops.contrast_draw(self.config, table, (self.seed + self.calls * _COUNTER_STRIDE) & _MASK64)
+            self.calls += 1
+        return ContrastParams(table)
+
+    def apply(self, img, params, out_dtype=None):
+        img = self._volumes(img)
+        table = params.table if isinstance(params, ContrastParams) else params
+        B, M = img.shape[:2]
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (B, M, CON_NPARAM):
+            raise ValueError(f"ContrastAugment: the table must be fp32 [{B}, {M}, {CON_NPARAM}] for these volumes, got "
+                             f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
+        if table.device != img.device:
+            raise ValueError(f"ContrastAugment: the table is on {table.device}, the volumes on {img.device}")
+        return ops.contrast_apply(img, table.contiguous(), out_dtype or self.out_dtype)
+
+    def forward(self, img):
+        if not self.training:
+            return img
+        img = self._volumes(img)
+        self.last_params = self.draw(img.shape[0], img.shape[1], img.device)
+        return self.apply(img, self.last_params)

@@ -995,6 +995,35 @@ def augment_apply(src, params, img_size, pad_value=-1.0, out_dtype=torch.bfloat1
     return out
 
 
+def contrast_draw(config, params, seed, counter=None, advance=False):
+    """xvit_contrast_draw (include/xvit.h): fill params [B, M, 32] (fp32) with one blur / bias / gamma record per volume drawn from `config`
+    (_lib.ContrastConfig) and `seed`.  counter: as in augment_draw."""
+    assert params.dtype == torch.float32 and params.dim() == 3 and params.shape[2] == _lib.CON_NPARAM and params.is_contiguous()
+    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
+        raise RuntimeError("contrast_draw: the counter is a one-element int64 GPU tensor (or None)")
+    nvol = params.shape[0] * params.shape[1]
+    _run("contrast_draw", params.numel() * 4.0, "byte",
+         lambda: _lib.load().xvit_contrast_draw(C.byref(config), _ptr(params), nvol, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter), int(bool(advance)),
+                                                _stream()),
+         "xvit_contrast_draw")
+    return params
+
+
+def contrast_apply(src, params, out_dtype=None):
+    """xvit_contrast_apply (include/xvit.h): src [B, M, ..., D, H, W] (bf16 or fp32, contiguous) through the records params [B, M, 32] -> a
+    new tensor of src's shape in out_dtype (None: src's): blur along x, y, z, bias field, gamma, one rounding."""
+    assert src.dim() >= 5 and src.is_contiguous() and params.dtype == torch.float32 and params.is_contiguous()
+    B, M = src.shape[:2]
+    D, H, W = src.shape[-3:]
+    assert src.numel() == B * M * D * H * W, f"volumes {tuple(src.shape)} are not [B, M, (1,) D, H, W]"
+    assert tuple(params.shape) == (B, M, _lib.CON_NPARAM), f"params {tuple(params.shape)} do not match {B} x {M} volumes"
+    out = torch.empty(src.shape, dtype=out_dtype or src.dtype, device=src.device)
+    _run("contrast_apply", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
+         lambda: _lib.load().xvit_contrast_apply(_ptr(src), _ptr(out), _dt(src), _dt(out), _ptr(params), B * M, D, H, W, _stream()),
+         "xvit_contrast_apply")
+    return out
+
+
 def volume_stats_workspace(nvol, device):
     """The zero-filled histogram workspace of volume_stats for nvol volumes (xvit_volume_stats_workspace_bytes): every call leaves it
     zero again, so it is filled once, here."""

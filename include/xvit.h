@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 315 /* 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 316 /* 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -440,6 +440,72 @@ typedef struct xvit_norm_config {
 int64_t xvit_volume_stats_workspace_bytes(int nvol);
 int xvit_volume_stats(const void* src, int src_dtype, int nvol, int64_t nvox, const xvit_norm_config* cfg, double* stats, float* params /* NULL: no fold */,
                       void* workspace, int64_t workspace_bytes, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Contrast augmentations (csrc/contrast.hip): Gaussian blur, a smooth multiplicative bias field and gamma, as a second, independent
+ * stage behind the augmenting input stage (what MONAI RandGaussianSmooth / RandBiasField / RandAdjustContrast, nnU-Net's blur + gamma and
+ * TorchIO's RandomBlur / RandomBiasField / RandomGamma do in kind).  The transform set and its ranges are this project's own; parity
+ * with the random streams of MONAI or TorchIO is NOT claimed.  Two kernels with a table between them, like the stage in front:
+ * xvit_contrast_draw turns (config, seed) into params[nvol, XVIT_CON_NPARAM] (fp32, one record per volume, i.e. per (sample, modality));
+ * xvit_contrast_apply is a pure, out-of-place function of (src, params) that reads every volume once and writes it once.
+ *
+ * Record (fp32 slots):
+ *    0      flags (integer-valued): bit 0 blur, bit 1 bias, bit 2 gamma       1..3   sigma in voxels along z, y, x (0: axis not blurred)
+ *    4..6   radius along z, y, x = min(ceil(3 sigma), 6), integral (0 where sigma is 0)
+ *    7      gamma g = (float)exp((double)beta) (1 when not drawn)              8, 9   gamma window lo, hi
+ *    10..18 bias coefficients of the monomials z, y, x, z^2, y^2, x^2, zy, zx, yx, in this order (0 when not drawn)
+ *    19..21 the uniform draws behind the blur, bias and gamma decisions        22     beta = log gamma as drawn (0 when not drawn)
+ *    23..31 zero
+ * xvit_contrast_apply reads slots 0..18 only.
+ *
+ * xvit_contrast_draw.  Uniform numbers are u(i) = (hash32(seed', i) & 0xFFFFFF) / 2^24 with the dropout hash, where
+ * seed' = (seed + *counter * 0xD1B54A32D192ED03) ^ 0x434F4E5452415354 (the counter as in xvit_augment_draw: optional, read at run time,
+ * advance != 0: one thread stores counter + 1 after every thread has read it; the xor keeps this stream apart from xvit_augment_draw's
+ * when both stages are given one seed).  Volume v uses i = 64 v + k, and a value "uniform in [lo, hi]" is
+ * fminf(fmaxf(fmaf(u, hi - lo, lo), lo), hi) in fp32:
+ *    k = 0        blur?  (u < blur_prob)        1, 2, 3   sigma along z, y, x, uniform in blur_sigma_range (blur_isotropic: draw 1 on all axes)
+ *    k = 4        bias?  (u < bias_prob)        5 .. 13   the nine coefficients in record order, each uniform in [-bias_coeff, bias_coeff]
+ *    k = 14       gamma? (u < gamma_prob)       15        beta, uniform in log_gamma_range
+ * Draws behind a decision that came out false are not taken (their slots stay 0, gamma 1).  The window is copied from the config into
+ * every record.  config is a HOST struct, read during the call.  params 16-byte, counter 8-byte aligned.  Refused before the launch:
+ * null pointers, nvol <= 0, a probability outside [0, 1], blur_sigma_range with lo <= 0, lo > hi or hi > 2.0 (the radius cap),
+ * bias_coeff < 0 or not finite, a reversed or non-finite log_gamma_range, a gamma_window with hi <= lo or not finite.
+ *
+ * xvit_contrast_apply.  src, dst [nvol, D, H, W] contiguous, bf16 or fp32 each (all four combinations), fewer than 2^31 voxels per volume,
+ * src != dst.  Per voxel, in fp32, with ONE rounding at the end:
+ *  1. Blur, only with flag bit 0: separable, along x, then y, then z.  Along an axis with radius R and sigma s the weights are
+ *     w_k = exp(-k^2 / (2 s^2)) for |k| <= R, divided by their sum; a tap outside the volume takes the nearest edge voxel (index clamp), so
+ *     a constant volume stays constant and every D, H, W >= 1 is legal, sizes below R included.  An axis with R = 0 (or a sigma that is
+ *     not positive) is skipped.  The kernel clamps every record's radius into [0, XVIT_CON_MAX_RADIUS] before use: no table content makes
+ *     it read outside its own volume.
+ *  2. Bias, only with flag bit 1: v *= exp(c . m(u)) with u_axis = 2 i / (n - 1) - 1 (0 when n = 1) for index i of an axis of length n,
+ *     m(u) the nine monomials above and c slots 10..18.
+ *  3. Gamma, only with flag bit 2: t = (v - lo) / (hi - lo); if 0 <= t <= 1 then v = lo + (hi - lo) t^g, otherwise v is unchanged: the
+ *     map is continuous and monotone and a NaN passes through.  Gamma and bias are meant for window-normalised volumes (the default
+ *     window is [0, 1]).
+ *  4. One rounding to the destination dtype (nearest even).
+ * A record with flags 0 is a copy, bit for bit (bf16 -> fp32: the exact widening; fp32 -> bf16: one rounding).  A 256-thread workgroup
+ * owns a 64 x 16 (x, y) tile of a blur record and marches along z: each source plane goes through LDS once (blurred along x, then y) into
+ * a ring of 2 R_z + 1 planes from which the z-sum, bias, gamma and the store are taken; long columns of a small grid are cut into
+ * z-segments that re-read 2 R_z planes each.  Records without blur take a pointwise path over the flat volume, 16 bytes per lane; the
+ * branch is per volume.  No atomics and no dependence on execution order: two runs are bit-identical.
+ * Refused before the launch: null pointers, unknown dtype codes, nvol, D, H or W <= 0, 2^31 voxels or more per volume, src, dst or params
+ * not 16-byte aligned, src == dst.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_CON_NPARAM 32
+#define XVIT_CON_MAX_RADIUS 6
+enum { XVIT_CON_FLAGS = 0, XVIT_CON_SIGMA = 1, XVIT_CON_RADIUS = 4, XVIT_CON_GAMMA = 7, XVIT_CON_WINDOW_LO = 8, XVIT_CON_WINDOW_HI = 9, XVIT_CON_BIAS = 10,
+       XVIT_CON_U_BLUR = 19, XVIT_CON_U_BIAS = 20, XVIT_CON_U_GAMMA = 21, XVIT_CON_BETA = 22 };
+enum { XVIT_CON_FLAG_BLUR = 1, XVIT_CON_FLAG_BIAS = 2, XVIT_CON_FLAG_GAMMA = 4 };
+typedef struct xvit_contrast_config {
+  float blur_prob, blur_sigma_range[2];        /* sigma in voxels, 0 < lo <= hi <= 2.0 */
+  int blur_isotropic;                          /* != 0: one sigma for the three axes */
+  float bias_prob, bias_coeff;                 /* nine coefficients, each uniform in [-bias_coeff, bias_coeff] */
+  float gamma_prob, log_gamma_range[2];        /* g = exp(beta), beta uniform in the range */
+  float gamma_window[2];                       /* lo < hi: the curve acts inside the window only */
+} xvit_contrast_config;
+int xvit_contrast_draw(const xvit_contrast_config* config, float* params, int nvol, uint64_t seed, uint64_t* counter, int advance, xvit_stream_t stream);
+int xvit_contrast_apply(const void* src, void* dst, int src_dtype, int dst_dtype, const float* params, int nvol, int D, int H, int W, xvit_stream_t stream);
 
 /* x[m, b, 0, :] = cls + pos[0]  (model_cross.py:195-197, the CLS row); x fp32 [M*B, N, d] */
 int xvit_cls_row_fwd(const float* cls, const float* pos, float* x, int MB, int N, int d, xvit_stream_t stream);
