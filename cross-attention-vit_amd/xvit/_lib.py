@@ -47,6 +47,14 @@ class AugmentConfig(C.Structure):
 AUG_NPARAM = 32   # XVIT_AUG_NPARAM
 
 
+class ElasticConfig(C.Structure):
+    """struct xvit_elastic_config (include/xvit.h)."""
+    _fields_ = [("prob", f32), ("max_displacement", f32 * 3), ("locked_borders", i32)]
+
+
+ELASTIC_MAX_GRID, ELASTIC_NREC = 16, 8   # XVIT_ELASTIC_MAX_GRID, XVIT_ELASTIC_NREC
+
+
 class ContrastConfig(C.Structure):
     """struct xvit_contrast_config (include/xvit.h)."""
     _fields_ = [("blur_prob", f32), ("blur_sigma_range", f32 * 2), ("blur_isotropic", i32), ("bias_prob", f32), ("bias_coeff", f32),
@@ -144,6 +152,8 @@ SIGNATURES = {
     "xvit_resize_pad_crop_i16": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_augment_draw": [C.POINTER(AugmentConfig), vp, i32, i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp],
     "xvit_augment_apply": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "xvit_elastic_draw": [C.POINTER(ElasticConfig), vp, vp, i32, i32, i32, i32, u64, vp, i32, vp],
+    "xvit_augment_apply_elastic": [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_contrast_draw": [C.POINTER(ContrastConfig), vp, i32, u64, vp, i32, vp],
     "xvit_contrast_apply": [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp],
     "xvit_volume_stats": [vp, i32, i32, i64, C.POINTER(NormConfig), vp, vp, vp, i64, vp],

@@ -7,6 +7,8 @@
 
     aug = xvit.augment.VolumeAugment((128, 128, 128), normalize="zscore")    # per-volume normalisation, also in eval()
     aug.last_stats                   # VolumeStats: n, n_w, mean, std, lo, hi, min, max of every volume's foreground
+    aug = xvit.augment.VolumeAugment((128, 128, 128), elastic_prob=.2)       # random elastic deformation inside the same resample
+    aug.last_elastic                 # ElasticField: the control grids and records this call drew; aug.apply(raw, params, elastic=...) replays
     xvit.augment.volume_stats(raw)   # the statistics alone
 
     con = xvit.augment.ContrastAugment(blur_prob=.2, bias_prob=.2, gamma_prob=.3, seed=0)      # a second stage behind the first
@@ -35,6 +37,8 @@ MATRIX, SCALE, SHIFT, SIGMA, NOISE_SEED, FLAGS, FLIPS, ANGLES, ZOOMS, TRANSLATIO
 CLAMP_LO, CLAMP_HI = 29, 30
 FLAG_EXACT, FLAG_CLAMP = 1, 2
 NSTAT = _lib.STATS_NSTAT
+ELASTIC_MAX_GRID, ELASTIC_NREC = _lib.ELASTIC_MAX_GRID, _lib.ELASTIC_NREC
+ELASTIC_FLAG, ELASTIC_U, ELASTIC_MAX_ABS = 0, 1, 2     # slots of an elastic record: enum XVIT_ELASTIC_* of include/xvit.h
 _NORM_MODES = {None: _lib.NORM_STATS_ONLY, "zscore": _lib.NORM_ZSCORE, "window": _lib.NORM_WINDOW}
 _COUNTER_STRIDE = 0xD1B54A32D192ED03   # seed' = seed + call index * this (mod 2^64), on the host here and in the draw kernel alike
 _MASK64 = (1 << 64) - 1
@@ -91,6 +95,33 @@ class AugmentParams:
 
     def clone(self):
         return AugmentParams(self.table.clone())
+
+
+class ElasticField:
+    """A B-spline control grid per sample (include/xvit.h, "Elastic deformation"): field [B, 3, Gz, Gy, Gx] (fp32; components z, y, x in
+    destination voxels) and record [B, 8] (fp32).  `active` and `max_abs` are views of the record."""
+
+    def __init__(self, field: torch.Tensor, record: torch.Tensor):
+        G = ELASTIC_MAX_GRID
+        if field.dtype != torch.float32 or field.dim() != 5 or field.shape[1] != 3 or not all(4 <= n <= G for n in field.shape[2:]):
+            raise ValueError(f"ElasticField: need an fp32 [B, 3, Gz, Gy, Gx] field with 4 <= G <= {G}, got {field.dtype} {tuple(field.shape)}")
+        if record.dtype != torch.float32 or tuple(record.shape) != (field.shape[0], ELASTIC_NREC):
+            raise ValueError(f"ElasticField: need an fp32 [{field.shape[0]}, {ELASTIC_NREC}] record, got {record.dtype} {tuple(record.shape)}")
+        self.field, self.record = field, record
+
+    @classmethod
+    def zeros(cls, B, grid, device=None):
+        """No sample deformed: zero fields, flags 0.  grid: an int or (Gz, Gy, Gx)."""
+        grid = (int(grid),) * 3 if isinstance(grid, int) else tuple(int(v) for v in grid)
+        return cls(torch.zeros((B, 3) + grid, dtype=torch.float32, device=device), torch.zeros(B, ELASTIC_NREC, dtype=torch.float32, device=device))
+
+    grid = property(lambda s: tuple(s.field.shape[2:]))
+    active = property(lambda s: s.record[:, ELASTIC_FLAG])                               # 1 = the sample is deformed
+    draw = property(lambda s: s.record[:, ELASTIC_U])                                    # the uniform behind the decision
+    max_abs = property(lambda s: s.record[:, ELASTIC_MAX_ABS:ELASTIC_MAX_ABS + 3])       # max |phi| per component (z, y, x) as drawn
+
+    def clone(self):
+        return ElasticField(self.field.clone(), self.record.clone())
 
 
 class VolumeStats:
@@ -186,12 +217,20 @@ class VolumeAugment(torch.nn.Module):
 
     Call k uses seed + k, so a run is reproducible from `seed`; eval() switches every probability off (pad / crop and the fixed intensity
     affine only) and does not advance k.  capturable=True keeps k in a device counter so that the call can sit inside torch.cuda.graph and
-    draw anew at every replay; call the stage once before capturing (it allocates its table, counter and statistics buffers then)."""
+    draw anew at every replay; call the stage once before capturing (it allocates its table, counter and statistics buffers then).
+
+    elastic_prob > 0 adds random elastic deformation (include/xvit.h, "Elastic deformation"): per sample, with that probability, a cubic
+    B-spline displacement on elastic_control_points control points per axis (an int or three), each free control point uniform in
+    +-elastic_max_displacement destination voxels (a float or three, z, y, x), the outer elastic_locked_borders control layers held at
+    zero.  It is composed into the one resample (p = A (q + u(q)) + t), costs one launch more (the field's draw, in front of the table's,
+    on the same call index) and is off in eval(); last_elastic holds the ElasticField of the last call (None when nothing was drawn).  A
+    displacement above half a control cell is refused unless elastic_allow_folding is set."""
 
     def __init__(self, img_size, pad_value=-1.0, flip_prob=(.5, .5, .5), rotate_prob=.5, rotate_range=(.26, .26, .26), zoom_prob=.5,
                  zoom_range=(.9, 1.1), translate_prob=.5, translate_range=(8, 8, 8), scale_intensity_prob=.5, scale_intensity_range=(.9, 1.1),
                  shift_intensity_prob=.5, shift_intensity_range=(-.1, .1), noise_prob=.2, noise_std=.05, intensity_scale=1.0, intensity_shift=0.0,
-                 out_dtype=torch.bfloat16, seed=0, capturable=False, normalize=None, foreground_above=0.0, percentiles=(0.005, 0.995), clip=True):
+                 out_dtype=torch.bfloat16, seed=0, capturable=False, normalize=None, foreground_above=0.0, percentiles=(0.005, 0.995), clip=True,
+                 elastic_prob=0.0, elastic_control_points=7, elastic_max_displacement=7.5, elastic_locked_borders=2, elastic_allow_folding=False):
         super().__init__()
         self.img_size = tuple(int(v) for v in img_size)
         if len(self.img_size) != 3 or min(self.img_size) <= 0:
@@ -225,6 +264,10 @@ class VolumeAugment(torch.nn.Module):
         except ValueError as e:
             raise ValueError(f"VolumeAugment: {e}") from None
         self.normalize = normalize
+        self.elastic_config, self.elastic_grid = self._elastic_arguments(elastic_prob, elastic_control_points, elastic_max_displacement,
+                                                                         elastic_locked_borders, elastic_allow_folding)
+        self._elastic = {}         # capturable: one static ElasticField per (B, device)
+        self.last_elastic = None
         self.calls = 0             # host call index (capturable: see call_index)
         self._counter = None       # capturable: the device call index
         self._tables = {}          # capturable: one static table per (B, M, device)
@@ -232,6 +275,31 @@ class VolumeAugment(torch.nn.Module):
         self._workspaces = {}      # normalize: the histogram workspace per (B M, device), zero between calls
         self.last_params = None
         self.last_stats = None
+
+    def _elastic_arguments(self, prob, control_points, max_displacement, locked_borders, allow_folding):
+        """_lib.ElasticConfig and the control grid (Gz, Gy, Gx) from the constructor's arguments.  With prob > 0 a displacement above half a
+        control cell, 0.5 (n - 1) / (G - 3) voxels, is refused unless allow_folding: beyond it the map q + u(q) can fold."""
+        c = _lib.ElasticConfig()
+        c.prob = _prob("elastic_prob", prob)
+        grid = (control_points,) * 3 if isinstance(control_points, int) else tuple(control_points)
+        if len(grid) != 3 or not all(isinstance(n, int) and 4 <= n <= ELASTIC_MAX_GRID for n in grid):
+            raise ValueError(f"VolumeAugment: elastic_control_points={control_points} needs one or three ints in 4 .. {ELASTIC_MAX_GRID}")
+        disp = (max_displacement,) * 3 if isinstance(max_displacement, (int, float)) else tuple(max_displacement)
+        disp = tuple(float(v) for v in disp)
+        if len(disp) != 3 or not all(v >= 0.0 and v - v == 0.0 for v in disp):
+            raise ValueError(f"VolumeAugment: elastic_max_displacement={max_displacement} needs one or three finite displacements >= 0 (voxels)")
+        if not (isinstance(locked_borders, int) and 0 <= locked_borders <= 3):
+            raise ValueError(f"VolumeAugment: elastic_locked_borders={locked_borders} must be 0, 1, 2 or 3")
+        if c.prob > 0.0 and not allow_folding:
+            for axis, (m, n, G) in enumerate(zip(disp, self.img_size, grid)):
+                half_cell = 0.5 * (n - 1) / (G - 3)
+                if m > half_cell:
+                    raise ValueError(f"VolumeAugment: elastic_max_displacement={m} along axis {axis} exceeds half a control cell ({half_cell:g} voxels for "
+                                     f"{G} control points over {n} voxels): the deformation can fold; lower it, use fewer control points or pass "
+                                     "elastic_allow_folding=True")
+        c.max_displacement[:] = disp
+        c.locked_borders = locked_borders
+        return c, grid
 
     @property
     def call_index(self) -> int:
@@ -266,6 +334,8 @@ class VolumeAugment(torch.nn.Module):
             if self.normalize is not None:
                 self._stats[key] = torch.empty(B, M, NSTAT, dtype=torch.float64, device=device)
                 self._workspaces[(B * M, device)] = ops.volume_stats_workspace(B * M, device)
+            if self.elastic_config.prob > 0.0:
+                self._elastic[(B, device)] = ElasticField.zeros(B, self.elastic_grid, device)
         return self._tables[key]
 
     def _normalise(self, raw, table):
@@ -292,19 +362,44 @@ class VolumeAugment(torch.nn.Module):
             self.calls += int(self.training)
         return AugmentParams(table)
 
-    def apply(self, raw, params, out_dtype=None):
+    def draw_elastic(self, B, M, device) -> ElasticField:
+        """One control grid per sample for the call that self.draw serves next: the same call index, which it does not advance."""
+        if self.capturable:
+            self._table(B, M, device)                      # the static buffers and the counter are allocated together, outside a capture
+            el = self._elastic[(B, device)]
+            ops.elastic_draw(self.elastic_config, el.field, el.record, self.seed, self._counter, advance=False)
+        else:
+            el = ElasticField(torch.empty((B, 3) + self.elastic_grid, dtype=torch.float32, device=device),
+                              torch.empty(B, ELASTIC_NREC, dtype=torch.float32, device=device))
+            ops.elastic_draw(self.elastic_config, el.field, el.record, (self.seed + self.calls * _COUNTER_STRIDE) & _MASK64)
+        return el
+
+    def apply(self, raw, params, out_dtype=None, elastic=None):
+        """The resample through an explicit table, and, with elastic= (an ElasticField), through its deformation as well."""
         raw = self._volumes(raw)
         table = params.table if isinstance(params, AugmentParams) else params
-        return ops.augment_apply(raw, table, self.img_size, self.pad_value, out_dtype or self.out_dtype)
+        if elastic is None:
+            return ops.augment_apply(raw, table, self.img_size, self.pad_value, out_dtype or self.out_dtype)
+        if not isinstance(elastic, ElasticField):
+            raise TypeError(f"VolumeAugment: elastic= takes an ElasticField, got {type(elastic).__name__}")
+        if elastic.field.shape[0] != raw.shape[0] or elastic.field.device != raw.device:
+            raise ValueError(f"VolumeAugment: the elastic field is for {elastic.field.shape[0]} samples on {elastic.field.device}, the volumes are "
+                             f"{raw.shape[0]} samples on {raw.device}")
+        return ops.augment_apply_elastic(raw, table, elastic.field.contiguous(), elastic.record.contiguous(), self.img_size, self.pad_value,
+                                         out_dtype or self.out_dtype)
 
     def forward(self, raw):
         raw = self._volumes(raw)
         if self.normalize is not None and raw.dtype == torch.float32:
             self._normalise(raw, None)     # the library refuses it before any launch (TypeError): nothing is drawn
+        elastic = None
+        if self.training and self.elastic_config.prob > 0.0:
+            elastic = self.draw_elastic(raw.shape[0], raw.shape[1], raw.device)      # first, on the call index the draw below advances
+        self.last_elastic = elastic
         self.last_params = self.draw(raw.shape[0], raw.shape[1], tuple(raw.shape[2:]), raw.device)
         if self.normalize is not None:
             self.last_stats = self._normalise(raw, self.last_params.table)
-        return self.apply(raw, self.last_params)
+        return self.apply(raw, self.last_params, elastic=elastic)
 
 
 # ---------------------------------------------------------------------------------------------------------------- contrast stage

@@ -995,6 +995,49 @@ def augment_apply(src, params, img_size, pad_value=-1.0, out_dtype=torch.bfloat1
     return out
 
 
+def _elastic_tables(field, erec, B, what):
+    G = _lib.ELASTIC_MAX_GRID
+    if not (isinstance(field, torch.Tensor) and field.dtype == torch.float32 and field.dim() == 5 and field.shape[0] == B and field.shape[1] == 3
+            and all(4 <= n <= G for n in field.shape[2:]) and field.is_contiguous()):
+        raise ValueError(f"{what}: the field must be a contiguous fp32 [{B}, 3, Gz, Gy, Gx] tensor with 4 <= G <= {G}, got "
+                         f"{getattr(field, 'dtype', type(field))} {tuple(getattr(field, 'shape', ()))}")
+    if not (isinstance(erec, torch.Tensor) and erec.dtype == torch.float32 and tuple(erec.shape) == (B, _lib.ELASTIC_NREC) and erec.is_contiguous()):
+        raise ValueError(f"{what}: the record must be a contiguous fp32 [{B}, {_lib.ELASTIC_NREC}] tensor, got "
+                         f"{getattr(erec, 'dtype', type(erec))} {tuple(getattr(erec, 'shape', ()))}")
+    return tuple(field.shape[2:])
+
+
+def elastic_draw(config, field, erec, seed, counter=None, advance=False):
+    """xvit_elastic_draw (include/xvit.h): fill field [B, 3, Gz, Gy, Gx] and erec [B, 8] (fp32) with one B-spline control grid per sample drawn
+    from `config` (_lib.ElasticConfig) and `seed`.  counter: as in augment_draw."""
+    B = field.shape[0] if isinstance(field, torch.Tensor) and field.dim() == 5 else 0
+    Gz, Gy, Gx = _elastic_tables(field, erec, B, "elastic_draw")
+    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
+        raise RuntimeError("elastic_draw: the counter is a one-element int64 GPU tensor (or None)")
+    _run("elastic_draw", (field.numel() + erec.numel()) * 4.0, "byte",
+         lambda: _lib.load().xvit_elastic_draw(C.byref(config), _ptr(field), _ptr(erec), B, Gz, Gy, Gx, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter),
+                                               int(bool(advance)), _stream()),
+         "xvit_elastic_draw")
+    return field, erec
+
+
+def augment_apply_elastic(src, params, field, erec, img_size, pad_value=-1.0, out_dtype=torch.bfloat16):
+    """xvit_augment_apply_elastic (include/xvit.h): augment_apply with the B-spline displacement of field [B, 3, Gz, Gy, Gx] composed into
+    the resample of every sample whose erec [B, 8] flag is 1; the other samples are processed as augment_apply processes them."""
+    assert src.dim() == 5 and src.is_contiguous() and params.dtype == torch.float32 and params.is_contiguous()
+    B, M, Ds, Hs, Ws = src.shape
+    assert tuple(params.shape) == (B, M, _lib.AUG_NPARAM), f"params {tuple(params.shape)} do not match {B} x {M} volumes"
+    Gz, Gy, Gx = _elastic_tables(field, erec, B, "augment_apply_elastic")
+    D, H, W = img_size
+    out = torch.empty(B, M, 1, D, H, W, dtype=out_dtype, device=src.device)
+    sdt = I16 if src.dtype == torch.int16 else _dt(src)
+    _run("augment_apply_elastic", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
+         lambda: _lib.load().xvit_augment_apply_elastic(_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params), _ptr(field), _ptr(erec), B * M, M, Gz, Gy, Gx,
+                                                        Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
+         "xvit_augment_apply_elastic")
+    return out
+
+
 def contrast_draw(config, params, seed, counter=None, advance=False):
     """xvit_contrast_draw (include/xvit.h): fill params [B, M, 32] (fp32) with one blur / bias / gamma record per volume drawn from `config`
     (_lib.ContrastConfig) and `seed`.  counter: as in augment_draw."""

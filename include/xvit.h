@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 316 /* 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 317 /* 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
@@ -384,6 +384,51 @@ int xvit_augment_draw(const xvit_augment_config* config, float* params, int B, i
                       uint64_t* counter, int advance, xvit_stream_t stream);
 int xvit_augment_apply(const void* src, int src_dtype, void* dst, int dst_dtype, const float* params, int nvol, int Ds, int Hs, int Ws, int D, int H,
                        int W, float pad_value, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Elastic deformation (csrc/elastic.hip): random non-rigid deformation composed into the ONE resample of the augmenting input stage, so
+ * that a volume is never interpolated twice.  The rule is this project's own: a cubic B-spline free-form deformation on a coarse control
+ * grid, as TorchIO's RandomElasticDeformation / SimpleITK's BSplineTransform build it; parity with their random streams is NOT claimed.
+ *
+ * Control grid, per SAMPLE (the M modalities of a sample are co-registered and move together): field [B, 3, Gz, Gy, Gx] fp32, contiguous,
+ * 16-byte aligned, component order (z, y, x), units DESTINATION voxels, 4 <= G_axis <= XVIT_ELASTIC_MAX_GRID.
+ * Record erec [B, XVIT_ELASTIC_NREC] fp32: slot 0 flag (1 = the sample is deformed), 1 the uniform draw behind the decision, 2..4
+ * max |phi| per component as drawn, 5..7 zero.
+ *
+ * Displacement at destination voxel index i along an axis of length n with G control points: s = (G - 3) / (n - 1) (0 when n = 1; fp32,
+ * rounded once), g = i s, c = min(floor(g), G - 4), tau = g - c in [0, 1]: the last voxel has c = G - 4, tau = 1 and nothing is read at
+ * c + 4.  Weights B0 = (1 - tau)^3 / 6, B1 = (3 tau^3 - 6 tau^2 + 4) / 6, B2 = (-3 tau^3 + 3 tau^2 + 3 tau + 1) / 6, B3 = tau^3 / 6;
+ *    u_k(q) = sum over a, b, c = 0..3 of B_a(tau_z) B_b(tau_y) B_c(tau_x) phi_k[c_z + a, c_y + b, c_x + c],   k = z, y, x.
+ * Composition: the deformation acts on the destination grid first, then the record's affine, p = A (q + u(q)) + t, computed as
+ * p_affine + A u with p_affine formed exactly as xvit_augment_apply forms it, so a zero field is bit-identical to xvit_augment_apply's
+ * general path.  Everything behind p is that path unchanged: the [-2, size + 1] clamp, trilinear taps with pad_value outside, the optional
+ * clamp window, a v + b, noise, one rounding.
+ *
+ * xvit_elastic_draw.  u(i) = (hash32(seed', i) & 0xFFFFFF) / 2^24, seed' = (seed + *counter * 0xD1B54A32D192ED03) ^ 0x00454C4153544943
+ * ("ELASTIC": apart from the augment and contrast streams under one seed); the counter is optional, read at run time, and advanced by one
+ * behind the draw when advance != 0, as in xvit_augment_draw.  Sample b uses i = 16384 b + k: k = 0 the decision (u < prob); the control
+ * point (component a, gz, gy, gx) uses k = 16 + ((a Gz + gz) Gy + gy) Gx + gx (< 16384 for G <= 16).  A free control point is
+ * fminf(fmaxf(fmaf(u, 2 m, -m), -m), m), m = max_displacement[a]; a locked one (an index < L or >= G - L along any axis, L =
+ * locked_borders) is 0: with L = 2 the displacement and its first derivative vanish at the volume faces (TorchIO's default).  A sample
+ * whose decision is false gets an all-zero field and flag 0.  config is a HOST struct, read during the call.
+ *
+ * xvit_augment_apply_elastic.  A pure function of (src, params, field, erec) with the dtypes, layouts and refusals of xvit_augment_apply;
+ * nvol is a multiple of M and volume v takes the field and record of sample v / M.  A sample whose flag is 0 is processed exactly as
+ * xvit_augment_apply processes it (exact path included) and its field is NOT read; a sample whose flag is 1 takes the general path even
+ * when its record carries XVIT_AUG_FLAG_EXACT.  Brick layout and order of xvit_augment_apply; no atomics: bit-reproducible.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_ELASTIC_MAX_GRID 16
+#define XVIT_ELASTIC_NREC 8
+enum { XVIT_ELASTIC_FLAG = 0, XVIT_ELASTIC_U = 1, XVIT_ELASTIC_MAX_ABS = 2 };
+typedef struct xvit_elastic_config {
+  float prob;                                  /* of deforming a sample */
+  float max_displacement[3];                   /* destination voxels, z, y, x: finite, >= 0 */
+  int locked_borders;                          /* 0..3 outer control layers held at zero */
+} xvit_elastic_config;
+int xvit_elastic_draw(const xvit_elastic_config* config, float* field, float* erec, int B, int Gz, int Gy, int Gx, uint64_t seed, uint64_t* counter,
+                      int advance, xvit_stream_t stream);
+int xvit_augment_apply_elastic(const void* src, int src_dtype, void* dst, int dst_dtype, const float* params, const float* field, const float* erec, int nvol,
+                               int M, int Gz, int Gy, int Gx, int Ds, int Hs, int Ws, int D, int H, int W, float pad_value, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-volume intensity statistics and normalisation (stands where a loader runs MONAI's NormalizeIntensity(nonzero=True) or

@@ -1,6 +1,8 @@
 """Time the augmenting input stage at the reference's input shape: B = 8, M = 2, 240 x 240 x 155 int16 -> 128^3 bf16.
 
-    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE]
+    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE] [--mode stage|elastic]
+
+--mode elastic times elastic deformation against the general path of the same run (see `elastic` below; profiles/elastic_measured.txt).
 
 Arms, interleaved inside every repeat (so that drift hits them alike): xvit_resize_pad_crop_i16 (twice: two identical arms), the exact
 path as identity, the exact path with all three flips, the general path (every random transform on), the draw kernel, the statistics pair
@@ -25,14 +27,97 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 B, M, SRC, DST = 8, 2, (240, 240, 155), (128, 128, 128)
 
 
+def interleaved(arms, reps, inner):
+    """Device-event microseconds per launch of every arm, the arms interleaved inside every repeat -> {name: [reps values]}."""
+    for _, fn in arms:          # warm-up: code objects, allocator
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in arms}
+    for _ in range(reps):
+        for name, fn in arms:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(inner):
+                fn()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / inner)
+    return times
+
+
+def elastic(a) -> int:
+    """--mode elastic: xvit_augment_apply on general-path records against xvit_augment_apply_elastic on the same records (every flag 1,
+    every flag 0), the elastic draw, and the whole stage with and without elastic_prob = 1.  Reported, not gated: nothing is asserted of a
+    time.  7^3 control points, max_displacement 7.5, locked_borders 2 (the defaults of VolumeAugment)."""
+    from xvit import ops
+    from xvit.augment import ElasticField, VolumeAugment
+
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    src = torch.randint(0, 3000, (B, M) + SRC, generator=g, dtype=torch.int16).to(dev)
+    on = dict(flip_prob=(1, 1, 1), rotate_prob=1, zoom_prob=1, translate_prob=1, scale_intensity_prob=1, shift_intensity_prob=1, noise_prob=0, intensity_scale=1e-3)
+    plain, deform = VolumeAugment(DST, **on), VolumeAugment(DST, elastic_prob=1.0, **on)
+    t_full = plain.draw(B, M, SRC, dev)
+    assert not bool(t_full.exact.any())
+    el_on = deform.draw_elastic(B, M, dev)
+    assert bool((el_on.active == 1).all())
+    el_off = ElasticField(el_on.field.clone(), torch.zeros_like(el_on.record))
+    zero = ElasticField.zeros(B, deform.elastic_grid, dev)
+    zero.active[:] = 1.0
+    want = plain.apply(src, t_full).view(torch.int16)
+    assert torch.equal(plain.apply(src, t_full, elastic=el_off).view(torch.int16), want)       # flags 0: xvit_augment_apply
+    assert torch.equal(plain.apply(src, t_full, elastic=zero).view(torch.int16), want)         # a zero field: the same bits
+    assert not torch.equal(plain.apply(src, t_full, elastic=el_on).view(torch.int16), want)
+    scratch = el_on.clone()
+
+    arms = [
+        ("xvit_augment_apply, general path", lambda: plain.apply(src, t_full)),
+        ("elastic apply, every flag 1", lambda: plain.apply(src, t_full, elastic=el_on)),
+        ("elastic apply, every flag 0", lambda: plain.apply(src, t_full, elastic=el_off)),
+        ("elastic draw", lambda: ops.elastic_draw(deform.elastic_config, scratch.field, scratch.record, 1)),
+        ("stage, elastic_prob=0", lambda: plain(src)),
+        ("stage, elastic_prob=1", lambda: deform(src)),
+        ("xvit_augment_apply, general path (again)", lambda: plain.apply(src, t_full)),
+    ]
+    times = interleaved(arms, a.reps, a.inner)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    same = ("xvit_augment_apply, general path", "xvit_augment_apply, general path (again)")
+    spread = max(max(times[n]) - min(times[n]) for n in same)
+    ref = min(med[n] for n in same)
+    lines = [f"augment_bench --mode elastic: B={B} M={M} {SRC} int16 -> {DST} bf16, control grid {deform.elastic_grid}, max_displacement "
+             f"{tuple(deform.elastic_config.max_displacement)}, {a.reps} repeats x {a.inner} launches per arm, interleaved; device-event microseconds per launch"]
+    for name, _ in arms:
+        t = times[name]
+        lines.append(f"  {name:42s} median {med[name]:8.2f} us  (min {min(t):8.2f}, max {max(t):8.2f})")
+    lines.append(f"  yardstick: xvit_augment_apply's general path in this run, {ref:.2f} us; spread between its two identical arms' repeats {spread:.2f} us, "
+                 f"their medians differ by {abs(med[same[0]] - med[same[1]]):.2f} us")
+    d0 = med["elastic apply, every flag 0"] - ref
+    lines.append(f"  every flag 0 against the yardstick: {d0:+.2f} us ({med['elastic apply, every flag 0'] / ref:.3f} x) -> "
+                 f"{'within' if abs(d0) <= spread else 'OUTSIDE'} the spread")
+    lines.append(f"  every flag 1 against the yardstick: {med['elastic apply, every flag 1'] - ref:+.2f} us ({med['elastic apply, every flag 1'] / ref:.3f} x)")
+    lines.append(f"  stage with elastic_prob=1 - stage without: {med['stage, elastic_prob=1'] - med['stage, elastic_prob=0']:+.2f} us "
+                 f"(elastic draw alone {med['elastic draw']:.2f} us)")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mode", choices=("stage", "elastic"), default="stage")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("augment_bench: needs a GPU; a CPU run measures nothing")
+    if a.mode == "elastic":
+        return elastic(a)
     from xvit import ops
     from xvit.augment import NSTAT, AugmentParams, VolumeAugment, norm_config
 
@@ -67,20 +152,7 @@ def main() -> int:
         ("stage, normalize=zscore", lambda: stage_norm(src)),
         ("xvit_resize_pad_crop_i16 (again)", lambda: ops.resize_pad_crop_i16(src, DST, -1.0)),
     ]
-    for _, fn in arms:          # warm-up: code objects, allocator
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name, _ in arms}
-    for _ in range(a.reps):
-        for name, fn in arms:
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(a.inner):
-                fn()
-            e.record()
-            e.synchronize()
-            times[name].append(s.elapsed_time(e) * 1e3 / a.inner)      # us per launch
+    times = interleaved(arms, a.reps, a.inner)      # us per launch
     nvol = B * M
     src_elems = nvol * min(SRC[0], DST[0]) * min(SRC[1], DST[1]) * min(SRC[2], DST[2])
     nbytes = src_elems * 2 + nvol * DST[0] * DST[1] * DST[2] * 2
