@@ -7,10 +7,6 @@
 
 namespace xvit {
 
-constexpr uint64_t kCounterStride = 0xD1B54A32D192ED03ull;   // the odd constant of drop_seed_at
-
-__device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) { return (float)draw24(seed, idx) * kInv24; }   // [0, 1), exact
-
 // ------------------------------------------------------------------------------------------
 // draw: one block; thread i serves volumes i, i + 256, ...  Every thread reads the counter before the barrier, one thread advances it
 // after it (a plain store), so all records of a launch see the same call index.
@@ -18,27 +14,26 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) { return
 __global__ void __launch_bounds__(256) augment_draw_kernel(xvit_augment_config c, float* __restrict__ params, int B, int M, AugGeom g, uint64_t seed,
                                                            uint64_t* counter, int advance) {
   const uint64_t count = counter ? *counter : 0;
-  const uint64_t s = seed + count * kCounterStride;
+  const uint64_t s = draw_seed(seed, count, 0);   // the first stream under a seed: no salt
   __syncthreads();
   if (advance && threadIdx.x == 0) *counter = count + 1;
 
   for (int vol = threadIdx.x; vol < B * M; vol += blockDim.x) {
     const uint64_t sp = 64ull * (uint64_t)(vol / M);   // spatial draws: by sample, never by modality
     const uint64_t in = 64ull * (uint64_t)vol + 32;    // intensity draws: by volume
-    auto range = [&](uint64_t i, float lo, float hi) { return fminf(fmaxf(fmaf(uniform01(s, i), hi - lo, lo), lo), hi); };
 
     float flip[3], ang[3] = {0.f, 0.f, 0.f}, zoom[3] = {1.f, 1.f, 1.f}, tr[3] = {0.f, 0.f, 0.f};
     for (int k = 0; k < 3; ++k) flip[k] = uniform01(s, sp + k) < c.flip_prob[k] ? 1.f : 0.f;
     if (uniform01(s, sp + 3) < c.rotate_prob)
-      for (int k = 0; k < 3; ++k) ang[k] = range(sp + 4 + k, -c.rotate_range[k], c.rotate_range[k]);
+      for (int k = 0; k < 3; ++k) ang[k] = uniform_in(s, sp + 4 + k, -c.rotate_range[k], c.rotate_range[k]);
     if (uniform01(s, sp + 7) < c.zoom_prob)
-      for (int k = 0; k < 3; ++k) zoom[k] = range(sp + 8 + k, c.zoom_range[0], c.zoom_range[1]);
+      for (int k = 0; k < 3; ++k) zoom[k] = uniform_in(s, sp + 8 + k, c.zoom_range[0], c.zoom_range[1]);
     if (uniform01(s, sp + 11) < c.translate_prob)
-      for (int k = 0; k < 3; ++k) tr[k] = range(sp + 12 + k, -c.translate_range[k], c.translate_range[k]);
+      for (int k = 0; k < 3; ++k) tr[k] = uniform_in(s, sp + 12 + k, -c.translate_range[k], c.translate_range[k]);
 
     float fac = 1.f, shift = 0.f, sigma = 0.f;
-    if (uniform01(s, in + 0) < c.scale_prob) fac = range(in + 1, c.scale_range[0], c.scale_range[1]);
-    if (uniform01(s, in + 2) < c.shift_prob) shift = range(in + 3, c.shift_range[0], c.shift_range[1]);
+    if (uniform01(s, in + 0) < c.scale_prob) fac = uniform_in(s, in + 1, c.scale_range[0], c.scale_range[1]);
+    if (uniform01(s, in + 2) < c.shift_prob) shift = uniform_in(s, in + 3, c.shift_range[0], c.shift_range[1]);
     if (uniform01(s, in + 4) < c.noise_prob) sigma = c.noise_std * ((float)(draw24(s, in + 5) + 1u) * kInv24);
     const uint32_t noise_seed = hash32(s, in + 6);
 
@@ -95,13 +90,6 @@ __global__ void __launch_bounds__(256) augment_apply_kernel(const S* __restrict_
   aug_apply_lane(src, dst, params + (int64_t)L.vol * XVIT_AUG_NPARAM, g, L, pad_value);   // the record is wave-uniform: scalar loads
 }
 
-template <typename S, typename T>
-static void launch_apply(const void* src, void* dst, const float* params, int nvol, const AugGeom& g, float pad_value, hipStream_t s) {
-  const AugBricks b(g);
-  hipLaunchKernelGGL((augment_apply_kernel<S, T>), dim3(b.blocks(nvol)), dim3(256), 0, s, (const S*)src, (T*)dst, params, g, b.lx, b.nbx, b.nby, b.nbz,
-                     pad_value);
-}
-
 }  // namespace xvit
 
 extern "C" int xvit_augment_draw(const xvit_augment_config* config, float* params, int B, int M, int Ds, int Hs, int Ws, int D, int H, int W, uint64_t seed,
@@ -110,22 +98,19 @@ extern "C" int xvit_augment_draw(const xvit_augment_config* config, float* param
   XVIT_REQUIRE(B > 0 && M > 0 && (int64_t)B * M < (1 << 24), "xvit_augment_draw: B=%d, M=%d must be positive (and B M < 2^24)", B, M);
   XVIT_REQUIRE(xvit::sizes_ok(Ds, Hs, Ws, D, H, W), "xvit_augment_draw: non-positive size (source %d x %d x %d, destination %d x %d x %d)", Ds, Hs, Ws, D, H, W);
   XVIT_REQUIRE(((uintptr_t)params & 15) == 0, "xvit_augment_draw: the parameter table must be 16-byte aligned");
-  XVIT_REQUIRE(((uintptr_t)counter & 7) == 0, "xvit_augment_draw: the counter must be 8-byte aligned");
-  XVIT_REQUIRE(counter || !advance, "xvit_augment_draw: advance needs a counter");
+  XVIT_REQUIRE_COUNTER("xvit_augment_draw", counter, advance);
   const xvit_augment_config& c = *config;
-  auto prob = [](float p) { return p >= 0.f && p <= 1.f; };   // false for NaN
+  const auto prob = xvit::prob_ok;
   XVIT_REQUIRE(prob(c.flip_prob[0]) && prob(c.flip_prob[1]) && prob(c.flip_prob[2]) && prob(c.rotate_prob) && prob(c.zoom_prob) && prob(c.translate_prob) &&
                    prob(c.scale_prob) && prob(c.shift_prob) && prob(c.noise_prob),
                "xvit_augment_draw: every probability must lie in [0, 1]");
   for (int k = 0; k < 3; ++k)
     XVIT_REQUIRE(c.rotate_range[k] >= 0.f && c.translate_range[k] >= 0.f && isfinite(c.rotate_range[k]) && isfinite(c.translate_range[k]),
                  "xvit_augment_draw: rotate_range and translate_range are half-widths: finite and >= 0");
-  XVIT_REQUIRE(c.zoom_range[0] > 0.f && c.zoom_range[0] <= c.zoom_range[1] && isfinite(c.zoom_range[1]),
-               "xvit_augment_draw: zoom_range (%g, %g) is reversed or not positive", c.zoom_range[0], c.zoom_range[1]);
-  XVIT_REQUIRE(c.scale_range[0] <= c.scale_range[1] && isfinite(c.scale_range[0]) && isfinite(c.scale_range[1]),
-               "xvit_augment_draw: scale_range (%g, %g) is reversed", c.scale_range[0], c.scale_range[1]);
-  XVIT_REQUIRE(c.shift_range[0] <= c.shift_range[1] && isfinite(c.shift_range[0]) && isfinite(c.shift_range[1]),
-               "xvit_augment_draw: shift_range (%g, %g) is reversed", c.shift_range[0], c.shift_range[1]);
+  XVIT_REQUIRE(c.zoom_range[0] > 0.f && xvit::range_ok(c.zoom_range[0], c.zoom_range[1]), "xvit_augment_draw: zoom_range (%g, %g) is reversed or not positive",
+               c.zoom_range[0], c.zoom_range[1]);
+  XVIT_REQUIRE(xvit::range_ok(c.scale_range[0], c.scale_range[1]), "xvit_augment_draw: scale_range (%g, %g) is reversed", c.scale_range[0], c.scale_range[1]);
+  XVIT_REQUIRE(xvit::range_ok(c.shift_range[0], c.shift_range[1]), "xvit_augment_draw: shift_range (%g, %g) is reversed", c.shift_range[0], c.shift_range[1]);
   XVIT_REQUIRE(c.noise_std >= 0.f && isfinite(c.noise_std), "xvit_augment_draw: noise_std=%g must be finite and >= 0", c.noise_std);
   XVIT_REQUIRE(isfinite(c.intensity_scale) && isfinite(c.intensity_shift), "xvit_augment_draw: the fixed intensity affine must be finite");
   hipLaunchKernelGGL(xvit::augment_draw_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, c, params, B, M, xvit::make_geom(Ds, Hs, Ws, D, H, W), seed, counter,
@@ -137,15 +122,14 @@ extern "C" int xvit_augment_apply(const void* src, int src_dtype, void* dst, int
                                   int W, float pad_value, xvit_stream_t stream) {
   XVIT_AUG_APPLY_REQUIRE("xvit_augment_apply");
   const xvit::AugGeom g = xvit::make_geom(Ds, Hs, Ws, D, H, W);
-  hipStream_t s = (hipStream_t)stream;
-#define XVIT_AUG_CASE(SD, S, DD, T) \
-  if (src_dtype == SD && dst_dtype == DD) xvit::launch_apply<S, T>(src, dst, params, nvol, g, pad_value, s)
-  XVIT_AUG_CASE(XVIT_I16, int16_t, XVIT_BF16, xvit::bf16);
-  XVIT_AUG_CASE(XVIT_I16, int16_t, XVIT_F32, float);
-  XVIT_AUG_CASE(XVIT_BF16, xvit::bf16, XVIT_BF16, xvit::bf16);
-  XVIT_AUG_CASE(XVIT_BF16, xvit::bf16, XVIT_F32, float);
-  XVIT_AUG_CASE(XVIT_F32, float, XVIT_BF16, xvit::bf16);
-  XVIT_AUG_CASE(XVIT_F32, float, XVIT_F32, float);
-#undef XVIT_AUG_CASE
+  const xvit::AugBricks b(g);
+  xvit::by_src_dtype(src_dtype, [&](auto sd) {
+    xvit::by_dtype(dst_dtype, [&](auto dd) {
+      using S = decltype(sd);
+      using T = decltype(dd);
+      hipLaunchKernelGGL((xvit::augment_apply_kernel<S, T>), dim3(b.blocks(nvol)), dim3(256), 0, (hipStream_t)stream, (const S*)src, (T*)dst, params, g, b.lx,
+                         b.nbx, b.nby, b.nbz, pad_value);
+    });
+  });
   return xvit::check_launch("xvit_augment_apply");
 }

@@ -5,45 +5,19 @@
 #pragma once
 #include <math.h>
 
-#include "xvit_common.h"
+#include "volume_io.h"
 
 namespace xvit {
-
-constexpr float kInv24 = 1.0f / kTwo24;
 
 struct AugGeom {
   int Ds, Hs, Ws, D, H, W;
   int od, oh, ow;   // the pad / crop offsets of xvit_resize_pad_crop_i16: source index = destination index + offset
 };
 
-__device__ __forceinline__ float src_f(int16_t v) { return (float)v; }
-__device__ __forceinline__ float src_f(bf16 v) { return bf2f(v); }
-__device__ __forceinline__ float src_f(float v) { return v; }
-
-// 8 consecutive source elements at any element-aligned address (the crop offset decides the alignment, not the kernel)
-template <typename S>
-__device__ __forceinline__ void load_run8(const S* p, float (&v)[8]) {
-  struct Run { S e[8]; } r;
-  __builtin_memcpy(&r, __builtin_assume_aligned(p, sizeof(S)), sizeof(r));
-  for (int i = 0; i < 8; ++i) v[i] = src_f(r.e[i]);
-}
-
-__device__ __forceinline__ void store_run8(bf16* p, const float (&v)[8]) {
-  bf16x8 o;
-  for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
-  *(bf16x8*)p = o;
-}
-__device__ __forceinline__ void store_run8(float* p, const float (&v)[8]) {
-  *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-  *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-}
-__device__ __forceinline__ void store_one(bf16* p, float v) { *p = f2bf(v); }
-__device__ __forceinline__ void store_one(float* p, float v) { *p = v; }
-
 // standard normal for voxel `idx` of a volume: Box-Muller on two 24-bit draws
 __device__ __forceinline__ float normal_at(uint32_t noise_seed, uint32_t idx) {
   const float u1 = (float)(draw24(noise_seed, 2ull * idx) + 1u) * kInv24;        // (0, 1]
-  const float u2 = (float)draw24(noise_seed, 2ull * idx + 1) * kInv24;           // [0, 1)
+  const float u2 = uniform01(noise_seed, 2ull * idx + 1);
   return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
 }
 

@@ -3,13 +3,11 @@
 // As in augment.hip the random numbers live in the table only: the kernel that touches the voxels is a pure function of (src, table).
 #include <math.h>
 
-#include "xvit_common.h"
+#include "volume_io.h"
 
 namespace xvit {
 
-constexpr uint64_t kConStride = 0xD1B54A32D192ED03ull;   // the counter stride of augment_draw_kernel (drop_seed_at)
 constexpr uint64_t kConSalt = 0x434F4E5452415354ull;     // "CONTRAST": keeps this stream apart from xvit_augment_draw's under one seed
-constexpr float kConInv24 = 1.0f / kTwo24;
 
 constexpr int TX = 64, TY = 16;                          // destination tile of a workgroup (x, y); it marches along z
 constexpr int RMAX = XVIT_CON_MAX_RADIUS, NRING = 2 * RMAX + 1;
@@ -26,31 +24,29 @@ constexpr int POINT_UNROLL = 4;                          // 16-byte runs a lane 
 __global__ void __launch_bounds__(256) contrast_draw_kernel(xvit_contrast_config c, float* __restrict__ params, int nvol, uint64_t seed, uint64_t* counter,
                                                             int advance) {
   const uint64_t count = counter ? *counter : 0;
-  const uint64_t s = (seed + count * kConStride) ^ kConSalt;
+  const uint64_t s = draw_seed(seed, count, kConSalt);
   __syncthreads();
   if (advance && threadIdx.x == 0) *counter = count + 1;
 
   for (int vol = threadIdx.x; vol < nvol; vol += blockDim.x) {
     const uint64_t i0 = 64ull * (uint64_t)vol;
-    auto u01 = [&](int k) { return (float)draw24(s, i0 + k) * kConInv24; };   // [0, 1), exact
-    auto range = [&](int k, float lo, float hi) { return fminf(fmaxf(fmaf(u01(k), hi - lo, lo), lo), hi); };
 
     float* __restrict__ P = params + (int64_t)vol * XVIT_CON_NPARAM;
     int flags = 0;
-    const float ublur = u01(0), ubias = u01(4), ugamma = u01(14);
+    const float ublur = uniform01(s, i0 + 0), ubias = uniform01(s, i0 + 4), ugamma = uniform01(s, i0 + 14);
     float sigma[3] = {0.f, 0.f, 0.f}, beta = 0.f, coeff[9];
     for (int k = 0; k < 9; ++k) coeff[k] = 0.f;
     if (ublur < c.blur_prob) {
       flags |= XVIT_CON_FLAG_BLUR;
-      for (int k = 0; k < 3; ++k) sigma[k] = range(c.blur_isotropic ? 1 : 1 + k, c.blur_sigma_range[0], c.blur_sigma_range[1]);
+      for (int k = 0; k < 3; ++k) sigma[k] = uniform_in(s, i0 + (c.blur_isotropic ? 1 : 1 + k), c.blur_sigma_range[0], c.blur_sigma_range[1]);
     }
     if (ubias < c.bias_prob) {
       flags |= XVIT_CON_FLAG_BIAS;
-      for (int k = 0; k < 9; ++k) coeff[k] = range(5 + k, -c.bias_coeff, c.bias_coeff);
+      for (int k = 0; k < 9; ++k) coeff[k] = uniform_in(s, i0 + 5 + k, -c.bias_coeff, c.bias_coeff);
     }
     if (ugamma < c.gamma_prob) {
       flags |= XVIT_CON_FLAG_GAMMA;
-      beta = range(15, c.log_gamma_range[0], c.log_gamma_range[1]);
+      beta = uniform_in(s, i0 + 15, c.log_gamma_range[0], c.log_gamma_range[1]);
     }
     P[XVIT_CON_FLAGS] = (float)flags;
     for (int k = 0; k < 3; ++k) {
@@ -72,32 +68,6 @@ __global__ void __launch_bounds__(256) contrast_draw_kernel(xvit_contrast_config
 // ------------------------------------------------------------------------------------------
 // apply
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float con_f(bf16 v) { return bf2f(v); }
-__device__ __forceinline__ float con_f(float v) { return v; }
-__device__ __forceinline__ void con_store(bf16* p, float v) { *p = f2bf(v); }
-__device__ __forceinline__ void con_store(float* p, float v) { *p = v; }
-
-// 8 consecutive elements from a 16-byte aligned address
-__device__ __forceinline__ void con_load8(const bf16* p, float (&v)[8]) {
-  const bf16x8 r = *(const bf16x8*)p;
-  for (int i = 0; i < 8; ++i) v[i] = bf2f(r[i]);
-}
-__device__ __forceinline__ void con_load8(const float* p, float (&v)[8]) {
-  const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-  for (int i = 0; i < 4; ++i) v[i] = a[i], v[4 + i] = b[i];
-}
-__device__ __forceinline__ void con_store8(bf16* p, const float (&v)[8]) {
-  bf16x8 o;
-  for (int i = 0; i < 8; ++i) o[i] = f2bf(v[i]);
-  *(bf16x8*)p = o;
-}
-__device__ __forceinline__ void con_store8(float* p, const float (&v)[8]) {
-  *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-  *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-}
-__device__ __forceinline__ void con_store4(bf16* p, const f32x4& v) { *(bf16x4*)p = to_bf16x4(v); }
-__device__ __forceinline__ void con_store4(float* p, const f32x4& v) { *(f32x4*)p = v; }
-
 // t^g for t in [0, 1], g > 0, without powf: measured against float64, powf(1e-30f, 0.74f) was 19 ulp off, and a power's relative error
 // is its exponent's absolute one.  So: t = m 2^e with m in [2^-1/2, 2^1/2), the exponent g (e + log2f(m)) formed in double (log2f's 1 ulp
 // of |log2 m| <= 0.5 is all that is lost), split into n + f, 2^f from exp2f and 2^n from ldexpf.  t = 1: m = 1, e = 0, exactly 1.
@@ -170,9 +140,9 @@ __global__ void __launch_bounds__(256) contrast_apply_kernel(const S* __restrict
         if (r >= last) break;
         const uint32_t i = r << 3;
         if (aligned && i + 8 <= nvox) {
-          con_load8(sv + i, v[u]);
+          load_run8_aligned(sv + i, v[u]);
         } else {
-          for (int e = 0; e < 8; ++e) v[u][e] = con_f(sv[min(i + e, nvox - 1)]);
+          for (int e = 0; e < 8; ++e) v[u][e] = src_f(sv[min(i + e, nvox - 1)]);
         }
       }
 #pragma unroll
@@ -194,10 +164,10 @@ __global__ void __launch_bounds__(256) contrast_apply_kernel(const S* __restrict
           }
         }
         if (aligned && i + 8 <= nvox) {
-          con_store8(dv + i, v[u]);
+          store_run8(dv + i, v[u]);
         } else {
           for (int e = 0; e < 8; ++e)
-            if (i + e < nvox) con_store(dv + i + e, v[u][e]);
+            if (i + e < nvox) store_one(dv + i + e, v[u][e]);
         }
       }
     }
@@ -251,9 +221,9 @@ __global__ void __launch_bounds__(256) contrast_apply_kernel(const S* __restrict
       const int gy = min(max(y0 - Ry + row, 0), H - 1), gx = x0 + run * 8;
       const S* __restrict__ line = sv + ((uint32_t)p * H + gy) * (uint32_t)W;
       if (vec && gx >= 0 && gx + 8 <= W) {
-        con_load8(line + gx, pre[u]);
+        load_run8_aligned(line + gx, pre[u]);
       } else {
-        for (int e = 0; e < 8; ++e) pre[u][e] = con_f(line[min(max(gx + e, 0), W - 1)]);
+        for (int e = 0; e < 8; ++e) pre[u][e] = src_f(line[min(max(gx + e, 0), W - 1)]);
       }
     }
   };
@@ -310,10 +280,10 @@ __global__ void __launch_bounds__(256) contrast_apply_kernel(const S* __restrict
       }
       T* __restrict__ out = dv + ((uint32_t)zo * H + gy_out) * (uint32_t)W + gx_out;
       if (store_vec) {   // W % 4 == 0: the run of 4 is inside the row and its address a multiple of 4 elements
-        con_store4(out, acc);
+        store_run4(out, acc);
       } else {
         for (int e = 0; e < 4; ++e)
-          if (gx_out + e < W) con_store(out + e, acc[e]);
+          if (gx_out + e < W) store_one(out + e, acc[e]);
       }
     }
   }
@@ -333,18 +303,17 @@ extern "C" int xvit_contrast_draw(const xvit_contrast_config* config, float* par
   XVIT_REQUIRE(config && params, "xvit_contrast_draw: null config or parameter table");
   XVIT_REQUIRE(nvol > 0 && nvol < (1 << 24), "xvit_contrast_draw: nvol=%d must be positive (and below 2^24)", nvol);
   XVIT_REQUIRE(((uintptr_t)params & 15) == 0, "xvit_contrast_draw: the parameter table must be 16-byte aligned");
-  XVIT_REQUIRE(((uintptr_t)counter & 7) == 0, "xvit_contrast_draw: the counter must be 8-byte aligned");
-  XVIT_REQUIRE(counter || !advance, "xvit_contrast_draw: advance needs a counter");
+  XVIT_REQUIRE_COUNTER("xvit_contrast_draw", counter, advance);
   const xvit_contrast_config& c = *config;
-  auto prob = [](float p) { return p >= 0.f && p <= 1.f; };   // false for NaN
-  XVIT_REQUIRE(prob(c.blur_prob) && prob(c.bias_prob) && prob(c.gamma_prob), "xvit_contrast_draw: every probability must lie in [0, 1]");
+  XVIT_REQUIRE(xvit::prob_ok(c.blur_prob) && xvit::prob_ok(c.bias_prob) && xvit::prob_ok(c.gamma_prob),
+               "xvit_contrast_draw: every probability must lie in [0, 1]");
   XVIT_REQUIRE(c.blur_sigma_range[0] > 0.f && c.blur_sigma_range[0] <= c.blur_sigma_range[1] && c.blur_sigma_range[1] <= 2.0f,
                "xvit_contrast_draw: blur_sigma_range (%g, %g) needs 0 < lo <= hi <= 2.0 (radius ceil(3 sigma) <= %d)", c.blur_sigma_range[0],
                c.blur_sigma_range[1], XVIT_CON_MAX_RADIUS);
   XVIT_REQUIRE(c.bias_coeff >= 0.f && isfinite(c.bias_coeff), "xvit_contrast_draw: bias_coeff=%g must be finite and >= 0", c.bias_coeff);
-  XVIT_REQUIRE(c.log_gamma_range[0] <= c.log_gamma_range[1] && isfinite(c.log_gamma_range[0]) && isfinite(c.log_gamma_range[1]),
-               "xvit_contrast_draw: log_gamma_range (%g, %g) is reversed or not finite", c.log_gamma_range[0], c.log_gamma_range[1]);
-  XVIT_REQUIRE(c.gamma_window[0] < c.gamma_window[1] && isfinite(c.gamma_window[0]) && isfinite(c.gamma_window[1]),
+  XVIT_REQUIRE(xvit::range_ok(c.log_gamma_range[0], c.log_gamma_range[1]), "xvit_contrast_draw: log_gamma_range (%g, %g) is reversed or not finite",
+               c.log_gamma_range[0], c.log_gamma_range[1]);
+  XVIT_REQUIRE(c.gamma_window[0] != c.gamma_window[1] && xvit::range_ok(c.gamma_window[0], c.gamma_window[1]),
                "xvit_contrast_draw: gamma_window (%g, %g) needs finite lo < hi", c.gamma_window[0], c.gamma_window[1]);
   hipLaunchKernelGGL(xvit::contrast_draw_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, c, params, nvol, seed, counter, advance);
   return xvit::check_launch("xvit_contrast_draw");

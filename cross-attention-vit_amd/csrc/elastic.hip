@@ -25,7 +25,6 @@
 
 namespace xvit {
 
-constexpr uint64_t kElaStride = 0xD1B54A32D192ED03ull;   // the counter stride of augment_draw_kernel (drop_seed_at)
 constexpr uint64_t kElaSalt = 0x00454C4153544943ull;     // "ELASTIC": keeps this stream apart from the augment and contrast streams under one seed
 constexpr int kElaSampleStride = 16384, kElaPointBase = 16;   // hash indices per sample; the first control point's index
 constexpr int kElaRowStride = 3 * XVIT_ELASTIC_MAX_GRID + 1;  // floats per destination row in LDS
@@ -43,10 +42,10 @@ __global__ void __launch_bounds__(256) elastic_draw_kernel(xvit_elastic_config c
                                                            uint64_t seed, const uint64_t* counter) {
   __shared__ float red[3][256];
   const uint64_t count = counter ? *counter : 0;
-  const uint64_t s = (seed + count * kElaStride) ^ kElaSalt;
+  const uint64_t s = draw_seed(seed, count, kElaSalt);
   const int b = blockIdx.x, L = c.locked_borders;
   const uint64_t i0 = (uint64_t)kElaSampleStride * (uint64_t)b;
-  const float udec = (float)draw24(s, i0) * kInv24;   // [0, 1), exact
+  const float udec = uniform01(s, i0);
   const bool active = udec < c.prob;
 
   const int per = Gz * Gy * Gx;
@@ -62,7 +61,7 @@ __global__ void __launch_bounds__(256) elastic_draw_kernel(xvit_elastic_config c
     float v = 0.f;
     if (active && !locked) {
       const float m = c.max_displacement[a];
-      v = fminf(fmaxf(fmaf((float)draw24(s, i0 + kElaPointBase + idx) * kInv24, 2.f * m, -m), -m), m);
+      v = uniform_in(s, i0 + kElaPointBase + idx, -m, m);   // m - -m = 2 m exactly
     }
     F[idx] = v;
     for (int k = 0; k < 3; ++k) mx[k] = a == k ? fmaxf(mx[k], fabsf(v)) : mx[k];
@@ -184,16 +183,15 @@ __global__ void __launch_bounds__(256) augment_apply_elastic_kernel(const S* __r
   aug_finish_run(P, flags, g, L, dst, v);
 }
 
-template <typename S, typename T>
-static void launch_apply_elastic(const void* src, void* dst, const float* params, const float* field, const float* erec, int nvol, int M, const AugGeom& g,
-                                 const ElasticGeom& e, float pad_value, hipStream_t s) {
-  const AugBricks b(g);
-  hipLaunchKernelGGL((augment_apply_elastic_kernel<S, T>), dim3(b.blocks(nvol)), dim3(256), 0, s, (const S*)src, (T*)dst, params, field, erec, M, g, e, b.lx,
-                     b.nbx, b.nby, b.nbz, pad_value);
-}
-
 static bool grid_ok(int G) { return G >= 4 && G <= XVIT_ELASTIC_MAX_GRID; }
 static float grid_step(int G, int n) { return n > 1 ? (float)(G - 3) / (float)(n - 1) : 0.f; }
+
+// What both entry points refuse about the grid and its buffers, under the caller's name.
+#define XVIT_ELASTIC_REQUIRE_GRID(who)                                                                                                                      \
+  XVIT_REQUIRE(xvit::grid_ok(Gz) && xvit::grid_ok(Gy) && xvit::grid_ok(Gx), who ": grid %d x %d x %d: every axis needs 4 .. %d control points", Gz, Gy, Gx, \
+               XVIT_ELASTIC_MAX_GRID)
+#define XVIT_ELASTIC_REQUIRE_ALIGNED(who) \
+  XVIT_REQUIRE(((uintptr_t)field & 15) == 0 && ((uintptr_t)erec & 15) == 0, who ": the field and the record must be 16-byte aligned")
 
 }  // namespace xvit
 
@@ -201,17 +199,15 @@ extern "C" int xvit_elastic_draw(const xvit_elastic_config* config, float* field
                                  int advance, xvit_stream_t stream) {
   XVIT_REQUIRE(config && field && erec, "xvit_elastic_draw: null config, field or record");
   XVIT_REQUIRE(B > 0 && B < (1 << 17), "xvit_elastic_draw: B=%d must be positive and below 2^17", B);
-  XVIT_REQUIRE(xvit::grid_ok(Gz) && xvit::grid_ok(Gy) && xvit::grid_ok(Gx), "xvit_elastic_draw: grid %d x %d x %d: every axis needs 4 .. %d control points", Gz,
-               Gy, Gx, XVIT_ELASTIC_MAX_GRID);
+  XVIT_ELASTIC_REQUIRE_GRID("xvit_elastic_draw");
   const xvit_elastic_config& c = *config;
-  XVIT_REQUIRE(c.prob >= 0.f && c.prob <= 1.f, "xvit_elastic_draw: the probability must lie in [0, 1]");   // false for NaN
+  XVIT_REQUIRE(xvit::prob_ok(c.prob), "xvit_elastic_draw: the probability must lie in [0, 1]");
   for (int k = 0; k < 3; ++k)
     XVIT_REQUIRE(c.max_displacement[k] >= 0.f && isfinite(c.max_displacement[k]), "xvit_elastic_draw: max_displacement[%d]=%g must be finite and >= 0", k,
                  c.max_displacement[k]);
   XVIT_REQUIRE(c.locked_borders >= 0 && c.locked_borders <= 3, "xvit_elastic_draw: locked_borders=%d must lie in 0 .. 3", c.locked_borders);
-  XVIT_REQUIRE(((uintptr_t)field & 15) == 0 && ((uintptr_t)erec & 15) == 0, "xvit_elastic_draw: the field and the record must be 16-byte aligned");
-  XVIT_REQUIRE(((uintptr_t)counter & 7) == 0, "xvit_elastic_draw: the counter must be 8-byte aligned");
-  XVIT_REQUIRE(counter || !advance, "xvit_elastic_draw: advance needs a counter");
+  XVIT_ELASTIC_REQUIRE_ALIGNED("xvit_elastic_draw");
+  XVIT_REQUIRE_COUNTER("xvit_elastic_draw", counter, advance);
   hipLaunchKernelGGL(xvit::elastic_draw_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, c, field, erec, Gz, Gy, Gx, seed, counter);
   if (advance) hipLaunchKernelGGL(xvit::elastic_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, counter);
   return xvit::check_launch("xvit_elastic_draw");
@@ -222,21 +218,19 @@ extern "C" int xvit_augment_apply_elastic(const void* src, int src_dtype, void* 
                                           xvit_stream_t stream) {
   XVIT_AUG_APPLY_REQUIRE("xvit_augment_apply_elastic");
   XVIT_REQUIRE(M > 0 && nvol % M == 0, "xvit_augment_apply_elastic: nvol=%d is no multiple of M=%d", nvol, M);
-  XVIT_REQUIRE(xvit::grid_ok(Gz) && xvit::grid_ok(Gy) && xvit::grid_ok(Gx), "xvit_augment_apply_elastic: grid %d x %d x %d: every axis needs 4 .. %d control points",
-               Gz, Gy, Gx, XVIT_ELASTIC_MAX_GRID);
+  XVIT_ELASTIC_REQUIRE_GRID("xvit_augment_apply_elastic");
   XVIT_REQUIRE(field && erec, "xvit_augment_apply_elastic: null field or record");
-  XVIT_REQUIRE(((uintptr_t)field & 15) == 0 && ((uintptr_t)erec & 15) == 0, "xvit_augment_apply_elastic: the field and the record must be 16-byte aligned");
+  XVIT_ELASTIC_REQUIRE_ALIGNED("xvit_augment_apply_elastic");
   const xvit::AugGeom g = xvit::make_geom(Ds, Hs, Ws, D, H, W);
   const xvit::ElasticGeom e{Gz, Gy, Gx, xvit::grid_step(Gz, D), xvit::grid_step(Gy, H), xvit::grid_step(Gx, W)};
-  hipStream_t s = (hipStream_t)stream;
-#define XVIT_ELA_CASE(SD, S, DD, T) \
-  if (src_dtype == SD && dst_dtype == DD) xvit::launch_apply_elastic<S, T>(src, dst, params, field, erec, nvol, M, g, e, pad_value, s)
-  XVIT_ELA_CASE(XVIT_I16, int16_t, XVIT_BF16, xvit::bf16);
-  XVIT_ELA_CASE(XVIT_I16, int16_t, XVIT_F32, float);
-  XVIT_ELA_CASE(XVIT_BF16, xvit::bf16, XVIT_BF16, xvit::bf16);
-  XVIT_ELA_CASE(XVIT_BF16, xvit::bf16, XVIT_F32, float);
-  XVIT_ELA_CASE(XVIT_F32, float, XVIT_BF16, xvit::bf16);
-  XVIT_ELA_CASE(XVIT_F32, float, XVIT_F32, float);
-#undef XVIT_ELA_CASE
+  const xvit::AugBricks b(g);
+  xvit::by_src_dtype(src_dtype, [&](auto sd) {
+    xvit::by_dtype(dst_dtype, [&](auto dd) {
+      using S = decltype(sd);
+      using T = decltype(dd);
+      hipLaunchKernelGGL((xvit::augment_apply_elastic_kernel<S, T>), dim3(b.blocks(nvol)), dim3(256), 0, (hipStream_t)stream, (const S*)src, (T*)dst, params,
+                         field, erec, M, g, e, b.lx, b.nbx, b.nby, b.nbz, pad_value);
+    });
+  });
   return xvit::check_launch("xvit_augment_apply_elastic");
 }

@@ -2,6 +2,7 @@
 // buffer_load ... lds (LDS-DMA), ds_read_b64_tr_b16.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <mutex>
@@ -73,6 +74,11 @@ static void by_dtype(int dtype, F&& f) {   // XVIT_F32 / XVIT_BF16 (host-checked
   if (dtype == XVIT_F32) f(float{});
   else f(bf16{});
 }
+template <class F>
+static void by_src_dtype(int dtype, F&& f) {   // by_dtype and XVIT_I16: the entry points that read raw volumes
+  if (dtype == XVIT_I16) f(int16_t{});
+  else by_dtype(dtype, f);
+}
 
 #define XVIT_REQUIRE(cond, ...)            \
   do {                                     \
@@ -81,6 +87,14 @@ static void by_dtype(int dtype, F&& f) {   // XVIT_F32 / XVIT_BF16 (host-checked
       return XVIT_ERR_ARG;                 \
     }                                      \
   } while (0)
+
+// What the draw entry points of the input stage (augment, elastic, contrast) refuse alike: under the caller's name, or as a predicate
+// where the message is the caller's own.
+#define XVIT_REQUIRE_COUNTER(who, counter, advance)                                                  \
+  XVIT_REQUIRE(((uintptr_t)(counter) & 7) == 0, who ": the counter must be 8-byte aligned");         \
+  XVIT_REQUIRE((counter) || !(advance), who ": advance needs a counter")
+static inline bool prob_ok(float p) { return p >= 0.f && p <= 1.f; }   // false for NaN
+static inline bool range_ok(float lo, float hi) { return lo <= hi && isfinite(lo) && isfinite(hi); }
 
 // ---- device helpers ------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
@@ -279,14 +293,22 @@ __device__ __forceinline__ uint32_t hash32(uint64_t seed, uint64_t idx) {
 }
 
 __device__ __forceinline__ uint32_t draw24(uint64_t seed, uint64_t idx) { return hash32(seed, idx) & 0xFFFFFFu; }   // uniform on [0, 2^24)
-constexpr float kTwo24 = 16777216.0f;
+constexpr float kTwo24 = 16777216.0f, kInv24 = 1.0f / kTwo24;
+__device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) { return (float)draw24(seed, idx) * kInv24; }   // [0, 1), exact
+__device__ __forceinline__ float uniform_in(uint64_t seed, uint64_t idx, float lo, float hi) {                          // [lo, hi], clamped
+  return fminf(fmaxf(fmaf(uniform01(seed, idx), hi - lo, lo), lo), hi);
+}
 
 // A captured step (HIP graph) freezes every kernel argument, the dropout seeds included.  A launch may therefore carry the device address
 // of an epoch counter (xvit_set_dropout_epoch): the seed a kernel then uses is seed + epoch * odd constant, read at run time, so that a
 // replay whose graph increments the counter first draws new masks — the same ones in its forward and its backward.
+constexpr uint64_t kSeedStride = 0xD1B54A32D192ED03ull;
 __device__ __forceinline__ uint64_t drop_seed_at(uint64_t seed, const uint64_t* __restrict__ epoch) {
-  return epoch ? seed + *epoch * 0xD1B54A32D192ED03ull : seed;
+  return epoch ? seed + *epoch * kSeedStride : seed;
 }
+// The draw kernels of the input stage step their seed the same way by the call index `count` they read from their counter (0 without
+// one), and xor the salt that keeps their stream apart from the other stages' under one seed.
+__device__ __forceinline__ uint64_t draw_seed(uint64_t seed, uint64_t count, uint64_t salt) { return (seed + count * kSeedStride) ^ salt; }
 
 // Dropout at rate p as a launch carries it.  Element idx is kept iff its 24-bit draw >= p 2^24 and then scaled by inv = 1 / (1 - p): the
 // mask of xvit_dropout on a contiguous tensor with this seed, regenerated wherever it is needed (forward and backward), never stored.

@@ -40,7 +40,7 @@ NSTAT = _lib.STATS_NSTAT
 ELASTIC_MAX_GRID, ELASTIC_NREC = _lib.ELASTIC_MAX_GRID, _lib.ELASTIC_NREC
 ELASTIC_FLAG, ELASTIC_U, ELASTIC_MAX_ABS = 0, 1, 2     # slots of an elastic record: enum XVIT_ELASTIC_* of include/xvit.h
 _NORM_MODES = {None: _lib.NORM_STATS_ONLY, "zscore": _lib.NORM_ZSCORE, "window": _lib.NORM_WINDOW}
-_COUNTER_STRIDE = 0xD1B54A32D192ED03   # seed' = seed + call index * this (mod 2^64), on the host here and in the draw kernel alike
+_COUNTER_STRIDE = 0xD1B54A32D192ED03   # seed' = seed + call index * this (mod 2^64): kSeedStride of csrc/xvit_common.h, on the host
 _MASK64 = (1 << 64) - 1
 
 
@@ -186,18 +186,19 @@ def volume_stats(raw, foreground_above=0.0, percentiles=None) -> VolumeStats:
     return VolumeStats(stats)
 
 
-def _prob(name, p):
+def _prob(who, name, p):
     p = float(p)
     if not 0.0 <= p <= 1.0:
-        raise ValueError(f"VolumeAugment: {name}={p} is not a probability")
+        raise ValueError(f"{who}: {name}={p} is not a probability")
     return p
 
 
-def _ordered(name, r):
-    lo, hi = (float(v) for v in r)
-    if not lo <= hi:
-        raise ValueError(f"VolumeAugment: {name}=({lo}, {hi}) is reversed")
-    return lo, hi
+def _ordered(who, name, r, finite=False):
+    """(lo, hi) with lo <= hi; finite=True refuses an infinite end as well, and says so."""
+    r = tuple(float(v) for v in r)
+    if len(r) != 2 or not r[0] <= r[1] or (finite and not all(v - v == 0.0 for v in r)):
+        raise ValueError(f"{who}: {name}={r} is reversed" + (" or not finite" if finite else ""))
+    return r
 
 
 def _half_widths(name, r):
@@ -207,7 +208,65 @@ def _half_widths(name, r):
     return r
 
 
-class VolumeAugment(torch.nn.Module):
+def _check_volumes(who, raw, dims, dtypes, why=""):
+    """The checks both stages make of their input: a contiguous GPU tensor [B, M, (1,) dims] of one of dtypes."""
+    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
+        raise RuntimeError(f"{who}: the volumes must be a GPU tensor; this stage has no CPU path")
+    if not (raw.dim() == 5 or (raw.dim() == 6 and raw.shape[2] == 1)):
+        raise ValueError(f"{who}: need [B, M, {dims}] or [B, M, 1, {dims}], got {tuple(raw.shape)}")
+    if raw.dtype not in dtypes:
+        raise TypeError(f"{who}: {raw.dtype} volumes are not supported ({', '.join(str(d).split('.')[1] for d in dtypes)})")
+    if not raw.is_contiguous():
+        raise ValueError(f"{who}: the volumes must be contiguous{why}")
+    return raw
+
+
+class _CallIndexed(torch.nn.Module):
+    """What the random stages share: call k draws from seed + k * stride (mod 2^64).  k is self.calls on the host, or, capturable, a device
+    counter that the draw kernel reads and advances, so that a captured call draws anew at every replay; the counter and the static tables
+    such a call needs are allocated here, outside a capture only."""
+
+    _WHO = ""                      # the stage's name in its messages
+
+    def __init__(self, seed, capturable):
+        super().__init__()
+        self.seed, self.capturable = int(seed), bool(capturable)
+        self.calls = 0             # host call index (capturable: see call_index)
+        self._counter = None       # capturable: the device call index
+        self._tables = {}          # capturable: one static table per (B, M, device)
+
+    @property
+    def call_index(self) -> int:
+        """Training calls made so far (capturable: read from the device counter, a host synchronisation)."""
+        return int(self._counter.item()) if self._counter is not None else self.calls
+
+    def _static_table(self, B, M, nparam, device, more=None):
+        """A table for one call: a new one, or, capturable, the static one of (B, M, device); more(key) allocates what else the stage
+        keeps per key, together with it."""
+        if not self.capturable:
+            return torch.empty(B, M, nparam, dtype=torch.float32, device=device)
+        key = (B, M, device)
+        if key not in self._tables or self._counter is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._WHO}(capturable=True): call the stage once on this batch shape before capturing it; "
+                                   "its table and counter must not be allocated inside the graph")
+            self._tables[key] = torch.empty(B, M, nparam, dtype=torch.float32, device=device)
+            if self._counter is None:
+                self._counter = torch.zeros(1, dtype=torch.int64, device=device)
+            if more is not None:
+                more(key)
+        return self._tables[key]
+
+    def _draw(self, launch, advance):
+        """launch(seed, counter, advance) on this call's index, which `advance` then moves on."""
+        if self.capturable:
+            launch(self.seed, self._counter, advance)
+        else:
+            launch((self.seed + self.calls * _COUNTER_STRIDE) & _MASK64, None, False)
+            self.calls += int(advance)
+
+
+class VolumeAugment(_CallIndexed):
     """Pad / crop to img_size, one random affine resample (flips, rotation about the volume centre, per-axis zoom, translation) and one
     random intensity transform (scale, shift, Gaussian noise), in two launches: the draw into a readable table and the resample.
     normalize="zscore" | "window" adds two launches between them (xvit.augment.volume_stats, folded into the table): the drawn scale /
@@ -226,12 +285,15 @@ class VolumeAugment(torch.nn.Module):
     on the same call index) and is off in eval(); last_elastic holds the ElasticField of the last call (None when nothing was drawn).  A
     displacement above half a control cell is refused unless elastic_allow_folding is set."""
 
+    _WHO = "VolumeAugment"
+
     def __init__(self, img_size, pad_value=-1.0, flip_prob=(.5, .5, .5), rotate_prob=.5, rotate_range=(.26, .26, .26), zoom_prob=.5,
                  zoom_range=(.9, 1.1), translate_prob=.5, translate_range=(8, 8, 8), scale_intensity_prob=.5, scale_intensity_range=(.9, 1.1),
                  shift_intensity_prob=.5, shift_intensity_range=(-.1, .1), noise_prob=.2, noise_std=.05, intensity_scale=1.0, intensity_shift=0.0,
                  out_dtype=torch.bfloat16, seed=0, capturable=False, normalize=None, foreground_above=0.0, percentiles=(0.005, 0.995), clip=True,
                  elastic_prob=0.0, elastic_control_points=7, elastic_max_displacement=7.5, elastic_locked_borders=2, elastic_allow_folding=False):
-        super().__init__()
+        super().__init__(seed, capturable)
+        who = self._WHO
         self.img_size = tuple(int(v) for v in img_size)
         if len(self.img_size) != 3 or min(self.img_size) <= 0:
             raise ValueError(f"VolumeAugment: img_size={img_size} needs three positive sizes")
@@ -241,15 +303,15 @@ class VolumeAugment(torch.nn.Module):
         if len(flip_prob) != 3:
             raise ValueError("VolumeAugment: flip_prob needs one probability per axis")
         c = _lib.AugmentConfig()
-        c.flip_prob[:] = [_prob("flip_prob", p) for p in flip_prob]
-        c.rotate_prob, c.rotate_range[:] = _prob("rotate_prob", rotate_prob), _half_widths("rotate_range", rotate_range)
-        c.zoom_prob, c.zoom_range[:] = _prob("zoom_prob", zoom_prob), _ordered("zoom_range", zoom_range)
+        c.flip_prob[:] = [_prob(who, "flip_prob", p) for p in flip_prob]
+        c.rotate_prob, c.rotate_range[:] = _prob(who, "rotate_prob", rotate_prob), _half_widths("rotate_range", rotate_range)
+        c.zoom_prob, c.zoom_range[:] = _prob(who, "zoom_prob", zoom_prob), _ordered(who, "zoom_range", zoom_range)
         if not c.zoom_range[0] > 0:
             raise ValueError(f"VolumeAugment: zoom_range={tuple(zoom_range)} must be positive")
-        c.translate_prob, c.translate_range[:] = _prob("translate_prob", translate_prob), _half_widths("translate_range", translate_range)
-        c.scale_prob, c.scale_range[:] = _prob("scale_intensity_prob", scale_intensity_prob), _ordered("scale_intensity_range", scale_intensity_range)
-        c.shift_prob, c.shift_range[:] = _prob("shift_intensity_prob", shift_intensity_prob), _ordered("shift_intensity_range", shift_intensity_range)
-        c.noise_prob, c.noise_std = _prob("noise_prob", noise_prob), float(noise_std)
+        c.translate_prob, c.translate_range[:] = _prob(who, "translate_prob", translate_prob), _half_widths("translate_range", translate_range)
+        c.scale_prob, c.scale_range[:] = _prob(who, "scale_intensity_prob", scale_intensity_prob), _ordered(who, "scale_intensity_range", scale_intensity_range)
+        c.shift_prob, c.shift_range[:] = _prob(who, "shift_intensity_prob", shift_intensity_prob), _ordered(who, "shift_intensity_range", shift_intensity_range)
+        c.noise_prob, c.noise_std = _prob(who, "noise_prob", noise_prob), float(noise_std)
         if not c.noise_std >= 0:
             raise ValueError(f"VolumeAugment: noise_std={noise_std} must be >= 0")
         c.intensity_scale, c.intensity_shift = float(intensity_scale), float(intensity_shift)
@@ -258,7 +320,7 @@ class VolumeAugment(torch.nn.Module):
         e.flip_prob[:] = [0.0, 0.0, 0.0]
         e.rotate_prob = e.zoom_prob = e.translate_prob = e.scale_prob = e.shift_prob = e.noise_prob = 0.0
         self._eval_config = e
-        self.pad_value, self.out_dtype, self.seed, self.capturable = float(pad_value), out_dtype, int(seed), bool(capturable)
+        self.pad_value, self.out_dtype = float(pad_value), out_dtype
         try:
             self.norm_config = norm_config(normalize, foreground_above, percentiles, clip)
         except ValueError as e:
@@ -268,9 +330,6 @@ class VolumeAugment(torch.nn.Module):
                                                                          elastic_locked_borders, elastic_allow_folding)
         self._elastic = {}         # capturable: one static ElasticField per (B, device)
         self.last_elastic = None
-        self.calls = 0             # host call index (capturable: see call_index)
-        self._counter = None       # capturable: the device call index
-        self._tables = {}          # capturable: one static table per (B, M, device)
         self._stats = {}           # capturable: one static statistics table per (B, M, device)
         self._workspaces = {}      # normalize: the histogram workspace per (B M, device), zero between calls
         self.last_params = None
@@ -280,7 +339,7 @@ class VolumeAugment(torch.nn.Module):
         """_lib.ElasticConfig and the control grid (Gz, Gy, Gx) from the constructor's arguments.  With prob > 0 a displacement above half a
         control cell, 0.5 (n - 1) / (G - 3) voxels, is refused unless allow_folding: beyond it the map q + u(q) can fold."""
         c = _lib.ElasticConfig()
-        c.prob = _prob("elastic_prob", prob)
+        c.prob = _prob(self._WHO, "elastic_prob", prob)
         grid = (control_points,) * 3 if isinstance(control_points, int) else tuple(control_points)
         if len(grid) != 3 or not all(isinstance(n, int) and 4 <= n <= ELASTIC_MAX_GRID for n in grid):
             raise ValueError(f"VolumeAugment: elastic_control_points={control_points} needs one or three ints in 4 .. {ELASTIC_MAX_GRID}")
@@ -301,42 +360,20 @@ class VolumeAugment(torch.nn.Module):
         c.locked_borders = locked_borders
         return c, grid
 
-    @property
-    def call_index(self) -> int:
-        """Training calls made so far (capturable: read from the device counter, a host synchronisation)."""
-        return int(self._counter.item()) if self._counter is not None else self.calls
-
-    @staticmethod
-    def _volumes(raw):
-        if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
-            raise RuntimeError("VolumeAugment: the volumes must be a GPU tensor; this stage has no CPU path")
-        if raw.dim() == 6 and raw.shape[2] == 1:
-            raw = raw[:, :, 0]
-        if raw.dim() != 5:
-            raise ValueError(f"VolumeAugment: need [B, M, Ds, Hs, Ws] or [B, M, 1, Ds, Hs, Ws], got {tuple(raw.shape)}")
-        if raw.dtype not in (torch.int16, torch.bfloat16, torch.float32):
-            raise TypeError(f"VolumeAugment: {raw.dtype} volumes are not supported (int16, bfloat16, float32)")
-        if not raw.is_contiguous():
-            raise ValueError("VolumeAugment: the volumes must be contiguous (the source is read once, in place)")
-        return raw
+    @classmethod
+    def _volumes(cls, raw):
+        raw = _check_volumes(cls._WHO, raw, "Ds, Hs, Ws", (torch.int16, torch.bfloat16, torch.float32), " (the source is read once, in place)")
+        return raw[:, :, 0] if raw.dim() == 6 else raw
 
     def _table(self, B, M, device):
-        if not self.capturable:
-            return torch.empty(B, M, NPARAM, dtype=torch.float32, device=device)
-        key = (B, M, device)
-        if key not in self._tables or self._counter is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("VolumeAugment(capturable=True): call the stage once on this batch shape before capturing it; "
-                                   "its table and counter must not be allocated inside the graph")
-            self._tables[key] = torch.empty(B, M, NPARAM, dtype=torch.float32, device=device)
-            if self._counter is None:
-                self._counter = torch.zeros(1, dtype=torch.int64, device=device)
+        def more(key):         # the statistics, their workspace and the elastic field of the same batch shape
             if self.normalize is not None:
                 self._stats[key] = torch.empty(B, M, NSTAT, dtype=torch.float64, device=device)
                 self._workspaces[(B * M, device)] = ops.volume_stats_workspace(B * M, device)
             if self.elastic_config.prob > 0.0:
                 self._elastic[(B, device)] = ElasticField.zeros(B, self.elastic_grid, device)
-        return self._tables[key]
+
+        return self._static_table(B, M, NPARAM, device, more)
 
     def _normalise(self, raw, table):
         """Statistics of raw, folded into the table just drawn (two launches) -> VolumeStats."""
@@ -355,11 +392,7 @@ class VolumeAugment(torch.nn.Module):
         """One table for B x M volumes of vol_shape; advances the call index in training mode."""
         table = self._table(B, M, device)
         config = self.config if self.training else self._eval_config
-        if self.capturable:
-            ops.augment_draw(config, table, vol_shape, self.img_size, self.seed, self._counter, advance=self.training)
-        else:
-            ops.augment_draw(config, table, vol_shape, self.img_size, (self.seed + self.calls * _COUNTER_STRIDE) & _MASK64)
-            self.calls += int(self.training)
+        self._draw(lambda *at: ops.augment_draw(config, table, vol_shape, self.img_size, *at), advance=self.training)
         return AugmentParams(table)
 
     def draw_elastic(self, B, M, device) -> ElasticField:
@@ -367,11 +400,10 @@ class VolumeAugment(torch.nn.Module):
         if self.capturable:
             self._table(B, M, device)                      # the static buffers and the counter are allocated together, outside a capture
             el = self._elastic[(B, device)]
-            ops.elastic_draw(self.elastic_config, el.field, el.record, self.seed, self._counter, advance=False)
         else:
             el = ElasticField(torch.empty((B, 3) + self.elastic_grid, dtype=torch.float32, device=device),
                               torch.empty(B, ELASTIC_NREC, dtype=torch.float32, device=device))
-            ops.elastic_draw(self.elastic_config, el.field, el.record, (self.seed + self.calls * _COUNTER_STRIDE) & _MASK64)
+        self._draw(lambda *at: ops.elastic_draw(self.elastic_config, el.field, el.record, *at), advance=False)
         return el
 
     def apply(self, raw, params, out_dtype=None, elastic=None):
@@ -448,7 +480,7 @@ class ContrastParams:
         return ContrastParams(self.table.clone())
 
 
-class ContrastAugment(torch.nn.Module):
+class ContrastAugment(_CallIndexed):
     """Random Gaussian blur (per-axis sigma in voxels), smooth multiplicative bias field (order-2 polynomial in the normalised voxel
     coordinates, exponentiated) and gamma (g = exp(beta), inside gamma_window only), drawn per (sample, modality) and applied in this fixed
     order by one fused kernel behind VolumeAugment: `con(aug(raw))`, or torch.nn.Sequential(aug, con).  Two launches: the draw into a
@@ -458,26 +490,17 @@ class ContrastAugment(torch.nn.Module):
     Call k uses seed + k; eval() returns its input tensor itself (no launch, no table, call index not advanced).  capturable=True keeps k
     in a device counter, as VolumeAugment does: call the stage once on the batch shape before capturing it."""
 
+    _WHO = "ContrastAugment"
+
     def __init__(self, blur_prob=.2, blur_sigma_range=(.5, 1.5), blur_isotropic=False, bias_prob=.2, bias_coeff=.3, gamma_prob=.3,
                  log_gamma_range=(-.3, .3), gamma_window=(0.0, 1.0), out_dtype=None, seed=0, capturable=False):
-        super().__init__()
-        who = "ContrastAugment"
+        super().__init__(seed, capturable)
+        who = self._WHO
         if out_dtype not in (None, torch.bfloat16, torch.float32):
             raise ValueError(f"{who}: out_dtype={out_dtype} must be None (the input's), torch.bfloat16 or torch.float32")
         c = _lib.ContrastConfig()
-        for name, p in (("blur_prob", blur_prob), ("bias_prob", bias_prob), ("gamma_prob", gamma_prob)):
-            p = float(p)
-            if not 0.0 <= p <= 1.0:
-                raise ValueError(f"{who}: {name}={p} is not a probability")
-            setattr(c, name, p)
-
-        def ordered(name, r):
-            r = tuple(float(v) for v in r)
-            if len(r) != 2 or not r[0] <= r[1] or not all(v - v == 0.0 for v in r):
-                raise ValueError(f"{who}: {name}={r} is reversed or not finite")
-            return r
-
-        c.blur_sigma_range[:] = ordered("blur_sigma_range", blur_sigma_range)
+        c.blur_prob, c.bias_prob, c.gamma_prob = _prob(who, "blur_prob", blur_prob), _prob(who, "bias_prob", bias_prob), _prob(who, "gamma_prob", gamma_prob)
+        c.blur_sigma_range[:] = _ordered(who, "blur_sigma_range", blur_sigma_range, finite=True)
         if not (c.blur_sigma_range[0] > 0.0 and c.blur_sigma_range[1] <= 2.0):
             raise ValueError(f"{who}: blur_sigma_range={tuple(blur_sigma_range)} needs 0 < lo <= hi <= 2.0 (the radius ceil(3 sigma) is capped at "
                              f"{CON_MAX_RADIUS} voxels)")
@@ -485,57 +508,28 @@ class ContrastAugment(torch.nn.Module):
         c.bias_coeff = float(bias_coeff)
         if not (c.bias_coeff >= 0.0 and c.bias_coeff - c.bias_coeff == 0.0):
             raise ValueError(f"{who}: bias_coeff={bias_coeff} must be finite and >= 0")
-        c.log_gamma_range[:] = ordered("log_gamma_range", log_gamma_range)
-        c.gamma_window[:] = ordered("gamma_window", gamma_window)
+        c.log_gamma_range[:] = _ordered(who, "log_gamma_range", log_gamma_range, finite=True)
+        c.gamma_window[:] = _ordered(who, "gamma_window", gamma_window, finite=True)
         if not c.gamma_window[0] < c.gamma_window[1]:
             raise ValueError(f"{who}: gamma_window={tuple(gamma_window)} needs lo < hi")
         self.config = c
-        self.out_dtype, self.seed, self.capturable = out_dtype, int(seed), bool(capturable)
-        self.calls = 0             # host call index (capturable: see call_index)
-        self._counter = None       # capturable: the device call index
-        self._tables = {}          # capturable: one static table per (B, M, device)
+        self.out_dtype = out_dtype
         self.last_params = None
 
-    @property
-    def call_index(self) -> int:
-        """Training calls made so far (capturable: read from the device counter, a host synchronisation)."""
-        return int(self._counter.item()) if self._counter is not None else self.calls
-
-    @staticmethod
-    def _volumes(img):
-        if not isinstance(img, torch.Tensor) or not img.is_cuda:
-            raise RuntimeError("ContrastAugment: the volumes must be a GPU tensor; this stage has no CPU path")
-        if not (img.dim() == 5 or (img.dim() == 6 and img.shape[2] == 1)):
-            raise ValueError(f"ContrastAugment: need [B, M, D, H, W] or [B, M, 1, D, H, W], got {tuple(img.shape)}")
-        if img.dtype not in (torch.bfloat16, torch.float32):
-            raise TypeError(f"ContrastAugment: {img.dtype} volumes are not supported (bfloat16, float32)")
-        if not img.is_contiguous():
-            raise ValueError("ContrastAugment: the volumes must be contiguous")
+    @classmethod
+    def _volumes(cls, img):
+        img = _check_volumes(cls._WHO, img, "D, H, W", (torch.bfloat16, torch.float32))
         if img.requires_grad:
             raise RuntimeError("ContrastAugment: the stage has no backward; detach the volumes")
         return img
 
     def _table(self, B, M, device):
-        if not self.capturable:
-            return torch.empty(B, M, CON_NPARAM, dtype=torch.float32, device=device)
-        key = (B, M, device)
-        if key not in self._tables or self._counter is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("ContrastAugment(capturable=True): call the stage once on this batch shape before capturing it; "
-                                   "its table and counter must not be allocated inside the graph")
-            self._tables[key] = torch.empty(B, M, CON_NPARAM, dtype=torch.float32, device=device)
-            if self._counter is None:
-                self._counter = torch.zeros(1, dtype=torch.int64, device=device)
-        return self._tables[key]
+        return self._static_table(B, M, CON_NPARAM, device)
 
     def draw(self, B, M, device) -> ContrastParams:
         """One table for B x M volumes; advances the call index."""
         table = self._table(B, M, device)
-        if self.capturable:
-            ops.contrast_draw(self.config, table, self.seed, self._counter, advance=True)
-        else:
-            ops.contrast_draw(self.config, table, (self.seed + self.calls * _COUNTER_STRIDE) & _MASK64)
-            self.calls += 1
+        self._draw(lambda *at: ops.contrast_draw(self.config, table, *at), advance=True)
         return ContrastParams(table)
 
     def apply(self, img, params, out_dtype=None):

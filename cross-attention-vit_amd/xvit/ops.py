@@ -102,6 +102,10 @@ def _dt(t) -> int:
     raise TypeError(f"xvit: unsupported dtype {t.dtype}")
 
 
+def _seed64(seed) -> int:
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 def _rows2d(t):
     """Leading dimension of a 2-D row-major view."""
     assert t.dim() == 2 and t.stride(1) == 1, f"need a row-major 2-D tensor, got shape {tuple(t.shape)} strides {t.stride()}"
@@ -912,7 +916,7 @@ def mix_draw(config, table, vol_size, seed):
     _mix_table(table, B, "mix_draw")
     D, H, W = vol_size
     _run("mix_draw", table.numel() * 4.0, "byte",
-         lambda: _lib.load().xvit_mix_draw(C.byref(config), _ptr(table), B, int(D), int(H), int(W), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "xvit_mix_draw")
+         lambda: _lib.load().xvit_mix_draw(C.byref(config), _ptr(table), B, int(D), int(H), int(W), _seed64(seed), _stream()), "xvit_mix_draw")
     return table
 
 
@@ -964,35 +968,55 @@ def resize_pad_crop_i16(vol, img_size, pad_value=-1.0):
 I16 = 2   # XVIT_I16: source volumes of augment_apply and volume_stats only
 
 
+def _src_dt(t) -> int:
+    return I16 if t.dtype == torch.int16 else _dt(t)
+
+
+def _counter_arg(counter, what):
+    """The optional call counter of a draw (augment_draw) is checked here, once for the three of them."""
+    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
+        raise RuntimeError(f"{what}: the counter is a one-element int64 GPU tensor (or None)")
+
+
 def augment_draw(config, params, vol_shape, img_size, seed, counter=None, advance=False):
     """xvit_augment_draw (include/xvit.h): fill params [B, M, 32] (fp32) with one augmentation record per volume drawn from `config`
     (_lib.AugmentConfig) and `seed`; vol_shape / img_size are the source and destination (D, H, W).  counter: optional one-element int64
     device tensor mixed into the seed at kernel run time, advanced by one after it is read when advance is set."""
     assert params.dtype == torch.float32 and params.dim() == 3 and params.shape[2] == _lib.AUG_NPARAM and params.is_contiguous()
-    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-        raise RuntimeError("augment_draw: the counter is a one-element int64 GPU tensor (or None)")
+    _counter_arg(counter, "augment_draw")
     B, M = params.shape[:2]
     (Ds, Hs, Ws), (D, H, W) = vol_shape, img_size
     _run("augment_draw", params.numel() * 4.0, "byte",
-         lambda: _lib.load().xvit_augment_draw(C.byref(config), _ptr(params), B, M, Ds, Hs, Ws, D, H, W, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter),
+         lambda: _lib.load().xvit_augment_draw(C.byref(config), _ptr(params), B, M, Ds, Hs, Ws, D, H, W, _seed64(seed), _ptr(counter),
                                                int(bool(advance)), _stream()),
          "xvit_augment_draw")
     return params
 
 
-def augment_apply(src, params, img_size, pad_value=-1.0, out_dtype=torch.bfloat16):
-    """xvit_augment_apply (include/xvit.h): src [B, M, Ds, Hs, Ws] (int16, bf16 or fp32) through the records params [B, M, 32] ->
-    [B, M, 1, D, H, W] in out_dtype (bf16 or fp32): pad / crop, affine resample (or the exact copy), a v + b, noise, one rounding."""
+def _augment_apply(name, src, params, img_size, pad_value, out_dtype, elastic=None):
+    """augment_apply and augment_apply_elastic: the latter passes elastic = (field, erec), checked before anything is allocated."""
     assert src.dim() == 5 and src.is_contiguous() and params.dtype == torch.float32 and params.is_contiguous()
     B, M, Ds, Hs, Ws = src.shape
     assert tuple(params.shape) == (B, M, _lib.AUG_NPARAM), f"params {tuple(params.shape)} do not match {B} x {M} volumes"
+    grid = _elastic_tables(*elastic, B, name) if elastic is not None else None
     D, H, W = img_size
     out = torch.empty(B, M, 1, D, H, W, dtype=out_dtype, device=src.device)
-    sdt = I16 if src.dtype == torch.int16 else _dt(src)
-    _run("augment_apply", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
-         lambda: _lib.load().xvit_augment_apply(_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params), B * M, Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
-         "xvit_augment_apply")
+    sdt = _src_dt(src)
+
+    def call():
+        head, tail = (_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params)), (Ds, Hs, Ws, D, H, W, float(pad_value), _stream())
+        if elastic is None:
+            return _lib.load().xvit_augment_apply(*head, B * M, *tail)
+        return _lib.load().xvit_augment_apply_elastic(*head, _ptr(elastic[0]), _ptr(elastic[1]), B * M, M, *grid, *tail)
+
+    _run(name, src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte", call, "xvit_" + name)
     return out
+
+
+def augment_apply(src, params, img_size, pad_value=-1.0, out_dtype=torch.bfloat16):
+    """xvit_augment_apply (include/xvit.h): src [B, M, Ds, Hs, Ws] (int16, bf16 or fp32) through the records params [B, M, 32] ->
+    [B, M, 1, D, H, W] in out_dtype (bf16 or fp32): pad / crop, affine resample (or the exact copy), a v + b, noise, one rounding."""
+    return _augment_apply("augment_apply", src, params, img_size, pad_value, out_dtype)
 
 
 def _elastic_tables(field, erec, B, what):
@@ -1012,10 +1036,9 @@ def elastic_draw(config, field, erec, seed, counter=None, advance=False):
     from `config` (_lib.ElasticConfig) and `seed`.  counter: as in augment_draw."""
     B = field.shape[0] if isinstance(field, torch.Tensor) and field.dim() == 5 else 0
     Gz, Gy, Gx = _elastic_tables(field, erec, B, "elastic_draw")
-    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-        raise RuntimeError("elastic_draw: the counter is a one-element int64 GPU tensor (or None)")
+    _counter_arg(counter, "elastic_draw")
     _run("elastic_draw", (field.numel() + erec.numel()) * 4.0, "byte",
-         lambda: _lib.load().xvit_elastic_draw(C.byref(config), _ptr(field), _ptr(erec), B, Gz, Gy, Gx, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter),
+         lambda: _lib.load().xvit_elastic_draw(C.byref(config), _ptr(field), _ptr(erec), B, Gz, Gy, Gx, _seed64(seed), _ptr(counter),
                                                int(bool(advance)), _stream()),
          "xvit_elastic_draw")
     return field, erec
@@ -1024,29 +1047,17 @@ def elastic_draw(config, field, erec, seed, counter=None, advance=False):
 def augment_apply_elastic(src, params, field, erec, img_size, pad_value=-1.0, out_dtype=torch.bfloat16):
     """xvit_augment_apply_elastic (include/xvit.h): augment_apply with the B-spline displacement of field [B, 3, Gz, Gy, Gx] composed into
     the resample of every sample whose erec [B, 8] flag is 1; the other samples are processed as augment_apply processes them."""
-    assert src.dim() == 5 and src.is_contiguous() and params.dtype == torch.float32 and params.is_contiguous()
-    B, M, Ds, Hs, Ws = src.shape
-    assert tuple(params.shape) == (B, M, _lib.AUG_NPARAM), f"params {tuple(params.shape)} do not match {B} x {M} volumes"
-    Gz, Gy, Gx = _elastic_tables(field, erec, B, "augment_apply_elastic")
-    D, H, W = img_size
-    out = torch.empty(B, M, 1, D, H, W, dtype=out_dtype, device=src.device)
-    sdt = I16 if src.dtype == torch.int16 else _dt(src)
-    _run("augment_apply_elastic", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
-         lambda: _lib.load().xvit_augment_apply_elastic(_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params), _ptr(field), _ptr(erec), B * M, M, Gz, Gy, Gx,
-                                                        Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
-         "xvit_augment_apply_elastic")
-    return out
+    return _augment_apply("augment_apply_elastic", src, params, img_size, pad_value, out_dtype, elastic=(field, erec))
 
 
 def contrast_draw(config, params, seed, counter=None, advance=False):
     """xvit_contrast_draw (include/xvit.h): fill params [B, M, 32] (fp32) with one blur / bias / gamma record per volume drawn from `config`
     (_lib.ContrastConfig) and `seed`.  counter: as in augment_draw."""
     assert params.dtype == torch.float32 and params.dim() == 3 and params.shape[2] == _lib.CON_NPARAM and params.is_contiguous()
-    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-        raise RuntimeError("contrast_draw: the counter is a one-element int64 GPU tensor (or None)")
+    _counter_arg(counter, "contrast_draw")
     nvol = params.shape[0] * params.shape[1]
     _run("contrast_draw", params.numel() * 4.0, "byte",
-         lambda: _lib.load().xvit_contrast_draw(C.byref(config), _ptr(params), nvol, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(counter), int(bool(advance)),
+         lambda: _lib.load().xvit_contrast_draw(C.byref(config), _ptr(params), nvol, _seed64(seed), _ptr(counter), int(bool(advance)),
                                                 _stream()),
          "xvit_contrast_draw")
     return params
@@ -1084,7 +1095,7 @@ def volume_stats(src, config, stats, workspace, params=None):
     assert tuple(stats.shape) == (B, M, _lib.STATS_NSTAT), f"stats {tuple(stats.shape)} do not match {B} x {M} volumes"
     if params is not None:
         assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B, M, _lib.AUG_NPARAM)
-    sdt = I16 if src.dtype == torch.int16 else _dt(src)
+    sdt = _src_dt(src)
     try:
         _run("volume_stats", src.numel() * float(src.element_size()), "byte",
              lambda: _lib.load().xvit_volume_stats(_ptr(src), sdt, B * M, nvox, C.byref(config), _ptr(stats), _ptr(params), _ptr(workspace),
@@ -1135,6 +1146,6 @@ def epoch_rank_stats(scores, labels32, preds, perm, n_dev, n_max, R, seed):
     conf = torch.empty(R + 1, Cn, Cn, dtype=torch.int64, device=dev)
     _run("epoch_rank_stats", (R + 1) * Cn * float(n_max) * 16.0, "byte",
          lambda: _lib.load().xvit_epoch_rank_stats(_ptr(scores), _ptr(labels32), _ptr(preds), _ptr(perm), perm.stride(0), _ptr(n_dev), int(n_max), Cn, int(R),
-                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ranks), _ptr(ap), _ptr(conf), _stream()),
+                                                   _seed64(seed), _ptr(ranks), _ptr(ap), _ptr(conf), _stream()),
          "xvit_epoch_rank_stats")
     return ranks, ap, conf
