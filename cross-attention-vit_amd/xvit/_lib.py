@@ -72,6 +72,17 @@ class NormConfig(C.Structure):
 STATS_NSTAT = 8                                        # XVIT_STATS_NSTAT
 STATS_WINDOW_LO, STATS_WINDOW_BINS = 32768, 32768      # XVIT_STATS_WINDOW_*: the keys the histogram kernel counts in LDS
 NORM_STATS_ONLY, NORM_ZSCORE, NORM_WINDOW = 0, 1, 2    # XVIT_NORM_*
+
+
+class CropConfig(C.Structure):
+    """struct xvit_crop_config (include/xvit.h)."""
+    _fields_ = [("mode", i32), ("margin", i32 * 3), ("allow_upscale", i32), ("foreground_above", f32)]
+
+
+BBOX_NREC = 8                                          # XVIT_BBOX_NREC
+BBOX_Z0, BBOX_Z1, BBOX_Y0, BBOX_Y1, BBOX_X0, BBOX_X1, BBOX_COUNT = 0, 1, 2, 3, 4, 5, 6   # XVIT_BBOX_*
+CROP_BOXES_ONLY, CROP_CENTER, CROP_FIT = 0, 1, 2       # XVIT_CROP_*
+AUG_CROP_SCALE = 31                                    # XVIT_AUG_CROP_SCALE
 MAE_MAX_PD = 8192                                      # XVIT_MAE_MAX_PD: the largest patch (voxels) xvit_mae_loss_fwd holds in LDS
 TOKEN_SELECT_MAX_P = 8192                              # XVIT_TOKEN_SELECT_MAX_P: the longest sequence xvit_token_select_draw ranks in LDS
 EPOCH_MAX_C, EPOCH_MAX_B = 64, 8192                    # XVIT_EPOCH_MAX_C, XVIT_EPOCH_MAX_B: the limits of xvit_epoch_metrics_update
@@ -157,6 +168,7 @@ SIGNATURES = {
     "xvit_contrast_draw": [C.POINTER(ContrastConfig), vp, i32, u64, vp, i32, vp],
     "xvit_contrast_apply": [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp],
     "xvit_volume_stats": [vp, i32, i32, i64, C.POINTER(NormConfig), vp, vp, vp, i64, vp],
+    "xvit_volume_bbox": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(CropConfig), vp, vp, vp, vp, i64, vp],
     "xvit_set_option": [C.c_char_p, i32],
     "xvit_set_dropout_epoch": [C.c_void_p],
     "xvit_adam_step": [vp, vp, i32, f32, f32, f32, f32, f32, i32, f32, vp],
@@ -171,7 +183,7 @@ SIGNATURES = {
 }
 EXPORTS = sorted(list(SIGNATURES) + ["xvit_version", "xvit_last_error_string", "xvit_gemm_workspace_bytes", "xvit_linear_f32_workspace_bytes",
                                     "xvit_colsum_workspace_bytes", "xvit_layernorm_bwd_workspace_bytes", "xvit_patch_embed_wgrad_workspace_bytes", "xvit_attn_fp8_workspace_bytes",
-                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes", "xvit_epoch_rank_stats_max_n"])
+                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes", "xvit_volume_bbox_workspace_bytes", "xvit_epoch_rank_stats_max_n"])
 
 _lib = None
 
@@ -204,6 +216,8 @@ def load() -> C.CDLL:
         lib.xvit_patch_embed_wgrad_workspace_bytes.restype = C.c_int64
         lib.xvit_volume_stats_workspace_bytes.argtypes = [i32]
         lib.xvit_volume_stats_workspace_bytes.restype = C.c_int64
+        lib.xvit_volume_bbox_workspace_bytes.argtypes = [i32, i64]
+        lib.xvit_volume_bbox_workspace_bytes.restype = C.c_int64
         lib.xvit_epoch_rank_stats_max_n.argtypes = []
         lib.xvit_epoch_rank_stats_max_n.restype = C.c_int64
         lib.xvit_version.restype = C.c_int

@@ -10,6 +10,9 @@
     aug = xvit.augment.VolumeAugment((128, 128, 128), elastic_prob=.2)       # random elastic deformation inside the same resample
     aug.last_elastic                 # ElasticField: the control grids and records this call drew; aug.apply(raw, params, elastic=...) replays
     xvit.augment.volume_stats(raw)   # the statistics alone
+    aug = xvit.augment.VolumeAugment((128, 128, 128), crop_foreground="fit", crop_margin=4)   # window the foreground, not the volume centre
+    aug.last_crop                    # ForegroundBoxes: every volume's foreground box and the crop of every sample
+    xvit.augment.foreground_boxes(raw)   # the boxes alone
 
     con = xvit.augment.ContrastAugment(blur_prob=.2, bias_prob=.2, gamma_prob=.3, seed=0)      # a second stage behind the first
     img = con(aug(raw))              # Gaussian blur, bias field, gamma: one fused kernel, a NEW tensor of the same shape
@@ -24,6 +27,12 @@ normalize="zscore" | "window" puts a per-volume normalisation in front of the dr
 statistics and normalisation"): exact statistics of the foreground voxels (v > foreground_above) of the WHOLE source volume, from a
 histogram on the device, folded into the table between the draw and the resample.  With clip=True the resampled value is clamped to the
 window [lo, hi] first, pad_value included: the background lands on the window floor.
+
+crop_foreground="center" | "fit" moves the pad / crop window from the centre of the volume to the bounding box of the sample's foreground
+(include/xvit.h, "Foreground bounding box and crop"; what MONAI's CropForegroundd followed by ResizeWithPadOrCropd or a resize does in a
+loader): two launches that fold the box into the table's A | t between the draw and the statistics fold, so the voxels are still
+interpolated once.  The box is the index range of v > crop_above over all modalities of the sample; nothing filters connected components,
+so one isolated bright background voxel widens it.  The box moves the window and masks nothing.
 """
 from __future__ import annotations
 
@@ -35,11 +44,14 @@ NPARAM = _lib.AUG_NPARAM
 # slots of a record: enum XVIT_AUG_* of include/xvit.h, by name
 MATRIX, SCALE, SHIFT, SIGMA, NOISE_SEED, FLAGS, FLIPS, ANGLES, ZOOMS, TRANSLATION = 0, 12, 13, 14, 15, 16, 17, 20, 23, 26
 CLAMP_LO, CLAMP_HI = 29, 30
+CROP_SCALE = _lib.AUG_CROP_SCALE
 FLAG_EXACT, FLAG_CLAMP = 1, 2
 NSTAT = _lib.STATS_NSTAT
 ELASTIC_MAX_GRID, ELASTIC_NREC = _lib.ELASTIC_MAX_GRID, _lib.ELASTIC_NREC
 ELASTIC_FLAG, ELASTIC_U, ELASTIC_MAX_ABS = 0, 1, 2     # slots of an elastic record: enum XVIT_ELASTIC_* of include/xvit.h
 _NORM_MODES = {None: _lib.NORM_STATS_ONLY, "zscore": _lib.NORM_ZSCORE, "window": _lib.NORM_WINDOW}
+BBOX_NREC = _lib.BBOX_NREC
+_CROP_MODES = {None: _lib.CROP_BOXES_ONLY, "center": _lib.CROP_CENTER, "fit": _lib.CROP_FIT}
 _COUNTER_STRIDE = 0xD1B54A32D192ED03   # seed' = seed + call index * this (mod 2^64): kSeedStride of csrc/xvit_common.h, on the host
 _MASK64 = (1 << 64) - 1
 
@@ -80,6 +92,7 @@ class AugmentParams:
     translation = property(lambda s: s.table[..., TRANSLATION:TRANSLATION + 3])
     clamp_lo = property(lambda s: s.table[..., CLAMP_LO])
     clamp_hi = property(lambda s: s.table[..., CLAMP_HI])
+    crop_scale = property(lambda s: s.table[..., CROP_SCALE])     # the k xvit_volume_bbox folded; 0: no crop folded
 
     @property
     def noise_seed(self):
@@ -186,6 +199,61 @@ def volume_stats(raw, foreground_above=0.0, percentiles=None) -> VolumeStats:
     return VolumeStats(stats)
 
 
+class ForegroundBoxes:
+    """Named views of the tables of xvit_volume_bbox: boxes [B, M, 8] (int32; the inclusive index range of every volume's foreground along
+    z, y, x, its voxel count, zero) and crop [B, 8] (int32; the union over the sample's modalities, widened by the margin and clipped, a
+    has-foreground flag, zero).  The tables stay on the device: reading a value is the one host synchronisation."""
+
+    def __init__(self, boxes: torch.Tensor, crop: torch.Tensor):
+        if boxes.dtype != torch.int32 or boxes.dim() != 3 or boxes.shape[2] != BBOX_NREC:
+            raise ValueError(f"ForegroundBoxes: need int32 [B, M, {BBOX_NREC}] boxes, got {boxes.dtype} {tuple(boxes.shape)}")
+        if crop.dtype != torch.int32 or tuple(crop.shape) != (boxes.shape[0], BBOX_NREC):
+            raise ValueError(f"ForegroundBoxes: need an int32 [{boxes.shape[0]}, {BBOX_NREC}] crop, got {crop.dtype} {tuple(crop.shape)}")
+        self.boxes, self.crop = boxes, crop
+
+    lo = property(lambda s: s.crop[:, 0:6:2])              # [B, 3]: the first index of the sample's crop along z, y, x
+    hi = property(lambda s: s.crop[:, 1:6:2])              # ... and the last, inclusive
+    nonempty = property(lambda s: s.crop[:, _lib.BBOX_COUNT])    # 1 = the sample has foreground
+    count = property(lambda s: s.boxes[..., _lib.BBOX_COUNT])    # [B, M]: foreground voxels of every volume
+    volume_lo = property(lambda s: s.boxes[..., 0:6:2])    # [B, M, 3]: every volume's own box (an empty one: lo = size, hi = -1)
+    volume_hi = property(lambda s: s.boxes[..., 1:6:2])
+
+    def clone(self):
+        return ForegroundBoxes(self.boxes.clone(), self.crop.clone())
+
+
+def crop_config(mode=None, margin=0, upscale=False, above=0.0):
+    """_lib.CropConfig from the Python arguments, validated as xvit_volume_bbox validates it."""
+    if mode not in _CROP_MODES:
+        raise ValueError(f"crop_foreground={mode!r} must be None, 'center' or 'fit'")
+    margin = (margin,) * 3 if isinstance(margin, int) and not isinstance(margin, bool) else margin
+    if not isinstance(margin, (tuple, list)) or len(margin) != 3 or not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v < 2 ** 31 for v in margin):
+        raise ValueError(f"crop_margin={margin!r} needs one or three ints >= 0 (voxels, z, y, x)")
+    fg = float(above)
+    if fg != fg:
+        raise ValueError("crop_above is NaN")
+    c = _lib.CropConfig()
+    c.mode, c.margin[:], c.allow_upscale, c.foreground_above = _CROP_MODES[mode], list(margin), int(bool(upscale)), fg
+    return c
+
+
+def _crop_tables(B, M, device):
+    """boxes, crop and a workspace that serves B x M volumes of any size (the chunk rule never gives a volume more parts than an
+    unbounded one gets)."""
+    return (torch.empty(B, M, BBOX_NREC, dtype=torch.int32, device=device), torch.empty(B, BBOX_NREC, dtype=torch.int32, device=device),
+            ops.volume_bbox_workspace(B * M, 2 ** 31 - 1, device))
+
+
+def foreground_boxes(raw, foreground_above=0.0, margin=0) -> ForegroundBoxes:
+    """The foreground boxes of raw [B, M, Ds, Hs, Ws] (int16, bf16 or fp32 on the GPU) over v > foreground_above, and per sample their
+    union widened by margin: two launches, no host synchronisation until the result is read."""
+    raw = VolumeAugment._volumes(raw)
+    config = crop_config(None, margin, False, foreground_above)
+    boxes, crop, workspace = _crop_tables(raw.shape[0], raw.shape[1], raw.device)
+    ops.volume_bbox(raw, config, (1, 1, 1), boxes, crop, workspace)
+    return ForegroundBoxes(boxes, crop)
+
+
 def _prob(who, name, p):
     p = float(p)
     if not 0.0 <= p <= 1.0:
@@ -283,7 +351,14 @@ class VolumeAugment(_CallIndexed):
     +-elastic_max_displacement destination voxels (a float or three, z, y, x), the outer elastic_locked_borders control layers held at
     zero.  It is composed into the one resample (p = A (q + u(q)) + t), costs one launch more (the field's draw, in front of the table's,
     on the same call index) and is off in eval(); last_elastic holds the ElasticField of the last call (None when nothing was drawn).  A
-    displacement above half a control cell is refused unless elastic_allow_folding is set."""
+    displacement above half a control cell is refused unless elastic_allow_folding is set.
+
+    crop_foreground="center" | "fit" adds two launches behind the draw (xvit.augment.foreground_boxes, folded into the table): the pad /
+    crop window moves from the centre of the volume to the box of the sample's foreground v > crop_above (None: foreground_above), taken
+    over all its modalities and widened by crop_margin voxels (an int or three) inside the volume.  "center" keeps the voxel size (the
+    exact copy stays exact); "fit" also zooms out by k = max over the axes of box size / img_size so that the whole box is seen, and
+    zooms in (k < 1) only with crop_upscale.  Like normalize it is preprocessing: not random, and it runs in eval() as in train().
+    last_crop holds the ForegroundBoxes of the last call and last_params.crop_scale the k that was folded."""
 
     _WHO = "VolumeAugment"
 
@@ -291,7 +366,8 @@ class VolumeAugment(_CallIndexed):
                  zoom_range=(.9, 1.1), translate_prob=.5, translate_range=(8, 8, 8), scale_intensity_prob=.5, scale_intensity_range=(.9, 1.1),
                  shift_intensity_prob=.5, shift_intensity_range=(-.1, .1), noise_prob=.2, noise_std=.05, intensity_scale=1.0, intensity_shift=0.0,
                  out_dtype=torch.bfloat16, seed=0, capturable=False, normalize=None, foreground_above=0.0, percentiles=(0.005, 0.995), clip=True,
-                 elastic_prob=0.0, elastic_control_points=7, elastic_max_displacement=7.5, elastic_locked_borders=2, elastic_allow_folding=False):
+                 elastic_prob=0.0, elastic_control_points=7, elastic_max_displacement=7.5, elastic_locked_borders=2, elastic_allow_folding=False,
+                 crop_foreground=None, crop_margin=0, crop_upscale=False, crop_above=None):
         super().__init__(seed, capturable)
         who = self._WHO
         self.img_size = tuple(int(v) for v in img_size)
@@ -332,8 +408,15 @@ class VolumeAugment(_CallIndexed):
         self.last_elastic = None
         self._stats = {}           # capturable: one static statistics table per (B, M, device)
         self._workspaces = {}      # normalize: the histogram workspace per (B M, device), zero between calls
+        try:
+            self._crop_config = crop_config(crop_foreground, crop_margin, crop_upscale, foreground_above if crop_above is None else crop_above)
+        except ValueError as e:
+            raise ValueError(f"VolumeAugment: {e}") from None
+        self.crop_foreground = crop_foreground
+        self._crops = {}           # capturable: the static box tables and workspace per (B, M, device)
         self.last_params = None
         self.last_stats = None
+        self.last_crop = None
 
     def _elastic_arguments(self, prob, control_points, max_displacement, locked_borders, allow_folding):
         """_lib.ElasticConfig and the control grid (Gz, Gy, Gx) from the constructor's arguments.  With prob > 0 a displacement above half a
@@ -366,7 +449,9 @@ class VolumeAugment(_CallIndexed):
         return raw[:, :, 0] if raw.dim() == 6 else raw
 
     def _table(self, B, M, device):
-        def more(key):         # the statistics, their workspace and the elastic field of the same batch shape
+        def more(key):         # the statistics, their workspace, the elastic field and the box tables of the same batch shape
+            if self.crop_foreground is not None:
+                self._crops[key] = _crop_tables(B, M, device)
             if self.normalize is not None:
                 self._stats[key] = torch.empty(B, M, NSTAT, dtype=torch.float64, device=device)
                 self._workspaces[(B * M, device)] = ops.volume_stats_workspace(B * M, device)
@@ -387,6 +472,19 @@ class VolumeAugment(_CallIndexed):
                 self._workspaces[(B * M, raw.device)] = ops.volume_stats_workspace(B * M, raw.device)
         ops.volume_stats(raw, self.norm_config, stats, self._workspaces[(B * M, raw.device)], table)
         return VolumeStats(stats)
+
+    crop_config = property(lambda self: self._crop_config, doc="_lib.CropConfig of the constructor's crop_* arguments")
+
+    def _crop(self, raw, table):
+        """The foreground boxes of raw, folded into the table just drawn (two launches) -> ForegroundBoxes."""
+        B, M = raw.shape[:2]
+        if self.capturable:
+            self._table(B, M, raw.device)                  # the static buffers are allocated together
+            boxes, crop, workspace = self._crops[(B, M, raw.device)]
+        else:
+            boxes, crop, workspace = _crop_tables(B, M, raw.device)
+        ops.volume_bbox(raw, self.crop_config, self.img_size, boxes, crop, workspace, table)
+        return ForegroundBoxes(boxes, crop)
 
     def draw(self, B, M, vol_shape, device) -> AugmentParams:
         """One table for B x M volumes of vol_shape; advances the call index in training mode."""
@@ -429,6 +527,8 @@ class VolumeAugment(_CallIndexed):
             elastic = self.draw_elastic(raw.shape[0], raw.shape[1], raw.device)      # first, on the call index the draw below advances
         self.last_elastic = elastic
         self.last_params = self.draw(raw.shape[0], raw.shape[1], tuple(raw.shape[2:]), raw.device)
+        if self.crop_foreground is not None:
+            self.last_crop = self._crop(raw, self.last_params.table)      # between the draw and the statistics fold
         if self.normalize is not None:
             self.last_stats = self._normalise(raw, self.last_params.table)
         return self.apply(raw, self.last_params, elastic=elastic)

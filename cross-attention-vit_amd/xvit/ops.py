@@ -1108,6 +1108,34 @@ def volume_stats(src, config, stats, workspace, params=None):
     return stats
 
 
+def volume_bbox_workspace(nvol, nvox, device):
+    """The partial-box workspace of volume_bbox for nvol volumes of nvox voxels (xvit_volume_bbox_workspace_bytes); its contents do not
+    matter on entry."""
+    return torch.empty(_lib.load().xvit_volume_bbox_workspace_bytes(int(nvol), int(nvox)), dtype=torch.uint8, device=device)
+
+
+def volume_bbox(src, config, img_size, boxes, crop, workspace, params=None):
+    """xvit_volume_bbox (include/xvit.h): the foreground index ranges of src [B, M, Ds, Hs, Ws] (int16, bf16 or fp32, contiguous) into boxes
+    [B, M, 8] and the per-sample union, widened and clipped, into crop [B, 8] (both int32).  config: _lib.CropConfig.  params: the table
+    [B, M, 32] of augment_draw, into which the crop towards img_size is folded (mode 1 / 2), or None.  workspace:
+    volume_bbox_workspace(B * M, Ds * Hs * Ws, device)."""
+    assert src.dim() == 5 and src.is_contiguous(), f"need contiguous [B, M, Ds, Hs, Ws] volumes, got {tuple(src.shape)}"
+    B, M, Ds, Hs, Ws = src.shape
+    assert boxes.dtype == torch.int32 and boxes.is_contiguous() and tuple(boxes.shape) == (B, M, _lib.BBOX_NREC), \
+        f"boxes {boxes.dtype} {tuple(boxes.shape)} do not match {B} x {M} volumes"
+    assert crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, _lib.BBOX_NREC), \
+        f"crop {crop.dtype} {tuple(crop.shape)} does not match {B} samples"
+    if params is not None:
+        assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B, M, _lib.AUG_NPARAM)
+    D, H, W = img_size
+    sdt = _src_dt(src)
+    _run("volume_bbox", src.numel() * float(src.element_size()), "byte",
+         lambda: _lib.load().xvit_volume_bbox(_ptr(src), sdt, B * M, M, Ds, Hs, Ws, D, H, W, C.byref(config), _ptr(boxes), _ptr(crop), _ptr(params),
+                                              _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+         "xvit_volume_bbox")
+    return boxes, crop
+
+
 def epoch_metrics_update(logits, labels, scores, labels32, preds, state):
     """xvit_epoch_metrics_update (include/xvit.h): append the step's softmax rows, labels and argmax to the epoch buffers at the device-side
     cursor state[0] and fold it into the integer confusion matrix behind the state head.  logits fp32 [B, C] (rows contiguous), labels

@@ -26,10 +26,10 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 317 /* 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 318 /* 0.3.18: xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
-enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply and xvit_volume_stats only */ };
+enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply, xvit_volume_stats and xvit_volume_bbox only */ };
 
 typedef void* xvit_stream_t; /* hipStream_t */
 
@@ -337,7 +337,8 @@ int xvit_resize_pad_crop_i16(const void* src_i16, void* dst_bf16, int nvol, int 
  *                                                            bit 1 = clamp: the resampled value is clamped to [slot 29, slot 30] before a v + b
  *    17..19 flips (1 = the axis is reversed)             20..22 rotation angles, radians (0 when not drawn)
  *    23..25 zooms (1 when not drawn)                     26..28 translation in voxels (0 when not drawn)
- *    29, 30 clamp window lo, hi in SOURCE units (zero as drawn; xvit_volume_stats writes them)                   31  zero
+ *    29, 30 clamp window lo, hi in SOURCE units (zero as drawn; xvit_volume_stats writes them)
+ *    31     the crop scale k folded by xvit_volume_bbox (zero as drawn: no crop folded)
  * Slots 17..28 record what was drawn; xvit_augment_apply reads slots 0..16 and, only when flag bit 1 is set, slots 29 and 30.
  *
  * xvit_augment_draw.  Uniform numbers are u(i) = (hash32(seed', i) & 0xFFFFFF) / 2^24 with the dropout hash (xvit_dropout), seed' = seed +
@@ -485,6 +486,67 @@ typedef struct xvit_norm_config {
 int64_t xvit_volume_stats_workspace_bytes(int nvol);
 int xvit_volume_stats(const void* src, int src_dtype, int nvol, int64_t nvox, const xvit_norm_config* cfg, double* stats, float* params /* NULL: no fold */,
                       void* workspace, int64_t workspace_bytes, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Foreground bounding box and crop (csrc/volume_bbox.hip; stands where a loader runs MONAI's CropForegroundd followed by a resize or
+ * ResizeWithPadOrCropd on the CPU).  xvit_augment_draw windows the source around the centre of the VOLUME; this moves the window to the
+ * foreground.  It is not a second resample: the box is folded into the record's A | t between the draw and the apply, as
+ * xvit_volume_stats folds the normalisation into SCALE / SHIFT, and the voxels are still interpolated once.  The rule is this project's
+ * own; parity with MONAI's numerics is NOT claimed.
+ *
+ * Boxes.  src [nvol, Ds, Hs, Ws] int16 / bf16 / fp32 (only a comparison is needed, so fp32 is supported here), contiguous, aligned to its
+ * element size; a volume has fewer than 2^31 voxels.  F = { (z, y, x) : src[v, z, y, x] > foreground_above }; NaN compares false and is
+ * never foreground, -0.0 is not above 0.  boxes [nvol, XVIT_BBOX_NREC] (int32): slots 0..5 the inclusive index range of F along z, y, x
+ * (XVIT_BBOX_Z0 .. XVIT_BBOX_X1), slot 6 |F|, slot 7 zero.  A volume without foreground gets lo = size, hi = -1, count 0.  There is no
+ * connected-component filtering: one isolated bright background voxel widens the box to itself.
+ *
+ * Sample crop.  The M modalities of a sample (volumes b M .. b M + M - 1; nvol is a multiple of M) are co-registered and share one
+ * spatial transform, so they share one box.  crop [nvol / M, XVIT_BBOX_NREC] (int32): the union of the sample's non-empty volume boxes,
+ * widened by margin[axis] on both sides, then clipped to [0, size - 1]; slot 6 is 1 when the sample has any foreground, else 0; slot 7
+ * zero.  For a sample without foreground the six box slots are 0, size - 1 per axis and nothing is folded into its records.
+ *
+ * Fold (params != NULL, mode != XVIT_CROP_BOXES_ONLY, the sample has foreground), into each of the sample's M records of params
+ * [nvol, XVIT_AUG_NPARAM], in double from the fp32 slots, every written slot rounded once.  Per axis i with [lo, hi] of crop:
+ * s = hi - lo + 1, n the destination size, o the draw's offset (that of xvit_resize_pad_crop_i16 for (source size, n)), c = (n - 1) / 2.
+ *    k = 1 for XVIT_CROP_CENTER;  XVIT_CROP_FIT: k = max_i (s_i / n_i), raised to 1 unless allow_upscale.  kf = fl32(k) is what is
+ *    applied, and what slot XVIT_AUG_CROP_SCALE receives.
+ *    kf == 1:  o'_i = lo_i + offset(s_i, n_i), the centre pad / crop rule applied to the box instead of the volume;
+ *              t_i <- fl32(t_i + (o'_i - o_i)).  A and FLAGS are untouched: an exact record stays exact and the apply is still the copy.
+ *    kf != 1:  cb_i = (lo_i + hi_i) / 2;  A_ij <- fl32(kf A_ij) (the product of two fp32 values is exact in double: one rounding);
+ *              t_i <- fl32(kf (t_i - c_i - o_i) + cb_i);  FLAGS &= ~XVIT_AUG_FLAG_EXACT.  The destination centre lands on the box centre
+ *              plus kf times the drawn translation; rotation, zoom and the elastic displacement (p = A (q + u) + t with the new A, t) stay
+ *              in destination voxels.
+ * No other slot is written.  The statistics fold (slots 12, 13, 16, 29, 30) and this one commute; both read-modify-write slot 16, in
+ * stream order.  The box moves the window; it masks nothing: voxels outside the box but inside the volume are the source's own, and
+ * pad_value appears only outside the VOLUME.
+ *
+ * Two launches, no host read-back, no atomics, no pre-initialised workspace: the pair can be captured in a graph.  (a) A 256-thread
+ * workgroup owns `chunk` consecutive voxels of one volume, read with 16-byte loads (scalar head and tail: a volume's base is only
+ * element-aligned when nvox is odd; rows are not aligned, (z, y, x) comes from the flat index, by two divisions per 16-byte run that
+ * holds foreground), and writes one 8-int partial box with plain stores.  Chunk rule, with nvox = Ds Hs Ws:
+ *    parts = min(max(1, 2048 / nvol), ceil(nvox / 8192));  chunk = ceil(nvox / parts) rounded up to a multiple of 8;
+ *    parts = ceil(nvox / chunk);  part j of a volume owns the flat voxel indices [j chunk, min(nvox, (j + 1) chunk)).
+ * xvit_volume_bbox_workspace_bytes(nvol, nvox) = nvol parts 32 (16-byte aligned, caller-owned, contents irrelevant on entry).
+ * (b) One workgroup per sample reduces its M x parts partials, writes boxes and crop, and thread m folds record m.  Every result is an
+ * integer or computed by one thread in a fixed order: the pair is bit-reproducible.
+ * Argument errors, raised before any launch: null pointers (params may be NULL; boxes and crop may not), an unknown dtype or mode,
+ * nvol <= 0, M <= 0 or nvol not a multiple of M, non-positive sizes or nvox >= 2^31, a negative margin, a NaN foreground_above, boxes /
+ * crop / params / workspace not 16-byte aligned, a workspace that is too small.  cfg is a HOST struct, read during the call.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_BBOX_NREC 8
+enum { XVIT_BBOX_Z0 = 0, XVIT_BBOX_Z1 = 1, XVIT_BBOX_Y0 = 2, XVIT_BBOX_Y1 = 3, XVIT_BBOX_X0 = 4, XVIT_BBOX_X1 = 5, XVIT_BBOX_COUNT = 6 };
+enum { XVIT_CROP_BOXES_ONLY = 0, XVIT_CROP_CENTER = 1, XVIT_CROP_FIT = 2 };
+#define XVIT_AUG_CROP_SCALE 31          /* slot 31 of an augment record: the crop scale k that was folded, 0 = no crop folded */
+typedef struct xvit_crop_config {
+  int mode;                 /* 0 boxes only, 1 center, 2 fit */
+  int margin[3];            /* voxels added on both sides, z, y, x; >= 0 */
+  int allow_upscale;        /* fit: k may fall below 1 */
+  float foreground_above;   /* F = { v > foreground_above }; NaN is never foreground */
+} xvit_crop_config;
+int64_t xvit_volume_bbox_workspace_bytes(int nvol, int64_t nvox);
+int xvit_volume_bbox(const void* src, int src_dtype, int nvol, int M, int Ds, int Hs, int Ws, int D, int H, int W, const xvit_crop_config* cfg,
+                     int32_t* boxes /* [nvol, 8] */, int32_t* crop /* [nvol / M, 8] */, float* params /* [nvol, 32]; NULL: no fold */, void* workspace,
+                     int64_t workspace_bytes, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Contrast augmentations (csrc/contrast.hip): Gaussian blur, a smooth multiplicative bias field and gamma, as a second, independent

@@ -1,8 +1,10 @@
 """Time the augmenting input stage at the reference's input shape: B = 8, M = 2, 240 x 240 x 155 int16 -> 128^3 bf16.
 
-    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE] [--mode stage|elastic]
+    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE] [--mode stage|elastic|crop]
 
 --mode elastic times elastic deformation against the general path of the same run (see `elastic` below; profiles/elastic_measured.txt).
+--mode crop times the foreground bounding-box pair against the statistics pair of the same run, and the whole stage with and without
+crop_foreground (see `crop` below; profiles/crop_measured.txt).
 
 Arms, interleaved inside every repeat (so that drift hits them alike): xvit_resize_pad_crop_i16 (twice: two identical arms), the exact
 path as identity, the exact path with all three flips, the general path (every random transform on), the draw kernel, the statistics pair
@@ -107,17 +109,90 @@ def elastic(a) -> int:
     return 0
 
 
+def brain_volumes(dev):
+    """A synthetic skull-stripped "brain" per volume: an off-centre ellipsoid of about 172 x 140 x 136 voxels (of 240 x 240 x 155) of
+    positive int16 values over an exactly-zero background, a little different per sample."""
+    g = torch.Generator().manual_seed(0)
+    src = torch.randint(1, 3000, (B, M) + SRC, generator=g, dtype=torch.int16).to(dev)
+    z, y, x = (torch.arange(n, device=dev, dtype=torch.float32) for n in SRC)
+    for b in range(B):
+        c = (125.0 + b, 112.0 - 2 * b, 80.0 + b)
+        inside = ((z[:, None, None] - c[0]) / 86.0) ** 2 + ((y[None, :, None] - c[1]) / 70.0) ** 2 + ((x[None, None, :] - c[2]) / 68.0) ** 2 <= 1.0
+        src[b] *= inside.to(torch.int16)
+    return src
+
+
+def crop(a) -> int:
+    """--mode crop: the xvit_volume_bbox pair (boxes only, twice: two identical arms) against the xvit_volume_stats pair on the same brains,
+    and the whole stage (every random transform on) with crop_foreground None / "center" / "fit", each without and with
+    normalize="zscore".  Reported, not gated: nothing is asserted of a time."""
+    from xvit import ops
+    from xvit.augment import NSTAT, VolumeAugment, _crop_tables, crop_config, norm_config
+
+    dev = torch.device("cuda:0")
+    src = brain_volumes(dev)
+    nvox = SRC[0] * SRC[1] * SRC[2]
+    on = dict(flip_prob=(1, 1, 1), rotate_prob=1, zoom_prob=1, translate_prob=1, scale_intensity_prob=1, shift_intensity_prob=1, noise_prob=0)
+    stages = {(c, n): VolumeAugment(DST, crop_foreground=c, normalize=n, **(on if n else dict(on, intensity_scale=1e-3)))
+              for c in (None, "center", "fit") for n in (None, "zscore")}
+    box_cfg = crop_config(None, 0, False, 0.0)
+    boxes, crop_t, _ = _crop_tables(B, M, dev)
+    box_ws = ops.volume_bbox_workspace(B * M, nvox, dev)
+    stats_cfg = norm_config(None, 0.0, (0.005, 0.995))
+    stats = torch.empty(B, M, NSTAT, dtype=torch.float64, device=dev)
+    stats_ws = ops.volume_stats_workspace(B * M, dev)
+    ops.volume_bbox(src, box_cfg, DST, boxes, crop_t, box_ws)
+    lo, hi = crop_t[:, 0:6:2].cpu(), crop_t[:, 1:6:2].cpu()
+    extent = (hi - lo + 1).float().mean(0).tolist()
+    fraction = float(boxes[..., 6].sum()) / (B * M * nvox)
+
+    bbox = lambda: ops.volume_bbox(src, box_cfg, DST, boxes, crop_t, box_ws)      # noqa: E731
+    arms = [("bounding-box pair", bbox), ("statistics pair", lambda: ops.volume_stats(src, stats_cfg, stats, stats_ws))]
+    arms += [(f"stage, crop={c}, normalize={n}", lambda st=st: st(src)) for (c, n), st in stages.items()]
+    arms += [("bounding-box pair (again)", bbox)]
+    times = interleaved(arms, a.reps, a.inner)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    raw_bytes = src.numel() * 2
+    lines = [f"augment_bench --mode crop: B={B} M={M} {SRC} int16 -> {DST} bf16; ellipsoid brains, mean box {extent[0]:.0f} x {extent[1]:.0f} x {extent[2]:.0f} voxels, "
+             f"{100 * fraction:.1f} % of the voxels foreground; {a.reps} repeats x {a.inner} calls per arm, interleaved; device-event microseconds per call"]
+    for name, _ in arms:
+        t = times[name]
+        rate = f"  {raw_bytes / med[name] / 1e3:8.1f} GB/s" if "pair" in name else ""
+        lines.append(f"  {name:40s} median {med[name]:8.2f} us  (min {min(t):8.2f}, max {max(t):8.2f}){rate}")
+    same = ("bounding-box pair", "bounding-box pair (again)")
+    spread = max(max(times[n]) - min(times[n]) for n in same)
+    pair, stat = min(med[n] for n in same), med["statistics pair"]
+    lines.append(f"  bounding-box pair: reads {raw_bytes / 1e6:.1f} MB of raw volumes once (GB/s above counts these); at the 8.0 TB/s HBM peak that is "
+                 f"{raw_bytes / 8.0e12 * 1e6:.1f} us: {pair / (raw_bytes / 8.0e12 * 1e6):.2f} x that ({pair / (raw_bytes / 6.3e12 * 1e6):.2f} x the time at the 6.3 TB/s a copy "
+                 f"reaches); spread between the two identical arms' repeats {spread:.2f} us")
+    lines.append(f"  bounding-box pair against the statistics pair of this run: {pair / stat:.3f} x ({pair - stat:+.2f} us) -> "
+                 f"{'not slower' if pair <= stat else 'SLOWER than the statistics pair'}")
+    base = med["stage, crop=None, normalize=None"]
+    for c in ("center", "fit"):
+        lines.append(f"  stage with crop={c} - stage without: {med[f'stage, crop={c}, normalize=None'] - base:+.2f} us; with normalize=zscore on both: "
+                     f"{med[f'stage, crop={c}, normalize=zscore'] - med['stage, crop=None, normalize=zscore']:+.2f} us")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", choices=("stage", "elastic"), default="stage")
+    ap.add_argument("--mode", choices=("stage", "elastic", "crop"), default="stage")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("augment_bench: needs a GPU; a CPU run measures nothing")
     if a.mode == "elastic":
         return elastic(a)
+    if a.mode == "crop":
+        return crop(a)
     from xvit import ops
     from xvit.augment import NSTAT, AugmentParams, VolumeAugment, norm_config
 

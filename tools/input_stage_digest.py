@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""One sha256 per case of the raw bytes the device input stage writes: the three draws, xvit_augment_apply, xvit_augment_apply_elastic
-and xvit_contrast_apply, on small fixed inputs.  Two builds of the library compute the same thing exactly when their printouts are equal:
+"""One sha256 per case of the raw bytes the device input stage writes: the three draws, xvit_augment_apply, xvit_augment_apply_elastic,
+xvit_contrast_apply and xvit_volume_bbox (boxes, crop and the folded table; these cases come last, so that a build without them prints
+the same lines up to there), on small fixed inputs.  Two builds of the library compute the same thing exactly when their printouts are equal:
 
     XVIT_LIB=/path/to/other/libxvit_hip.so python tools/input_stage_digest.py > other.txt
     python tools/input_stage_digest.py > this.txt && cmp other.txt this.txt
@@ -132,6 +133,21 @@ def contrast_applies():
                 say(f"contrast_apply {short(sdt)} -> {short(ddt)} {shape}", ops.contrast_apply(src, table, ddt))
 
 
+def crops():
+    """xvit_volume_bbox on sparse volumes (about one voxel in six above 0, so the boxes do not fill the volume): boxes only, and both folds
+    into the records of augment_records, with and without a margin."""
+    for src_shape, dst_shape in (((9, 10, 37), (5, 6, 20)), ((9, 31, 31), (4, 5, 40))):      # the second: two chunks per volume
+        for sdt in (torch.int16, torch.bfloat16, torch.float32):
+            src = volumes((2, 2) + src_shape, sdt, -2500.0, 500.0)
+            src[:, :, :2], src[:, :, :, -3:], src[1, 1] = 0, 0, 0                            # empty faces; sample 1 has an empty modality
+            workspace = ops.volume_bbox_workspace(4, src[0, 0].numel(), DEV)
+            for mode, margin, up in ((None, 0, False), ("center", 0, False), ("center", (1, 0, 2), False), ("fit", 0, False), ("fit", (0, 2, 1), True)):
+                table = augment_records(src_shape, dst_shape)
+                boxes, crop = torch.empty(2, 2, A.BBOX_NREC, dtype=torch.int32, device=DEV), torch.empty(2, A.BBOX_NREC, dtype=torch.int32, device=DEV)
+                ops.volume_bbox(src, A.crop_config(mode, margin, up, 0.0), dst_shape, boxes, crop, workspace, table)
+                say(f"volume_bbox {short(sdt)} {src_shape} -> {dst_shape} {mode} margin {margin} upscale {up}", boxes, crop, table)
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         raise SystemExit("input_stage_digest: needs a GPU")
@@ -139,4 +155,5 @@ if __name__ == "__main__":
     draws()
     augment_applies()
     contrast_applies()
+    crops()
     torch.cuda.synchronize()
