@@ -5,43 +5,30 @@
 //   xvit_token_rows_gather/scatter the dropped rows of the decoder output (only they reach the prediction head), and the backward
 //   xvit_mae_loss_fwd / _bwd       mean squared error against the (per-patch normalised) voxels, read straight from the volume
 // No atomics: every sum below has one fixed order, stated in include/xvit.h.
-#include "xvit_common.h"
+#include "token_rows.h"
 
 namespace xvit {
 
 constexpr int kComplBlock = 1024;
 constexpr int kLossBlock = 256;
 
-// One workgroup per sequence, 1024 patches per round: a ballot prefix inside each wave, the waves' totals through LDS (the draw kernel's
-// scheme, on "dropped" instead of "kept").  Positions past Rm (a slot row with fewer than K kept entries) are not written and read as
-// kept in mslot; a row with more than K kept entries leaves the tail of drop_idx at -1.
+// One workgroup per sequence, 1024 patches per compaction round, on "dropped" where the draw compacts "kept".  Positions past Rm (a slot
+// row with fewer than K kept entries) are not written and read as kept in mslot; a row with more than K kept entries leaves the tail of
+// drop_idx at -1.
 __global__ __launch_bounds__(kComplBlock) void token_select_complement_kernel(const int* __restrict__ slot, int* __restrict__ drop_idx, int* __restrict__ mslot,
                                                                               int P, int Rm) {
   __shared__ int wave_tot[kComplBlock / kWave];
   const int s = blockIdx.x, tid = threadIdx.x;
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
   int base = 0;   // dropped patches in the rounds before this one (the same in every thread)
   for (int p0 = 0; p0 < P; p0 += kComplBlock) {     // uniform over the workgroup
     const int p = p0 + tid;
     const bool dropped = p < P && slot[(int64_t)s * P + p] < 0;
-    const uint64_t vote = __ballot(dropped);
-    const int in_wave = __popcll(vote & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(vote);
-    __syncthreads();
-    int before = 0, round = 0;
-    for (int w = 0; w < kComplBlock / kWave; ++w) {
-      const int t = wave_tot[w];
-      before += w < wave ? t : 0;
-      round += t;
-    }
+    const int pos = compact_round<kComplBlock>(dropped, wave_tot, base);
     if (p < P) {
-      const int pos = base + before + in_wave;
       const bool place = dropped && pos < Rm;
       mslot[(int64_t)s * P + p] = place ? pos : -1;
       if (place) drop_idx[(int64_t)s * Rm + pos] = p;
     }
-    base += round;
-    __syncthreads();                    // wave_tot is rewritten in the next round
   }
   for (int j = base + tid; j < Rm; j += kComplBlock) drop_idx[(int64_t)s * Rm + j] = -1;   // fewer dropped patches than Rm: no stale index
 }
@@ -52,8 +39,7 @@ __global__ void mae_unshuffle_fwd_kernel(const float* __restrict__ xe, const flo
                                          int64_t total) {
   const int dv = dd >> 2;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % dv) * 4;
-    const int64_t row = i / dv;
+    const auto [row, c] = row_col(i, dv);
     const int n = (int)(row % (P + 1));
     const int64_t s = row / (P + 1);
     const int m = (int)(s / B);
@@ -64,28 +50,41 @@ __global__ void mae_unshuffle_fwd_kernel(const float* __restrict__ xe, const flo
   }
 }
 
-// dxe[s, 0] = dy[s, 0];  dxe[s, 1 + j] = dy[s, 1 + keep_idx[s][j]]: every row written once (an index outside the grid gives a zero row)
-__global__ void mae_unshuffle_dxe_kernel(const float* __restrict__ dy, const int* __restrict__ keep_idx, float* __restrict__ dxe, int P, int K, int dd, int64_t total) {
-  const int dv = dd >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % dv) * 4;
-    const int64_t row = i / dv;
+// The maps of the three row movers (move_rows_kernel): output row -> input row, or -1 for a zero row.
+// dxe[s, 0] = dy[s, 0];  dxe[s, 1 + j] = dy[s, 1 + keep_idx[s][j]]  (an index outside the grid gives a zero row)
+struct UnshuffleDxeMap {
+  const int* __restrict__ keep_idx; int P, K;
+  __device__ __forceinline__ int64_t operator()(int64_t row) const {
     const int j = (int)(row % (K + 1));
     const int64_t s = row / (K + 1);
     const int n = j == 0 ? 0 : 1 + keep_idx[s * K + (j - 1)];
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((unsigned)n <= (unsigned)P) v = *(const f32x4*)(dy + (s * (P + 1) + n) * dd + c);
-    *(f32x4*)(dxe + row * dd + c) = v;
+    return (unsigned)n <= (unsigned)P ? s * (P + 1) + n : -1;
   }
-}
+};
+// g[s Rm + j] = x[s, 1 + drop_idx[s][j]]  (an index outside the grid gives a zero row)
+struct RowsGatherMap {
+  const int* __restrict__ drop_idx; int P, Rm;
+  __device__ __forceinline__ int64_t operator()(int64_t row) const {
+    const int t = drop_idx[row];
+    return (unsigned)t < (unsigned)P ? (row / Rm) * (P + 1) + 1 + t : -1;
+  }
+};
+// dx[s, 0] = 0;  dx[s, 1 + p] = mslot[s][p] >= 0 ? dg[s Rm + mslot[s][p]] : 0
+struct RowsScatterMap {
+  const int* __restrict__ mslot; int P, Rm;
+  __device__ __forceinline__ int64_t operator()(int64_t row) const {
+    const int n = (int)(row % (P + 1));
+    const int64_t s = row / (P + 1);
+    const int j = n == 0 ? -1 : mslot[s * P + (n - 1)];
+    return (unsigned)j < (unsigned)Rm ? s * Rm + j : -1;
+  }
+};
 
 // ddpos_m[m, n] = sum over b ascending of dy[(m, b), n]: one thread per (m, n, 4 features), its sequences in order
 __global__ void mae_unshuffle_dpos_kernel(const float* __restrict__ dy, float* __restrict__ ddpos_m, int B, int P, int dd, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over M (P + 1) dd / 4
   if (i >= total) return;
-  const int dv = dd >> 2;
-  const int c = (int)(i % dv) * 4;
-  const int64_t row = i / dv;
+  const auto [row, c] = row_col(i, dd >> 2);
   const int n = (int)(row % (P + 1));
   const int64_t m = row / (P + 1);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -97,9 +96,7 @@ __global__ void mae_unshuffle_dpos_kernel(const float* __restrict__ dy, float* _
 __global__ void mae_unshuffle_dmask_part_kernel(const float* __restrict__ dy, const int* __restrict__ slot, float* __restrict__ part, int P, int dd, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over S dd / 4
   if (i >= total) return;
-  const int dv = dd >> 2;
-  const int c = (int)(i % dv) * 4;
-  const int64_t s = i / dv;
+  const auto [s, c] = row_col(i, dd >> 2);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int p = 0; p < P; ++p)
     if (slot[s * P + p] < 0) acc += *(const f32x4*)(dy + (s * (P + 1) + 1 + p) * dd + c);
@@ -116,90 +113,18 @@ __global__ void mae_unshuffle_dmask_kernel(const float* __restrict__ part, float
   *(f32x4*)(dmask_token + c) = acc;
 }
 
-// g[s Rm + j] = x[s, 1 + drop_idx[s][j]]  (an index outside the grid gives a zero row)
-__global__ void token_rows_gather_kernel(const float* __restrict__ x, const int* __restrict__ drop_idx, float* __restrict__ g, int P, int Rm, int dd, int64_t total) {
-  const int dv = dd >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % dv) * 4;
-    const int64_t row = i / dv;        // s Rm + j
-    const int64_t s = row / Rm;
-    const int t = drop_idx[row];
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((unsigned)t < (unsigned)P) v = *(const f32x4*)(x + (s * (P + 1) + 1 + t) * dd + c);
-    *(f32x4*)(g + row * dd + c) = v;
-  }
-}
-
-// dx[s, 0] = 0;  dx[s, 1 + p] = mslot[s][p] >= 0 ? dg[s Rm + mslot[s][p]] : 0: every row written once
-__global__ void token_rows_scatter_kernel(const float* __restrict__ dg, const int* __restrict__ mslot, float* __restrict__ dx, int P, int Rm, int dd, int64_t total) {
-  const int dv = dd >> 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % dv) * 4;
-    const int64_t row = i / dv;
-    const int n = (int)(row % (P + 1));
-    const int64_t s = row / (P + 1);
-    const int j = n == 0 ? -1 : mslot[s * P + (n - 1)];
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((unsigned)j < (unsigned)Rm) v = *(const f32x4*)(dg + (s * Rm + j) * dd + c);
-    *(f32x4*)(dx + row * dd + c) = v;
-  }
-}
-
 // ---- the loss ------------------------------------------------------------------------------------------------------------------------
-
-struct LossGeom { int B, M, D, H, W, dp, hp, wp, Rm; };
-
-// VEC features of patch t of sequence s, from feature f on, as floats (token / feature order of patchify_kernel; a run of VEC features
-// stays inside one W-run of the volume: VEC divides wp)
-template <typename T, int VEC>
-__device__ __forceinline__ void load_voxels(const T* __restrict__ img, const LossGeom& g, int s, int t, int f, float (&v)[VEC]) {
-  const int Dn = g.D / g.dp, Wn = g.W / g.wp;
-  const int m = s / g.B, b = s - m * g.B;
-  const int d = t % Dn, hw = t / Dn, w = hw % Wn, h = hw / Wn;
-  const int p3 = f % g.wp, p12 = f / g.wp, p2 = p12 % g.hp, p1 = p12 / g.hp;
-  const T* src = img + ((((int64_t)b * g.M + m) * g.D + (d * g.dp + p1)) * g.H + (h * g.hp + p2)) * g.W + (w * g.wp + p3);
-  if constexpr (VEC == 8) {
-    if constexpr (sizeof(T) == 4) {
-      const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = a[i], v[4 + i] = c[i];
-    } else {
-      const bf16x8 a = *(const bf16x8*)src;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = bf2f(a[i]);
-    }
-  } else {
-    v[0] = (float)*src;
-  }
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_row(const T* __restrict__ src, float (&v)[VEC]) {
-  if constexpr (VEC == 8) {
-    if constexpr (sizeof(T) == 4) {
-      const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = a[i], v[4 + i] = c[i];
-    } else {
-      const bf16x8 a = *(const bf16x8*)src;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = bf2f(a[i]);
-    }
-  } else {
-    v[0] = (float)*src;
-  }
-}
 
 // One workgroup per predicted row.  The patch's voxels go to LDS once (the volume is read once); the mean, then the centred squares, then
 // the squared error against pred are each a block-wide sum in a fixed order (thread-strided partial sums, wave_reduce, the waves in order).
 template <typename TV, typename TP, int VEC>
 __global__ __launch_bounds__(kLossBlock) void mae_loss_fwd_kernel(const TP* __restrict__ pred, const int* __restrict__ drop_idx, const TV* __restrict__ img,
-                                                                  int norm_pix, float* __restrict__ stats, float* __restrict__ row_loss, const LossGeom g) {
+                                                                  int norm_pix, float* __restrict__ stats, float* __restrict__ row_loss, const TokenGeom g) {
   extern __shared__ float vox[];              // pd floats
   __shared__ float red[kLossBlock / kWave];
   const int pd = g.dp * g.hp * g.wp;
-  const int P = (g.D / g.dp) * (g.H / g.hp) * (g.W / g.wp);
-  const int r = blockIdx.x, s = r / g.Rm, tid = threadIdx.x;
+  const int P = patch_count(g);
+  const int r = blockIdx.x, s = r / g.n, tid = threadIdx.x;
   const int t = drop_idx[r];
   if ((unsigned)t >= (unsigned)P) {           // no such patch (uniform over the workgroup): the row scores nothing
     if (tid == 0) stats[2 * (int64_t)r] = 0.f, stats[2 * (int64_t)r + 1] = 1.f, row_loss[r] = 0.f;
@@ -208,7 +133,7 @@ __global__ __launch_bounds__(kLossBlock) void mae_loss_fwd_kernel(const TP* __re
   float part = 0.f;
   for (int f = tid * VEC; f < pd; f += kLossBlock * VEC) {
     float v[VEC];
-    load_voxels<TV, VEC>(img, g, s, t, f, v);
+    load_run<VEC>(img + voxel_index(g, s, t, f), v);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) vox[f + i] = v[i], part += v[i];
   }
@@ -230,7 +155,7 @@ __global__ __launch_bounds__(kLossBlock) void mae_loss_fwd_kernel(const TP* __re
   const TP* prow = pred + (int64_t)r * pd;
   for (int f = tid * VEC; f < pd; f += kLossBlock * VEC) {
     float p[VEC];
-    load_row<TP, VEC>(prow + f, p);
+    load_run<VEC>(prow + f, p);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       const float e = p[i] - (vox[f + i] - mean) * rstd;
@@ -262,24 +187,12 @@ __global__ __launch_bounds__(kLossBlock) void mae_loss_finish_kernel(const float
   }
 }
 
-template <typename T, int VEC>
-__device__ __forceinline__ void store_row(T* __restrict__ dst, const float (&v)[VEC]) {
-  if constexpr (VEC == 8) {
-    const f32x4 a = {v[0], v[1], v[2], v[3]}, c = {v[4], v[5], v[6], v[7]};
-    if constexpr (sizeof(T) == 4) ((f32x4*)dst)[0] = a, ((f32x4*)dst)[1] = c;
-    else *(bf16x8*)dst = to_bf16x8(a, c);
-  } else {
-    if constexpr (sizeof(T) == 4) *dst = v[0];
-    else *dst = f2bf(v[0]);
-  }
-}
-
 // dpred[r, f] = coef (pred[r, f] - target[r, f]),  coef = g 2 / (pd rows), the target recomputed from the volume and stats
 template <typename TV, typename TP, int VEC>
 __global__ void mae_loss_bwd_kernel(const TP* __restrict__ pred, const int* __restrict__ drop_idx, const TV* __restrict__ img, const float* __restrict__ stats,
-                                    const float* __restrict__ gup, TP* __restrict__ dpred, const LossGeom g, int64_t rows, int64_t total_vec) {
+                                    const float* __restrict__ gup, TP* __restrict__ dpred, const TokenGeom g, int64_t rows, int64_t total_vec) {
   const int pd = g.dp * g.hp * g.wp, pv = pd / VEC;
-  const int P = (g.D / g.dp) * (g.H / g.hp) * (g.W / g.wp);
+  const int P = patch_count(g);
   const float coef = gup[0] * (2.0f / ((float)pd * (float)rows));
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x) {
     const int f = (int)(idx % pv) * VEC;
@@ -292,19 +205,13 @@ __global__ void mae_loss_bwd_kernel(const TP* __restrict__ pred, const int* __re
     } else {
       const float mean = stats[2 * r], rstd = stats[2 * r + 1];
       float v[VEC], p[VEC];
-      load_voxels<TV, VEC>(img, g, (int)(r / g.Rm), t, f, v);
-      load_row<TP, VEC>(pred + r * pd + f, p);
+      load_run<VEC>(img + voxel_index(g, (int)(r / g.n), t, f), v);
+      load_run<VEC>(pred + r * pd + f, p);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) o[i] = coef * (p[i] - (v[i] - mean) * rstd);
     }
-    store_row<TP, VEC>(dpred + r * pd + f, o);
+    store_run<VEC>(dpred + r * pd + f, o);
   }
-}
-
-static bool aligned16(std::initializer_list<const void*> ptrs) {
-  uintptr_t all = 0;
-  for (const void* p : ptrs) all |= reinterpret_cast<uintptr_t>(p);
-  return (all & 15) == 0;
 }
 
 }  // namespace xvit
@@ -343,7 +250,7 @@ extern "C" int xvit_mae_unshuffle_bwd(const float* dy, const int32_t* keep_idx, 
   const int dv = dd / 4, M = S / B;
   const hipStream_t st = (hipStream_t)stream;
   const int64_t t_xe = (int64_t)S * (K + 1) * dv, t_pos = (int64_t)M * (P + 1) * dv, t_part = (int64_t)S * dv;
-  hipLaunchKernelGGL(mae_unshuffle_dxe_kernel, dim3(grid_for(t_xe, 256)), dim3(256), 0, st, dy, keep_idx, dxe, P, K, dd, t_xe);
+  hipLaunchKernelGGL(move_rows_kernel<UnshuffleDxeMap>, dim3(grid_for(t_xe, 256)), dim3(256), 0, st, dy, dxe, UnshuffleDxeMap{keep_idx, P, K}, dd, t_xe);
   hipLaunchKernelGGL(mae_unshuffle_dpos_kernel, dim3((unsigned)((t_pos + 255) / 256)), dim3(256), 0, st, dy, ddpos_m, B, P, dd, t_pos);
   hipLaunchKernelGGL(mae_unshuffle_dmask_part_kernel, dim3((unsigned)((t_part + 63) / 64)), dim3(64), 0, st, dy, slot, dmask_part, P, dd, t_part);
   hipLaunchKernelGGL(mae_unshuffle_dmask_kernel, dim3((unsigned)((dv + 63) / 64)), dim3(64), 0, st, (const float*)dmask_part, dmask_token, S, dd);
@@ -360,7 +267,7 @@ extern "C" int xvit_token_rows_gather(const float* x, const int32_t* drop_idx, f
   XVIT_MAE_ROWS_ARGS("xvit_token_rows_gather");
   XVIT_REQUIRE(aligned16({x, g}), "xvit_token_rows_gather: x and g must be 16-byte aligned");
   const int64_t total = (int64_t)S * Rm * (dd / 4);
-  hipLaunchKernelGGL(token_rows_gather_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, drop_idx, g, P, Rm, dd, total);
+  hipLaunchKernelGGL(move_rows_kernel<RowsGatherMap>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, g, RowsGatherMap{drop_idx, P, Rm}, dd, total);
   return check_launch("xvit_token_rows_gather");
 }
 
@@ -369,15 +276,13 @@ extern "C" int xvit_token_rows_scatter(const float* dg, const int32_t* mslot, fl
   XVIT_MAE_ROWS_ARGS("xvit_token_rows_scatter");
   XVIT_REQUIRE(aligned16({dg, dx}), "xvit_token_rows_scatter: dg and dx must be 16-byte aligned");
   const int64_t total = (int64_t)S * (P + 1) * (dd / 4);
-  hipLaunchKernelGGL(token_rows_scatter_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dg, mslot, dx, P, Rm, dd, total);
+  hipLaunchKernelGGL(move_rows_kernel<RowsScatterMap>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dg, dx, RowsScatterMap{mslot, P, Rm}, dd, total);
   return check_launch("xvit_token_rows_scatter");
 }
 
 // Shared argument checks of the two loss entry points -> 0, or an error already set.
 static int mae_loss_args(const char* name, const void* pred, int pred_dtype, const void* img, int img_dtype, const void* dpred, int B, int M, int D, int H, int W, int dp, int hp, int wp, int Rm, int norm_pix) {
-  XVIT_REQUIRE(B > 0 && M > 0 && D > 0 && H > 0 && W > 0 && dp > 0 && hp > 0 && wp > 0, "%s: bad sizes", name);
-  XVIT_REQUIRE(D % dp == 0 && H % hp == 0 && W % wp == 0, "%s: image dimensions must be divisible by the patch size", name);
-  XVIT_REQUIRE((pred_dtype == XVIT_F32 || pred_dtype == XVIT_BF16) && (img_dtype == XVIT_F32 || img_dtype == XVIT_BF16), "%s: bad dtype (bf16 or fp32)", name);
+  XVIT_REQUIRE_PATCH_GRID(name, dtype_ok(pred_dtype) && dtype_ok(img_dtype));
   const uintptr_t pa = pred_dtype == XVIT_F32 ? 3 : 1, ia = img_dtype == XVIT_F32 ? 3 : 1;
   XVIT_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(dpred)) & pa) == 0 && (reinterpret_cast<uintptr_t>(img) & ia) == 0,
                "%s: the volume and the prediction must be aligned to their element size", name);
@@ -387,16 +292,6 @@ static int mae_loss_args(const char* name, const void* pred, int pred_dtype, con
   XVIT_REQUIRE(!norm_pix || pd >= 2, "%s: norm_pix needs at least 2 voxels per patch (unbiased variance)", name);
   XVIT_REQUIRE(P < (1ll << 31) && (int64_t)M * B * Rm < (1ll << 31), "%s: geometry too large", name);
   return 0;
-}
-
-template <class F>
-static void by_loss_types(int img_dtype, int pred_dtype, bool vec, F&& f) {
-  by_dtype(img_dtype, [&](auto tv) {
-    by_dtype(pred_dtype, [&](auto tp) {
-      if (vec) f(tv, tp, Int<8>{});
-      else f(tv, tp, Int<1>{});
-    });
-  });
 }
 
 extern "C" int xvit_mae_loss_fwd(const void* pred, int pred_dtype, const int32_t* drop_idx, const void* img, int img_dtype, int norm_pix, float* stats,
@@ -409,13 +304,13 @@ extern "C" int xvit_mae_loss_fwd(const void* pred, int pred_dtype, const int32_t
   const int pd = dp * hp * wp, S = M * B;
   // 8-voxel runs are 16-byte accesses (two of them for fp32): 16-byte aligned volume and prediction, else one voxel per access
   const bool vec = (wp % 8 == 0) && aligned16({img, pred});
-  const LossGeom g = {B, M, D, H, W, dp, hp, wp, Rm};
-  by_loss_types(img_dtype, pred_dtype, vec, [&](auto tv, auto tp, auto v) {
+  const TokenGeom g = {B, M, D, H, W, dp, hp, wp, Rm};
+  by_dtype(img_dtype, [&](auto tv) { by_dtype_vec(pred_dtype, vec, [&](auto tp, auto v) {
     using TV = decltype(tv);
     using TP = decltype(tp);
     hipLaunchKernelGGL((mae_loss_fwd_kernel<TV, TP, decltype(v)::value>), dim3(S * Rm), dim3(kLossBlock), (size_t)pd * sizeof(float), (hipStream_t)stream,
                        (const TP*)pred, drop_idx, (const TV*)img, norm_pix ? 1 : 0, stats, row_loss, g);
-  });
+  }); });
   hipLaunchKernelGGL(mae_loss_finish_kernel, dim3(1), dim3(kLossBlock), 0, (hipStream_t)stream, (const float*)row_loss, loss_seq, loss, S, Rm);
   return check_launch("xvit_mae_loss_fwd");
 }
@@ -427,13 +322,13 @@ extern "C" int xvit_mae_loss_bwd(const void* pred, int pred_dtype, const int32_t
   const int pd = dp * hp * wp;
   const int64_t rows = (int64_t)M * B * Rm, total = rows * pd;
   const bool vec = (wp % 8 == 0) && aligned16({img, pred, dpred});
-  const LossGeom g = {B, M, D, H, W, dp, hp, wp, Rm};
-  by_loss_types(img_dtype, pred_dtype, vec, [&](auto tv, auto tp, auto v) {
+  const TokenGeom g = {B, M, D, H, W, dp, hp, wp, Rm};
+  by_dtype(img_dtype, [&](auto tv) { by_dtype_vec(pred_dtype, vec, [&](auto tp, auto v) {
     using TV = decltype(tv);
     using TP = decltype(tp);
     constexpr int VEC = decltype(v)::value;
     hipLaunchKernelGGL((mae_loss_bwd_kernel<TV, TP, VEC>), dim3(grid_for(total / VEC, 256)), dim3(256), 0, (hipStream_t)stream, (const TP*)pred, drop_idx,
                        (const TV*)img, stats, g_up, (TP*)dpred, g, rows, total / VEC);
-  });
+  }); });
   return check_launch("xvit_mae_loss_bwd");
 }

@@ -1,6 +1,6 @@
 // HBM-bound helpers around the GEMMs: 3-D patchify, CLS/pos rows, column sums (bias grads),
-// casts, dropout, the num_classes head and the mean + cross-entropy tail.
-#include "xvit_common.h"
+// casts, dropout and the num_classes head (the mean + cross-entropy tail: mix.hip).
+#include "token_rows.h"
 
 namespace xvit {
 
@@ -9,68 +9,18 @@ namespace xvit {
 // one 16/32-byte run each), so reads are fully coalesced; a wave then covers 4 H-rows of 8
 // patches and its writes land as whole 128-byte lines of 8 different token rows.
 // ------------------------------------------------------------------------------------------
-// Where the VEC voxels at linear volume index idx * VEC live in the patch matrix: element offset (patch row) * patch_dim + (offset
-// inside the patch) of the first; the run stays inside one patch row (VEC divides wp).
-struct PatchGeom { int M, D, H, W, dp, hp, wp; int64_t stride_b, stride_m; int row_off; };
-template <int VEC>
-__device__ __forceinline__ int64_t patch_elem(const PatchGeom& g, int64_t idx) {
-  const int Wv = g.W / VEC;
-  const int Dn = g.D / g.dp, Wn = g.W / g.wp;
-  const int wv = (int)(idx % Wv);
-  int64_t r = idx / Wv;
-  const int hh = (int)(r % g.H); r /= g.H;
-  const int dd = (int)(r % g.D); r /= g.D;
-  const int vol = (int)r;  // b*M + m
-  const int b = vol / g.M, m = vol - b * g.M;
-  const int w0 = wv * VEC;
-  const int w = w0 / g.wp, p3 = w0 - w * g.wp;
-  const int h = hh / g.hp, p2 = hh - h * g.hp;
-  const int d = dd / g.dp, p1 = dd - d * g.dp;
-  const int t = (h * Wn + w) * Dn + d;
-  const int f = (p1 * g.hp + p2) * g.wp + p3;
-  return ((int64_t)b * g.stride_b + (int64_t)m * g.stride_m + t + g.row_off) * (g.dp * g.hp * g.wp) + f;
-}
-
 template <typename T, int VEC>
 __global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ out, const PatchGeom g, int64_t total_vec) {
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x) {
-    bf16* dst = out + patch_elem<VEC>(g, idx);
-    const T* src = img + idx * VEC;
-    if constexpr (VEC == 8) {
-      bf16x8 o;
-      if constexpr (sizeof(T) == 4) {
-        const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
-        o = to_bf16x8(a, c);
-      } else {
-        o = *(const bf16x8*)src;
-      }
-      *(bf16x8*)dst = o;
-    } else {
-      *dst = f2bf((float)*src);
-    }
-  }
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x)
+    copy_run<VEC>(out + patch_elem<VEC>(g, idx), img + idx * VEC);
 }
 
 // unpatchify: the exact inverse of patchify_kernel (fp32 patch rows -> fp32 / bf16 volume).  Threads walk the OUTPUT in memory
 // order, 8 voxels = one 32 / 16-byte run each, so the volume is written fully coalesced; each reads its 32 bytes from one patch row.
 template <typename T, int VEC>
 __global__ void unpatchify_kernel(const float* __restrict__ in, T* __restrict__ img, const PatchGeom g, int64_t total_vec) {
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x) {
-    const float* src = in + patch_elem<VEC>(g, idx);
-    T* dst = img + idx * VEC;
-    if constexpr (VEC == 8) {
-      const f32x4 a = ((const f32x4*)src)[0], c = ((const f32x4*)src)[1];
-      if constexpr (sizeof(T) == 4) {
-        ((f32x4*)dst)[0] = a;
-        ((f32x4*)dst)[1] = c;
-      } else {
-        *(bf16x8*)dst = to_bf16x8(a, c);
-      }
-    } else {
-      if constexpr (sizeof(T) == 4) *dst = *src;
-      else *dst = f2bf(*src);
-    }
-  }
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_vec; idx += (int64_t)gridDim.x * blockDim.x)
+    copy_run<VEC>(img + idx * VEC, in + patch_elem<VEC>(g, idx));
 }
 
 // zero row 0 of every [rows_per, pd] sample (the CLS slot of the padded patch matrix)
@@ -258,64 +208,14 @@ __global__ void small_linear_bwd_kernel(const float* __restrict__ dy, const bf16
   }
 }
 
-// logits = mean_m logits_m; loss = mean_b CE(logits_b, label_b) with label smoothing;
-// dlogits_m = (softmax - target) / (B * M).   One block; B*C small.
-__global__ void mean_ce_kernel(const float* __restrict__ logits_m, const int64_t* __restrict__ labels, float eps, float* __restrict__ logits,
-                               float* __restrict__ loss, float* __restrict__ dlogits_m, int M, int B, int C) {
-  __shared__ float red[4];
-  float part = 0.f;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    float mx = -INFINITY;
-    for (int c = 0; c < C; ++c) {
-      float s = 0.f;
-      for (int m = 0; m < M; ++m) s += logits_m[((int64_t)m * B + b) * C + c];
-      s /= (float)M;
-      logits[b * C + c] = s;
-      mx = fmaxf(mx, s);
-    }
-    float z = 0.f;
-    for (int c = 0; c < C; ++c) z += expf(logits[b * C + c] - mx);
-    const float lz = mx + logf(z);
-    const int y = (int)labels[b];
-    float l = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float logp = logits[b * C + c] - lz;
-      const float tgt = (c == y ? 1.0f - eps : 0.f) + eps / (float)C;
-      l -= tgt * logp;
-      const float g = (expf(logp) - tgt) / (float)(B * M);
-      for (int m = 0; m < M; ++m) dlogits_m[((int64_t)m * B + b) * C + c] = g;
-    }
-    part += l;
-  }
-  part = wave_sum(part);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-    *loss = t / (float)B;
-  }
-}
-
 }  // namespace xvit
 
 using namespace xvit;
 
-// f(T{}, Int<VEC>{}, units of work): the (image dtype, voxels per thread) instantiation of a patchify / unpatchify launch
-template <class F>
-static void patch_dispatch(int img_dtype, bool vec, int64_t total, F&& f) {
-  by_dtype(img_dtype, [&](auto t) {
-    if (vec) f(t, Int<8>{}, total / 8);
-    else f(t, Int<1>{}, total);
-  });
-}
-
 extern "C" int xvit_patchify(const void* img, int img_dtype, void* out, int B, int M, int D, int H, int W, int dp, int hp, int wp,
                              int64_t stride_b, int64_t stride_m, int row_off, int zero_rows, int64_t zero_row_stride, xvit_stream_t stream) {
   XVIT_REQUIRE(img && out, "xvit_patchify: null pointer");
-  XVIT_REQUIRE(B > 0 && M > 0 && D > 0 && H > 0 && W > 0 && dp > 0 && hp > 0 && wp > 0, "xvit_patchify: bad sizes");
-  XVIT_REQUIRE(D % dp == 0 && H % hp == 0 && W % wp == 0, "xvit_patchify: image dimensions must be divisible by the patch size");
-  XVIT_REQUIRE(img_dtype == XVIT_F32 || img_dtype == XVIT_BF16, "xvit_patchify: bad dtype");
+  XVIT_REQUIRE_PATCH_GRID("xvit_patchify", dtype_ok(img_dtype));
   XVIT_REQUIRE(stride_b > 0 && stride_m > 0 && row_off >= 0 && zero_rows >= 0, "xvit_patchify: bad output placement");
   XVIT_REQUIRE(zero_rows == 0 || (dp * hp * wp) % 8 == 0, "xvit_patchify: zero rows need patch_dim %% 8 == 0");
   const int64_t total = (int64_t)B * M * D * H * W;
@@ -323,8 +223,9 @@ extern "C" int xvit_patchify(const void* img, int img_dtype, void* out, int B, i
   const bool vec = (wp % 8 == 0) && ((reinterpret_cast<uintptr_t>(img) & 31) == 0);
   bf16* o = (bf16*)out;
   const PatchGeom g = {M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off};
-  patch_dispatch(img_dtype, vec, total, [&](auto t, auto v, int64_t work) {
+  by_dtype_vec(img_dtype, vec, [&](auto t, auto v) {
     using T = decltype(t);
+    const int64_t work = total / decltype(v)::value;
     hipLaunchKernelGGL((patchify_kernel<T, decltype(v)::value>), dim3(grid_for(work, 256)), dim3(256), 0, s, (const T*)img, o, g, work);
   });
   if (zero_rows > 0) {
@@ -338,16 +239,15 @@ extern "C" int xvit_patchify(const void* img, int img_dtype, void* out, int B, i
 extern "C" int xvit_unpatchify(const float* patches, void* img, int img_dtype, int B, int M, int D, int H, int W, int dp, int hp, int wp, int64_t stride_b,
                                int64_t stride_m, int row_off, xvit_stream_t stream) {
   XVIT_REQUIRE(patches && img, "xvit_unpatchify: null pointer");
-  XVIT_REQUIRE(B > 0 && M > 0 && D > 0 && H > 0 && W > 0 && dp > 0 && hp > 0 && wp > 0, "xvit_unpatchify: bad sizes");
-  XVIT_REQUIRE(D % dp == 0 && H % hp == 0 && W % wp == 0, "xvit_unpatchify: image dimensions must be divisible by the patch size");
-  XVIT_REQUIRE(img_dtype == XVIT_F32 || img_dtype == XVIT_BF16, "xvit_unpatchify: bad dtype");
+  XVIT_REQUIRE_PATCH_GRID("xvit_unpatchify", dtype_ok(img_dtype));
   XVIT_REQUIRE(stride_b > 0 && stride_m > 0 && row_off >= 0, "xvit_unpatchify: bad input placement");
   const int64_t total = (int64_t)B * M * D * H * W;
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (wp % 8 == 0) && ((reinterpret_cast<uintptr_t>(patches) & 31) == 0) && ((reinterpret_cast<uintptr_t>(img) & 31) == 0);
   const PatchGeom g = {M, D, H, W, dp, hp, wp, stride_b, stride_m, row_off};
-  patch_dispatch(img_dtype, vec, total, [&](auto t, auto v, int64_t work) {
+  by_dtype_vec(img_dtype, vec, [&](auto t, auto v) {
     using T = decltype(t);
+    const int64_t work = total / decltype(v)::value;
     hipLaunchKernelGGL((unpatchify_kernel<T, decltype(v)::value>), dim3(grid_for(work, 256)), dim3(256), 0, s, patches, (T*)img, g, work);
   });
   return check_launch("xvit_unpatchify");
@@ -368,15 +268,14 @@ extern "C" int xvit_embed_bwd(const float* dx, float* dpos, float* dcls, int MB,
 
 extern "C" int xvit_cast_f32_bf16(const float* src, void* dst, int64_t n, xvit_stream_t stream) {
   XVIT_REQUIRE(src && dst && n > 0, "xvit_cast_f32_bf16: bad arguments");
-  XVIT_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0, "xvit_cast_f32_bf16: pointers must be 16-byte aligned");
+  XVIT_REQUIRE(aligned16({src, dst}), "xvit_cast_f32_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(cast_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, n);
   return check_launch("xvit_cast_f32_bf16");
 }
 
 extern "C" int xvit_add_cast_f32_bf16(const float* a, const float* b, float* out, void* out_bf16, int64_t n, xvit_stream_t stream) {
   XVIT_REQUIRE(a && b && out && out_bf16 && n > 0 && n % 8 == 0, "xvit_add_cast_f32_bf16: bad arguments (n must be a positive multiple of 8)");
-  XVIT_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(out_bf16)) & 15) == 0,
-               "xvit_add_cast_f32_bf16: pointers must be 16-byte aligned");
+  XVIT_REQUIRE(aligned16({a, b, out, out_bf16}), "xvit_add_cast_f32_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(add_cast_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, (bf16*)out_bf16, n);
   return check_launch("xvit_add_cast_f32_bf16");
 }
@@ -446,13 +345,6 @@ extern "C" int xvit_small_linear_bwd(const float* dy, const void* x, int64_t ldx
   hipLaunchKernelGGL(small_linear_bwd_kernel, dim3((K + 255) / 256, (M + rows - 1) / rows), dim3(256), 0, (hipStream_t)stream, dy, (const bf16*)x, ldx, W,
                      (const bf16*)z, ldz, (bf16*)dx, lddx, dW, db, M, N, K, rows);
   return check_launch("xvit_small_linear_bwd");
-}
-
-extern "C" int xvit_mean_ce(const float* logits_m, const int64_t* labels, float label_smoothing, float* logits, float* loss, float* dlogits_m, int M,
-                            int B, int C, xvit_stream_t stream) {
-  XVIT_REQUIRE(logits_m && labels && logits && loss && dlogits_m && M > 0 && B > 0 && C > 0, "xvit_mean_ce: bad arguments");
-  hipLaunchKernelGGL(mean_ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits_m, labels, label_smoothing, logits, loss, dlogits_m, M, B, C);
-  return check_launch("xvit_mean_ce");
 }
 
 // ------------------------------------------------------------------------------------------

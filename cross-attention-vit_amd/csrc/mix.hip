@@ -1,7 +1,8 @@
 // Mixup (Zhang et al. 2018) and CutMix (Yun et al. 2019) on the volumes, with the soft-target loss (include/xvit.h, "Mixup / CutMix"):
 //   xvit_mix_draw      one readable record per sample from (config, seed, dropout epoch): capturable, no host read-back
 //   xvit_mix_apply     dst = the volumes of src mixed through the records: a pure function of (src, table)
-//   xvit_mean_ce_mix   xvit_mean_ce with the target lam smooth(y_b) + oml smooth(y_partner[b]), read from the same table
+//   xvit_mean_ce       the mean over the modalities and the cross-entropy tail, forward and backward in one launch
+//   xvit_mean_ce_mix   the same with the target lam smooth(y_b) + oml smooth(y_partner[b]), read from the same table
 // The random numbers live in the table only.
 #include <math.h>
 
@@ -187,11 +188,13 @@ __global__ void __launch_bounds__(256) mix_apply_kernel(const T* __restrict__ sr
 }
 
 // ------------------------------------------------------------------------------------------
-// loss: mean_ce_kernel (misc.hip) with the two-label target; the same operations in the same order, so that a table of lam = 1
-// reproduces its bits.
+// loss.  logits = mean_m logits_m; loss = mean_b CE(logits_b, target_b); dlogits_m = (softmax - target) / (B * M).  One block; B*C small.
+// target_b is the smoothed label of sample b and, with MIX, lam times it plus oml times the smoothed label of the partner the record names
+// (a copy record: the label alone).  Without MIX neither the table nor a second label is read.
 // ------------------------------------------------------------------------------------------
-__global__ void mean_ce_mix_kernel(const float* __restrict__ logits_m, const int64_t* __restrict__ labels, const float* __restrict__ table, float eps,
-                                   float* __restrict__ logits, float* __restrict__ loss, float* __restrict__ dlogits_m, int M, int B, int C) {
+template <bool MIX>
+__global__ void mean_ce_kernel(const float* __restrict__ logits_m, const int64_t* __restrict__ labels, const float* __restrict__ table, float eps,
+                               float* __restrict__ logits, float* __restrict__ loss, float* __restrict__ dlogits_m, int M, int B, int C) {
   __shared__ float red[4];
   float part = 0.f;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
@@ -207,13 +210,17 @@ __global__ void mean_ce_mix_kernel(const float* __restrict__ logits_m, const int
     for (int c = 0; c < C; ++c) z += expf(logits[b * C + c] - mx);
     const float lz = mx + logf(z);
     const int y = (int)labels[b];
-    const MixRecord r = mix_record(table + (int64_t)b * XVIT_MIX_NPARAM, B);
-    const int yp = r.mode != 0 ? (int)labels[r.partner] : y;
+    MixRecord r = {0, 0, 1.f, 0.f};
+    int yp = y;
+    if constexpr (MIX) {
+      r = mix_record(table + (int64_t)b * XVIT_MIX_NPARAM, B);
+      if (r.mode != 0) yp = (int)labels[r.partner];
+    }
     float l = 0.f;
     for (int c = 0; c < C; ++c) {
       const float logp = logits[b * C + c] - lz;
       float tgt = (c == y ? 1.0f - eps : 0.f) + eps / (float)C;
-      if (r.mode != 0) tgt = fmaf(r.lam, tgt, r.oml * ((c == yp ? 1.0f - eps : 0.f) + eps / (float)C));
+      if (MIX && r.mode != 0) tgt = fmaf(r.lam, tgt, r.oml * ((c == yp ? 1.0f - eps : 0.f) + eps / (float)C));
       l -= tgt * logp;
       const float g = (expf(logp) - tgt) / (float)(B * M);
       for (int m = 0; m < M; ++m) dlogits_m[((int64_t)m * B + b) * C + c] = g;
@@ -238,7 +245,7 @@ extern "C" int xvit_mix_draw(const xvit_mix_config* config, float* table, int B,
   XVIT_REQUIRE(config && table, "xvit_mix_draw: null config or record table");
   XVIT_REQUIRE(B > 0 && B < (1 << 24), "xvit_mix_draw: B=%d must be positive and below 2^24 (the partner index is stored as a float)", B);
   XVIT_REQUIRE(D > 0 && H > 0 && W > 0 && (int64_t)D * H * W < (1ll << 31), "xvit_mix_draw: bad volume %d x %d x %d (positive, fewer than 2^31 voxels)", D, H, W);
-  XVIT_REQUIRE(((uintptr_t)table & 15) == 0, "xvit_mix_draw: the record table must be 16-byte aligned");
+  XVIT_REQUIRE(aligned16({table}), "xvit_mix_draw: the record table must be 16-byte aligned");
   const xvit_mix_config& c = *config;
   XVIT_REQUIRE(c.mixup_alpha >= 0.f && c.cutmix_alpha >= 0.f && isfinite(c.mixup_alpha) && isfinite(c.cutmix_alpha),
                "xvit_mix_draw: mixup_alpha=%g and cutmix_alpha=%g must be finite and >= 0", c.mixup_alpha, c.cutmix_alpha);
@@ -263,7 +270,7 @@ extern "C" int xvit_mix_apply(const void* src, void* dst, int dtype, const float
   const uintptr_t t0 = (uintptr_t)dst, t1 = t0 + (uintptr_t)((int64_t)B * M * nvox * size);
   XVIT_REQUIRE(s1 <= t0 || t1 <= s0, "xvit_mix_apply: dst aliases src (the mix is out of place: dst != src, no overlap)");
   const int vec = (int)(16 / size);
-  const bool wide = W % vec == 0 && stride_b % vec == 0 && stride_m % vec == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  const bool wide = W % vec == 0 && stride_b % vec == 0 && stride_m % vec == 0 && aligned16({src, dst});
   const int64_t nvec = wide ? nvox / vec : nvox;
   const int64_t per_vol = (nvec + kMixItems * 256 - 1) / (kMixItems * 256);
   XVIT_REQUIRE(per_vol * B * M < (1ll << 31), "xvit_mix_apply: too many workgroups for one launch");
@@ -279,10 +286,17 @@ extern "C" int xvit_mix_apply(const void* src, void* dst, int dtype, const float
   return check_launch("xvit_mix_apply");
 }
 
+extern "C" int xvit_mean_ce(const float* logits_m, const int64_t* labels, float label_smoothing, float* logits, float* loss, float* dlogits_m, int M,
+                            int B, int C, xvit_stream_t stream) {
+  XVIT_REQUIRE(logits_m && labels && logits && loss && dlogits_m && M > 0 && B > 0 && C > 0, "xvit_mean_ce: bad arguments");
+  hipLaunchKernelGGL(mean_ce_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits_m, labels, (const float*)nullptr, label_smoothing, logits, loss, dlogits_m, M, B, C);
+  return check_launch("xvit_mean_ce");
+}
+
 extern "C" int xvit_mean_ce_mix(const float* logits_m, const int64_t* labels, const float* table, float label_smoothing, float* logits, float* loss,
                                 float* dlogits_m, int M, int B, int C, xvit_stream_t stream) {
   XVIT_REQUIRE(table, "xvit_mean_ce_mix: null record table (xvit_mean_ce is the loss without mixing)");
   XVIT_REQUIRE(logits_m && labels && logits && loss && dlogits_m && M > 0 && B > 0 && C > 0, "xvit_mean_ce_mix: bad arguments");
-  hipLaunchKernelGGL(mean_ce_mix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits_m, labels, table, label_smoothing, logits, loss, dlogits_m, M, B, C);
+  hipLaunchKernelGGL(mean_ce_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits_m, labels, table, label_smoothing, logits, loss, dlogits_m, M, B, C);
   return check_launch("xvit_mean_ce_mix");
 }

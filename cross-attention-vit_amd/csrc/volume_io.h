@@ -1,5 +1,5 @@
-// Typed element access of the input-stage kernels (augment_apply.h, contrast.hip): volumes are int16, bf16 or fp32 on the way in, bf16 or
-// fp32 on the way out, and every value passes through fp32 in between.
+// Typed element access of the input-stage kernels (augment_apply.h, contrast.hip) and the token-path kernels (token_rows.h): volumes are
+// int16, bf16 or fp32 on the way in, bf16 or fp32 on the way out, and every value passes through fp32 in between (copy_run8 excepted).
 #pragma once
 #include "xvit_common.h"
 
@@ -40,5 +40,20 @@ __device__ __forceinline__ void store_run8(float* p, const float (&v)[8]) {
 }
 __device__ __forceinline__ void store_run4(bf16* p, const f32x4& v) { *(bf16x4*)p = to_bf16x4(v); }
 __device__ __forceinline__ void store_run4(float* p, const f32x4& v) { *(f32x4*)p = v; }
+
+// 8 consecutive elements from one 16-byte aligned address to another.  The same type on both sides moves the bits (16 or 2 x 16 bytes,
+// no conversion: a signalling NaN keeps its payload); any other pair goes through fp32.
+template <typename D, typename S>
+__device__ __forceinline__ void copy_run8(D* dst, const S* src) {
+  float v[8];
+  load_run8_aligned(src, v);
+  store_run8(dst, v);
+}
+__device__ __forceinline__ void copy_run8(bf16* dst, const bf16* src) { *(bf16x8*)dst = *(const bf16x8*)src; }
+__device__ __forceinline__ void copy_run8(float* dst, const float* src) {
+  const f32x4 a = *(const f32x4*)src, b = *(const f32x4*)(src + 4);
+  *(f32x4*)dst = a;
+  *(f32x4*)(dst + 4) = b;
+}
 
 }  // namespace xvit

@@ -5,6 +5,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 
@@ -79,6 +80,19 @@ static void by_src_dtype(int dtype, F&& f) {   // by_dtype and XVIT_I16: the ent
   if (dtype == XVIT_I16) f(int16_t{});
   else by_dtype(dtype, f);
 }
+template <class F>
+static void by_dtype_vec(int dtype, bool vec, F&& f) {   // by_dtype and Int<8> | Int<1>: elements per access, 8 where the caller found 16-byte runs
+  by_dtype(dtype, [&](auto t) {
+    if (vec) f(t, Int<8>{});
+    else f(t, Int<1>{});
+  });
+}
+
+static inline bool aligned16(std::initializer_list<const void*> ptrs) {
+  uintptr_t all = 0;
+  for (const void* p : ptrs) all |= reinterpret_cast<uintptr_t>(p);
+  return (all & 15) == 0;
+}
 
 #define XVIT_REQUIRE(cond, ...)            \
   do {                                     \
@@ -93,6 +107,12 @@ static void by_src_dtype(int dtype, F&& f) {   // by_dtype and XVIT_I16: the ent
 #define XVIT_REQUIRE_COUNTER(who, counter, advance)                                                  \
   XVIT_REQUIRE(((uintptr_t)(counter) & 7) == 0, who ": the counter must be 8-byte aligned");         \
   XVIT_REQUIRE((counter) || !(advance), who ": advance needs a counter")
+// What the entry points that take a [B, M, 1, D, H, W] volume and a patch refuse alike, under the caller's name (a const char*): reads the caller's B, M, D, H, W, dp, hp, wp, as every such entry point names them.
+#define XVIT_REQUIRE_PATCH_GRID(who, dtypes_ok)                                                                                    \
+  XVIT_REQUIRE(B > 0 && M > 0 && D > 0 && H > 0 && W > 0 && dp > 0 && hp > 0 && wp > 0, "%s: bad sizes", who);                    \
+  XVIT_REQUIRE(D % dp == 0 && H % hp == 0 && W % wp == 0, "%s: image dimensions must be divisible by the patch size", who);       \
+  XVIT_REQUIRE(dtypes_ok, "%s: bad dtype (bf16 or fp32)", who)
+static inline bool dtype_ok(int dtype) { return dtype == XVIT_F32 || dtype == XVIT_BF16; }
 static inline bool prob_ok(float p) { return p >= 0.f && p <= 1.f; }   // false for NaN
 static inline bool range_ok(float lo, float hi) { return lo <= hi && isfinite(lo) && isfinite(hi); }
 

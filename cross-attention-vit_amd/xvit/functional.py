@@ -795,7 +795,7 @@ class PatchEmbedFn(Function):
         # geometries) go through the patchify kernel, which also converts
         fused = not concat and ops.patch_embed_supported(img, patch, d, cls_rows=1)
         if fused:
-            N = 1 + (img.shape[3] // patch[0]) * (img.shape[4] // patch[1]) * (img.shape[5] // patch[2])
+            N = 1 + ops._patch_counts(img.shape, patch)[0]
             pos2 = pos.detach().reshape(N, d)
             x = ops.patch_embed_fwd(img, patch, w_s, b, pos2, cls_rows=1)
             patches = img
@@ -839,7 +839,7 @@ class PatchEmbedFn(Function):
         Bn, M = img.shape[0], img.shape[1]
         d, pd = w_s.shape
         K, P = keep_idx.shape[1], slot.shape[1]
-        if P != (img.shape[3] // patch[0]) * (img.shape[4] // patch[1]) * (img.shape[5] // patch[2]) or pos.numel() != (P + 1) * d:
+        if P != ops._patch_counts(img.shape, patch)[0] or pos.numel() != (P + 1) * d:
             raise RuntimeError(f"PatchEmbedFn: keep was drawn for {P} patches per sequence, which is not this volume's patch grid")
         N = K + 1
         patches = ops.patchify_select(img.contiguous(), patch, keep_idx).reshape(-1, pd)       # [M*B*N, pd], row 0 of each sequence = 0
@@ -980,7 +980,7 @@ def _input_grad(dxb, w_s, shape, patch, concat, dtype):
     if not concat and ops.patch_embed_dgrad_supported(shape, patch, d, cls_rows=1):
         return ops.patch_embed_dgrad(dxb, w_s, shape, patch, dtype)
     B, M = shape[0], shape[1]
-    P = (shape[3] // patch[0]) * (shape[4] // patch[1]) * (shape[5] // patch[2])
+    P = ops._patch_counts(shape, patch)[0]
     out = torch.empty(shape, dtype=dtype, device=dxb.device)
     if concat:   # ModelVIT: one sequence per sample, cls + the patches of every modality
         S = M * P + 1

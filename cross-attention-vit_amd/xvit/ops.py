@@ -4,6 +4,7 @@ is not on the GPU is an error."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -486,6 +487,21 @@ def xattn_kv_dgrad(coef, R, B, N, H, d):
     return dhn
 
 
+def _patch_counts(shape, patch):
+    """(P, pd) of a [B, M, 1, D, H, W] volume tensor: patches per volume and voxels per patch."""
+    (D, H, W), (dp, hp, wp) = shape[3:], patch
+    return (D // dp) * (H // hp) * (W // wp), dp * hp * wp
+
+
+def _patch_place(B, M, P, pad_cls_row, concat):
+    """Where patchify puts the patch rows -> ((stride_b, stride_m, row_off, zero_rows, zero_row_stride) in rows, the leading output shape)."""
+    if concat:
+        rows = M * P + 1
+        return (rows, P, 1, B, rows), (B * rows,)
+    pad = int(bool(pad_cls_row))
+    return (P + pad, B * (P + pad), pad, M * B if pad else 0, P + pad), (M, B * (P + pad))
+
+
 def patchify(img, patch, pad_cls_row=False, concat=False):
     """img [B, M, 1, D, H, W] fp32|bf16 contiguous -> bf16 patch rows.
       default            [M, B*P, pd]           per modality, no padding
@@ -494,15 +510,9 @@ def patchify(img, patch, pad_cls_row=False, concat=False):
     assert img.dim() == 6 and img.shape[2] == 1 and img.is_contiguous()
     B, M, _, D, H, W = img.shape
     dp, hp, wp = patch
-    P, pd = (D // dp) * (H // hp) * (W // wp), dp * hp * wp
-    if concat:
-        rows = M * P + 1
-        out = torch.empty(B * rows, pd, dtype=torch.bfloat16, device=img.device)
-        place = (rows, P, 1, B, rows)
-    else:
-        pad = int(bool(pad_cls_row))
-        out = torch.empty(M, B * (P + pad), pd, dtype=torch.bfloat16, device=img.device)
-        place = (P + pad, B * (P + pad), pad, M * B if pad else 0, P + pad)
+    P, pd = _patch_counts(img.shape, patch)
+    place, lead = _patch_place(B, M, P, pad_cls_row, concat)
+    out = torch.empty(*lead, pd, dtype=torch.bfloat16, device=img.device)
     _run("patchify", img.numel() * (img.element_size() + 2.0), "byte",
          lambda: _lib.load().xvit_patchify(_ptr(img), _dt(img), _ptr(out), B, M, D, H, W, dp, hp, wp, *place, _stream()), "xvit_patchify")
     return out
@@ -537,7 +547,7 @@ def patch_embed_fwd(img, patch, w_b, bias, pos, cls_rows=1):
     (model_cross.py:193-197).  w_b: bf16 [d, pd]; pos: fp32 [cls_rows + P, d] or None."""
     g = _patch_geom(img, patch, cls_rows)
     B, M, _, D, H, W = img.shape
-    P, pd = (D // patch[0]) * (H // patch[1]) * (W // patch[2]), patch[0] * patch[1] * patch[2]
+    P, pd = _patch_counts(img.shape, patch)
     d = w_b.shape[0]
     assert w_b.dtype == torch.bfloat16 and w_b.shape[1] == pd and (pos is None or pos.shape == (cls_rows + P, d))
     rows = M * B * (cls_rows + P)
@@ -553,7 +563,7 @@ def patch_embed_wgrad(img, patch, dx_b, cls_rows=1, out=None):
     """dW [d, pd] fp32 = sum over patch rows of dx[row]^T patch(row); dx_b: bf16 [M*B*(cls_rows + P), d]."""
     g = _patch_geom(img, patch, cls_rows)
     B, M, _, D, H, W = img.shape
-    P, pd = (D // patch[0]) * (H // patch[1]) * (W // patch[2]), patch[0] * patch[1] * patch[2]
+    P, pd = _patch_counts(img.shape, patch)
     d = dx_b.shape[1]
     assert dx_b.dtype == torch.bfloat16 and dx_b.shape[0] == M * B * (cls_rows + P) and dx_b.is_contiguous()
     need = _lib.load().xvit_patch_embed_wgrad_workspace_bytes(C.byref(g), d)
@@ -582,7 +592,7 @@ def patch_embed_dgrad(dx_b, w_b, shape, patch, dtype=torch.float32, cls_rows=1, 
     shape = tuple(shape)
     g = _patch_geom_of(shape, patch, cls_rows)
     B, M, _, D, H, W = shape
-    P, pd = (D // patch[0]) * (H // patch[1]) * (W // patch[2]), patch[0] * patch[1] * patch[2]
+    P, pd = _patch_counts(shape, patch)
     d = w_b.shape[0]
     assert dx_b.dtype == torch.bfloat16 and dx_b.shape == (M * B * (cls_rows + P), d) and dx_b.stride(1) == 1
     assert w_b.dtype == torch.bfloat16 and w_b.shape == (d, pd) and w_b.stride(1) == 1
@@ -600,16 +610,11 @@ def unpatchify(patches, out, patch, pad_cls_row=False, concat=False):
     assert out.dim() == 6 and out.shape[2] == 1 and out.is_contiguous()
     B, M, _, D, H, W = out.shape
     dp, hp, wp = patch
-    P, pd = (D // dp) * (H // hp) * (W // wp), dp * hp * wp
-    if concat:
-        rows = M * P + 1
-        place, n = (rows, P, 1), B * rows
-    else:
-        pad = int(bool(pad_cls_row))
-        place, n = (P + pad, B * (P + pad), pad), M * B * (P + pad)
-    assert patches.dtype == torch.float32 and patches.is_contiguous() and patches.numel() == n * pd
+    P, pd = _patch_counts(out.shape, patch)
+    place, lead = _patch_place(B, M, P, pad_cls_row, concat)
+    assert patches.dtype == torch.float32 and patches.is_contiguous() and patches.numel() == math.prod(lead) * pd
     _run("unpatchify", out.numel() * (4.0 + out.element_size()), "byte",
-         lambda: _lib.load().xvit_unpatchify(_ptr(patches), _ptr(out), _dt(out), B, M, D, H, W, dp, hp, wp, *place, _stream()), "xvit_unpatchify")
+         lambda: _lib.load().xvit_unpatchify(_ptr(patches), _ptr(out), _dt(out), B, M, D, H, W, dp, hp, wp, *place[:3], _stream()), "xvit_unpatchify")
     return out
 
 
@@ -644,7 +649,7 @@ def patchify_select(img, patch, keep_idx, out=None):
     assert img.dim() == 6 and img.shape[2] == 1 and img.is_contiguous()
     B, M, _, D, H, W = img.shape
     dp, hp, wp = patch
-    pd = dp * hp * wp
+    pd = _patch_counts(img.shape, patch)[1]
     K = keep_idx.shape[1]
     _i32c(keep_idx, (M * B, K), "keep_idx")
     out = out if out is not None else torch.empty(M, B * (K + 1), pd, dtype=torch.bfloat16, device=img.device)
@@ -758,10 +763,10 @@ def _mae_loss_geom(pred, drop_idx, img, patch):
     assert img.dim() == 6 and img.shape[2] == 1 and img.is_contiguous(), "mae loss: need a contiguous volume tensor [B, M, 1, D, H, W]"
     B, M, _, D, H, W = img.shape
     dp, hp, wp = patch
-    Rm = drop_idx.shape[1]
+    Rm, pd = drop_idx.shape[1], _patch_counts(img.shape, patch)[1]
     _i32c(drop_idx, (M * B, Rm), "drop_idx")
-    assert pred.dim() == 2 and pred.is_contiguous() and tuple(pred.shape) == (M * B * Rm, dp * hp * wp), \
-        f"mae loss: pred must be a contiguous [{M * B * Rm}, {dp * hp * wp}] tensor, got {tuple(pred.shape)}"
+    assert pred.dim() == 2 and pred.is_contiguous() and tuple(pred.shape) == (M * B * Rm, pd), \
+        f"mae loss: pred must be a contiguous [{M * B * Rm}, {pd}] tensor, got {tuple(pred.shape)}"
     return (B, M, D, H, W, dp, hp, wp, Rm)
 
 
