@@ -8,12 +8,17 @@ ready during backward (reverse registration order: heads -> last MultiScaleBlock
 shared patch embedding last).  When the last gradient of a bucket has been accumulated its
 all-reduce is issued immediately on a SIDE stream behind an event, so RCCL traffic overlaps the
 rest of backward; `finish()` makes the compute stream wait for the tail.  After `finish()` every
-`p.grad` is a view into its bucket (no copy back).
+`p.grad` is a view into its bucket (no copy back).  One backward per `finish()`: a second gradient for a
+parameter (or for a bucket already on the wire) in the same round is refused, not dropped.
 
 No pack pass for the weight matrices: `grad_sink()` maps every 2-D parameter (by the address of the fp32 master and of
 its bf16 operand copy) to its bucket view, and with `xvit.functional.GRAD_SINK` set to it the weight-gradient kernels
 write straight into the buckets (the gradient autograd hands on IS the view); the 1/world of the mean rides on the
 collective itself (ReduceOp.AVG on RCCL).  What is left to copy are the 1-D gradients (biases, norms: 0.3 % of the bytes).
+The sink's rule in eager mode: a view is handed out only while its parameter has NO .grad.  A kept p.grad (zeroed in place, or
+accumulating over several backward + finish() rounds) IS the view after finish(); a kernel writing there would make AccumulateGrad add
+the view to itself.  The kernel then gets a fresh tensor, autograd adds it into the view, and p.grad = reduce(p.grad_old + g_local) as
+with plain autograd.
 
 With a captured step (`xvit.graph.GraphedStep(model, img, labels, reducer=...)`) the same logic runs from TENSOR hooks on
 the step's leaf aliases while the graph is being captured, so the bucket all-reduces become nodes of the graph, forked
@@ -60,7 +65,7 @@ def comm_dtype_from(comm_dtype=None):
 
 
 class _Bucket:
-    __slots__ = ("params", "flat", "views", "offsets", "wire", "done", "pending", "work", "launched", "events")
+    __slots__ = ("params", "flat", "views", "offsets", "wire", "done", "pending", "seen", "work", "launched", "events", "waited")
 
     def __init__(self, params, device, comm_dtype=torch.float32):
         self.params = params
@@ -75,7 +80,9 @@ class _Bucket:
         self.wire = torch.zeros(self.flat.numel(), dtype=comm_dtype, device=device) if comm_dtype != torch.float32 else None
         self.done = torch.cuda.Event() if self.wire is not None and device.type == "cuda" else None
         self.pending, self.work, self.launched = len(params), None, False
-        self.events = {}      # stream id -> (stream, event): the latest gradient write of this bucket on each stream
+        self.seen = set()     # id(p) of the parameters whose gradient has arrived since the last finish()
+        self.events = {}      # stream id -> (stream, event): the latest gradient write of this bucket on each stream; emptied by finish()
+        self.waited = 0       # how many of them the last launch waited for
 
 
 def plan_buckets(params, bucket_bytes: int):
@@ -93,6 +100,21 @@ def plan_buckets(params, bucket_bytes: int):
     if cur:
         buckets.append(cur)
     return buckets
+
+
+class GradSink(dict):
+    """{address of a weight matrix (fp32 master or bf16 operand copy) -> its bucket view}, plus the owner of every view: what
+    BucketedGradReducer.grad_sink() returns and xvit.functional._grad_out reads."""
+
+    def __init__(self, reducer):
+        super().__init__()
+        self.reducer = reducer
+        self.owner = {}       # view address -> parameter
+
+    def free(self, view) -> bool:
+        """May a weight-gradient kernel write into `view` now?  Captured step: always (p.grad IS the view by design, the step takes its
+        gradients with autograd.grad).  Eager: only while the owner has no .grad, else AccumulateGrad would add the view to itself."""
+        return self.reducer._graph_mode or self.owner[view.data_ptr()].grad is None
 
 
 class BucketedGradReducer:
@@ -124,23 +146,31 @@ class BucketedGradReducer:
 
     def grad_sink(self, model=None):
         """{address -> bucket view} for every weight matrix: its fp32 master and, when `model` keeps a flat bf16 operand copy
-        (ModelCross: xvit.functional.FlatWeights), that copy's view.  Assign to xvit.functional.GRAD_SINK."""
-        sink = {}
+        (ModelCross: xvit.functional.FlatWeights), that copy's view.  Assign to xvit.functional.GRAD_SINK.  In eager mode a view is
+        handed out only while its parameter has no .grad (GradSink.free; module docstring)."""
+        sink = GradSink(self)
         for b in self.buckets:
             for p, v in zip(b.params, b.views):
                 if p.dim() == 2:
                     sink[p.data_ptr()] = v
+                    sink.owner[v.data_ptr()] = p
         flat = getattr(model, "_flat", None) if model is not None else None
         if flat is not None:
             for p, v16 in zip(flat.params, flat.view16):
                 v = self._view_of.get(id(p))
                 if v is not None:
                     sink[v16.data_ptr()] = v
+                    sink.owner[v.data_ptr()] = p
         return sink
 
     # ---- per-gradient hook (runs inside backward) ----------------------------------------------
     def _on_grad(self, p):
         b = self._bucket_of[id(p)]
+        if b.launched or id(p) in b.seen:
+            raise RuntimeError("BucketedGradReducer: a second gradient arrived for a " + ("bucket whose all-reduce has already been issued" if b.launched else
+                               "parameter") + " in this round, so it would never be reduced. Call finish() after every backward (gradient accumulation: "
+                               "one finish() per backward, keeping p.grad)")
+        b.seen.add(id(p))
         if self.cuda:
             # The model's modality branches and fusions run on their own streams, and autograd replays each backward node
             # on the stream of its forward, so the gradients of ONE bucket are written on several streams.  The hook runs
@@ -196,6 +226,7 @@ class BucketedGradReducer:
             with torch.cuda.stream(self.comm_stream):
                 for _, ev in b.events.values():        # every stream that wrote one of this bucket's gradients
                     self.comm_stream.wait_event(ev)
+                b.waited = len(b.events)
                 if not torch.cuda.is_current_stream_capturing():
                     for g in grads:                    # allocated on a branch stream, last read here
                         g.record_stream(self.comm_stream)
@@ -262,6 +293,8 @@ class BucketedGradReducer:
             for p, v in zip(b.params, b.views):
                 p.grad = v
             b.pending, b.work, b.launched = len(b.params), None, False
+            b.seen.clear()
+            b.events.clear()   # the collective is behind them; events of a captured round must never be waited for by an eager one
 
     def zero_grad(self):
         """Drop gradients (set_to_none semantics) so the next backward writes fresh tensors."""

@@ -277,11 +277,15 @@ GRAD_SINK = None
 
 
 def _grad_out(like, shape, device):
-    """Destination of a weight gradient: the reducer's bucket view registered for `like` (a master weight or its bf16 copy), else a fresh tensor."""
+    """Destination of a weight gradient: the reducer's bucket view registered for `like` (a master weight or its bf16 copy), else a fresh tensor.
+    A sink that knows its owners (xvit.ddp.GradSink) withholds the view in eager mode while the owning parameter has a .grad: that .grad
+    is the view itself after finish(), and AccumulateGrad would add the view to itself (2 * g, whatever was accumulated before lost)."""
     if GRAD_SINK is not None and like is not None:
         v = GRAD_SINK.get(like.data_ptr())
         if v is not None and tuple(v.shape) == tuple(shape):
-            return v.detach()                 # a fresh alias: autograd may take it over (its use count is 1)
+            free = getattr(GRAD_SINK, "free", None)
+            if free is None or free(v):
+                return v.detach()             # a fresh alias: autograd may take it over (its use count is 1)
     return torch.empty(*shape, dtype=torch.float32, device=device)
 
 

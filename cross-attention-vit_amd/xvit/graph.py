@@ -71,6 +71,7 @@ class GraphedStep:
                                    + ("(capturable=False)" if isinstance(optimizer, FusedAdam) else "") + ". Leave optimizer=None and step it after the replay")
         self.optimizer = optimizer
         # dropout active anywhere in the step: a device-side epoch makes every replay draw new masks (module docstring)
+        self._training = model.training        # frozen into the graph: the epoch below, and every kernel choice that depends on the mode
         self._epoch = torch.zeros(1, dtype=torch.int64, device=img.device) if model.training and _has_dropout(model) else None
         if os.environ.get("XVIT_FANOUT", "1") != "1" and os.environ.get("XVIT_GRAPH_STREAMS", "1") == "1":
             # without the fan-out node a branch output read by two forked fusions has its gradients accumulated by the autograd
@@ -182,6 +183,10 @@ class GraphedStep:
         if any(p.data_ptr() != q for p, q in zip(self.params, self._ptrs)) or getattr(self.model, "_flat", None) is not self._flat:
             raise RuntimeError("GraphedStep: the model's parameter storage changed after capture (model.to(...), a re-built flat weight buffer): "
                                "the captured graph would keep training the old buffers; build a new GraphedStep")
+        if self.model.training != self._training:
+            mode = lambda t: "training" if t else "eval"          # noqa: E731
+            raise RuntimeError(f"GraphedStep: the step was captured in {mode(self._training)} mode and the model is now in {mode(self.model.training)} mode; "
+                               "the replay would keep the captured mode (dropout, patch dropout and mix draws included). Restore the mode, or build a new GraphedStep")
         if self.optimizer is not None:
             self.optimizer.check_addresses(grads=False)    # the graph owns the gradient buffers; the optimizer's parameters must not have moved
             self.optimizer.sync_lr()

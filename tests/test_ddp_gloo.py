@@ -6,6 +6,7 @@ import os
 import socket
 import sys
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -51,14 +52,53 @@ def _worker(rank, world, port, out_dir):
     assert launched_in_backward >= 3 * (len(red.buckets) - 1)  # all but the unused-parameter bucket fire from hooks
     assert red.exposed_launches == 3 and float(unused.grad.abs().max()) == 0.0
     torch.save(model.state_dict(), os.path.join(out_dir, f"p{rank}.pt"))
+    # one accumulation round on the trained replicas: two backward + finish() with p.grad kept in between.  The local gradients of both
+    # rounds come from autograd.grad, which neither touches p.grad nor runs the reducer's hooks.
+    gx = torch.Generator().manual_seed(9)
+    xa, ya = torch.randn(32, 24, generator=gx), torch.randint(0, 3, (32,), generator=gx)
+    params = list(model.parameters())
+    acc = {"local": [], "after": []}
+    red.zero_grad()
+    for rnd in range(2):
+        sl = slice(rnd * 16 + rank * 8, rnd * 16 + (rank + 1) * 8)
+        acc["local"].append([g.clone() for g in torch.autograd.grad(nn.functional.cross_entropy(model(xa[sl]), ya[sl]), params)])
+        nn.functional.cross_entropy(model(xa[sl]), ya[sl]).backward()
+        red.finish()
+        acc["after"].append([p.grad.clone() for p in params])
+    torch.save(acc, os.path.join(out_dir, f"acc{rank}.pt"))
     dist.destroy_process_group()
 
 
-def test_bucketed_reducer_world2(tmp_path):
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
-    g0, g1 = torch.load(tmp_path / "g0.pt"), torch.load(tmp_path / "g1.pt")
-    p0, p1 = torch.load(tmp_path / "p0.pt"), torch.load(tmp_path / "p1.pt")
+@pytest.fixture(scope="module")
+def world2_dir(tmp_path_factory):
+    """both tests of the worker read the files of ONE two-rank run"""
+    out = tmp_path_factory.mktemp("world2")
+    mp.spawn(_worker, args=(2, _free_port(), str(out)), nprocs=2, join=True)
+    return out
+
+
+def test_bucketed_reducer_world2_accumulation(world2_dir):
+    """After two backward + finish() rounds with p.grad kept, p.grad == mean(g1) + mean(g2) on every rank.  Element-wise bound
+    3 * 2^-24 * (|acc| + |g_0| + |g_1|), with acc the reduced gradient of round 1 and g_r rank r's local gradient of round 2: derived,
+    not measured.  Rank r adds g_r to acc (one fp32 rounding, <= 2^-24 (|acc| + |g_r|)), halves it (exact) and gloo sums the two shares
+    (one rounding, <= 2^-24 (|acc| + (|g_0| + |g_1|) / 2)); acc itself carries the rounding of round 1's sum (<= 2^-24 |acc|) against
+    the float64 mean it is compared with.  Sum: 2^-24 (3 |acc| + |g_0| + |g_1|), inside the bound."""
+    a0, a1 = torch.load(world2_dir / "acc0.pt"), torch.load(world2_dir / "acc1.pt")
+    for i in range(len(a0["after"][0])):
+        for rnd in range(2):
+            assert torch.equal(a0["after"][rnd][i], a1["after"][rnd][i]), (rnd, i)          # identical on every rank
+        m1 = (a0["local"][0][i].double() + a1["local"][0][i].double()) / 2
+        m2 = (a0["local"][1][i].double() + a1["local"][1][i].double()) / 2
+        acc = a0["after"][0][i].double().abs()
+        bound = 3 * 2.0 ** -24 * (acc + a0["local"][1][i].double().abs() + a1["local"][1][i].double().abs())
+        err = (a0["after"][1][i].double() - (m1 + m2)).abs()
+        assert (err <= bound).all(), (i, float((err - bound).max()))
+        assert float(m2.abs().max()) > 0 and not torch.equal(a0["after"][1][i], a0["after"][0][i]), i   # the second round really added something
+
+
+def test_bucketed_reducer_world2(world2_dir):
+    g0, g1 = torch.load(world2_dir / "g0.pt"), torch.load(world2_dir / "g1.pt")
+    p0, p1 = torch.load(world2_dir / "p0.pt"), torch.load(world2_dir / "p1.pt")
     # single-process reference: rank 0's initial weights, the whole batch
     model = _model(seed=100)
     g = torch.Generator().manual_seed(7)
