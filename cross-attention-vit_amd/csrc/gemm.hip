@@ -731,12 +731,12 @@ struct Transpose8 {
 #pragma unroll
       for (int k = 0; k < 2; ++k) roffw[par][k] = (uint32_t)(rr * 256 + (((2 * c + k) ^ ((par * 8 + rr) & 15)) << 4));
   }
-  template <int PASS>
+  template <int FIRST, int COUNT>   // the 16-row accumulator tiles FIRST .. FIRST + COUNT - 1 = one pass
   __device__ __forceinline__ void write(XVIT_LDS char* slice, const f32x4 (&acc)[8][4]) const {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < COUNT; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) *(XVIT_LDS f32x4*)(slice + i * 4096 + woff[j]) = acc[PASS * 4 + i][j];
+      for (int j = 0; j < 4; ++j) *(XVIT_LDS f32x4*)(slice + i * 4096 + woff[j]) = acc[FIRST + i][j];
   }
   // the lane's 8 columns of row 8 it + rr of the pass (it = 0..7)
   __device__ __forceinline__ void read(const XVIT_LDS char* slice, int it, f32x4& v0, f32x4& v1) const {
@@ -747,19 +747,20 @@ struct Transpose8 {
 // Region R (0..7) = 2 bodies = rows 16 R .. 16 R + 15 of the wave tile (one scheduling window: with 4 bodies of 8 elements
 // in one window the allocator spills); regions 0-3 and 4-7 share one LDS transpose pass.  prefetch(nxt) issues the next region's
 // loads in front of this region's stores; body(v0, v1, cur, b) consumes body b of `cur`, the loads issued one region earlier.
-template <int R, class Loads, class Prefetch, class Body>
+template <int R, int PASS = 64, class Loads, class Prefetch, class Body>
 __device__ __forceinline__ void transpose8_regions(const Transpose8& t, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, Loads& cur, const Prefetch& prefetch, const Body& body) {
-  if constexpr ((R & 3) == 0) t.write<(R >> 2)>(slice, acc);
+  constexpr int RPP = PASS / 16;   // regions per pass: 4, or 2 under the tile loop (half the slice)
+  if constexpr (R % RPP == 0) t.write<R, RPP>(slice, acc);
   Loads nxt;
   if constexpr (R < 7) prefetch(nxt);
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
     f32x4 v0, v1;
-    t.read(slice, (R & 3) * 2 + b, v0, v1);   // 8-row group inside the 64-row pass
+    t.read(slice, (R % RPP) * 2 + b, v0, v1);   // 8-row group inside the pass
     body(v0, v1, cur, b);
   }
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (R < 7) transpose8_regions<R + 1>(t, acc, slice, nxt, prefetch, body);
+  if constexpr (R < 7) transpose8_regions<R + 1, PASS>(t, acc, slice, nxt, prefetch, body);
 }
 
 typedef __attribute__((ext_vector_type(8))) float f32x8;
@@ -818,7 +819,7 @@ __device__ __forceinline__ void wide_body(const GemmParams& p, WideEpi& e, f32x4
   e.row += 8; e.c += e.c_step; e.aux += e.aux_step;
 }
 
-template <int ACT, bool DROP>
+template <int ACT, bool DROP, int PASS = 64>
 __device__ __forceinline__ void wide_epilogue(const GemmParams& p, WideEpi& e, const f32x4 (&acc)[8][4], XVIT_LDS char* slice, const Transpose8& t, float* colsum_dst) {
   WideCursor lc = {e.row, e.aux};
   const auto prefetch = [&](WideLoads& L) {
@@ -826,14 +827,14 @@ __device__ __forceinline__ void wide_epilogue(const GemmParams& p, WideEpi& e, c
   };
   WideLoads first;
   prefetch(first);
-  transpose8_regions<0>(t, acc, slice, first, prefetch, [&](f32x4 v0, f32x4 v1, const WideLoads& cur, int b) { wide_body<ACT, DROP>(p, e, v0, v1, cur.aux[b]); });
+  transpose8_regions<0, PASS>(t, acc, slice, first, prefetch, [&](f32x4 v0, f32x4 v1, const WideLoads& cur, int b) { wide_body<ACT, DROP>(p, e, v0, v1, cur.aux[b]); });
   if (colsum_dst) {   // lanes l, l+8, ..., l+56 share their 8 columns
     colsum_flush<8>(colsum_dst, e.csum0, e.col_ok);
     colsum_flush<8>(colsum_dst + 4, e.csum1, e.col_ok);
   }
 }
 
-template <int ACT>
+template <int ACT, int PASS = 64>
 __device__ __forceinline__ void wave_tile_epilogue_wide(const GemmParams& p, const f32x4 (&acc)[8][4], XVIT_LDS char* smem, int wave, int lane, int row0, int col0,
                                                         int batch) {
   WideEpi e;
@@ -845,7 +846,7 @@ __device__ __forceinline__ void wave_tile_epilogue_wide(const GemmParams& p, con
   const int wl = pin_lane(lane);
   Transpose8 t;
   t.init(wl);
-  XVIT_LDS char* slice = smem + wave * EPI_WAVE_BYTES;
+  XVIT_LDS char* slice = smem + wave * (PASS * 256);
   e.col = (uint32_t)(col0 + (wl & 7) * 8);
   e.col_ok = e.col < (uint32_t)p.N;
   e.bias0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rbias, e.col * 4, 0, 0));
@@ -858,7 +859,7 @@ __device__ __forceinline__ void wave_tile_epilogue_wide(const GemmParams& p, con
   e.aux = e.row * (uint32_t)p.ldaux * 2u + e.col * 2u;
   e.c_step = 8u * (uint32_t)p.ldc * 2u;
   e.aux_step = 8u * (uint32_t)p.ldaux * 2u;
-  wide_epilogue<ACT, false>(p, e, acc, slice, t, colsum_dst);
+  wide_epilogue<ACT, false, PASS>(p, e, acc, slice, t, colsum_dst);
 }
 
 // Epilogue of one wave's 128 x 64 accumulator tile whose first element is (row0, col0); shared by every tile kernel
@@ -1004,13 +1005,24 @@ __device__ __forceinline__ void scatter_epilogue(const GemmParams& p, const f32x
 // Diagnostic build (tools/gemm_kstep_probe.py): workgroup b < 4096 leaves its lifetime in shader cycles (clock64) and in
 // ticks of the constant 100 MHz counter (wall_clock64); their ratio is the clock the CU ran at under this kernel's load.
 __device__ long long xvit_dbg_clk[2 * 4096];
+// Segments of the workgroup's FIRST tile, in shader cycles from kernel entry: mark(0) the first barrier passed (K-step 0 has
+// landed), mark(1) the K loop's end, mark(2) the last epilogue store issued.  (Under the tile loop the lifetime above covers
+// all of the workgroup's tiles, these three its first one.)
+__device__ long long xvit_dbg_seg[3 * 4096];
 struct ClockProbe {
-  long long c0, w0;
+  long long c0, w0, t[3] = {0, 0, 0};
   __device__ ClockProbe() : c0(clock64()), w0(wall_clock64()) {}
+  __device__ void mark(int i) { if (t[i] == 0) t[i] = clock64(); }
   __device__ ~ClockProbe() {
-    if (threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x < 4096) { xvit_dbg_clk[2 * blockIdx.x] = clock64() - c0; xvit_dbg_clk[2 * blockIdx.x + 1] = wall_clock64() - w0; }
+    if (threadIdx.x == 0 && blockIdx.z == 0 && blockIdx.x < 4096) {
+      xvit_dbg_clk[2 * blockIdx.x] = clock64() - c0; xvit_dbg_clk[2 * blockIdx.x + 1] = wall_clock64() - w0;
+      for (int i = 0; i < 3; ++i) xvit_dbg_seg[3 * blockIdx.x + i] = t[i] - c0;
+    }
   }
 };
+#define XVIT_PROBE_MARK(i) clock_probe.mark(i)
+#else
+#define XVIT_PROBE_MARK(i)
 #endif
 template <bool A_KS, bool B_KS, int WIDE_ACT, int GATHER = 0>
 __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
@@ -1095,6 +1107,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    XVIT_PROBE_MARK(0);
     const bool more = kt + 1 < nk;
     uint32_t soff_a, soff_b;
     step_off(kt + 1, soff_a, soff_b);
@@ -1105,12 +1118,139 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(const GemmParams p) {
     big_tile_mma<A_KS, B_KS>(sa, sb, fa, fb, acc, la, lb, more ? la.rsrc : null_rsrc, more ? lb.rsrc : null_rsrc, nxt, wave, soff_a, soff_b);
 #endif
   }
+  XVIT_PROBE_MARK(1);
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last iteration's (zero-fill) DMAs have landed before the stage buffers are recycled
   __syncthreads();   // every wave is done reading the last stage: the stage buffers become the transpose slices
   if constexpr (GATHER == 4) scatter_epilogue(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64);
   else if constexpr (WIDE_ACT >= 0) wave_tile_epilogue_wide<WIDE_ACT>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch);
   else wave_tile_epilogue<GATHER == 1, GATHER <= 1>(p, acc, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, batch, split);
+  XVIT_PROBE_MARK(2);
+}
+
+// ---- the tile loop: gemm_big_kernel's NT / NN products without split-K or batch, one resident workgroup per CU walking many tiles ----
+// gridDim.x = G <= tiles workgroups; workgroup b takes the dispatch slots b, b + G, b + 2 G, ... of gemm_big_kernel's grid, i.e. the
+// logical tiles xcd_logical(b + i G, tiles) of the same super-column walk.  With G = the CU count (a multiple of 8) an XCD holds at
+// any time the run of consecutive logical ids it holds under the one-tile-per-workgroup launch, so the L2 sharing of A row-panels and
+// W slices is unchanged.  Static assignment: no tile counter, nothing shared between workgroups.
+// What it removes is the exposed prologue of every tile but a workgroup's first: with one workgroup per CU nothing overlaps a
+// tile's set-up and the LDS-DMA round trip of its K-step 0.  Here the K ring runs across tiles: in a tile's last K-step the free stage
+// takes K-step 0 of the workgroup's NEXT tile (gemm_big_kernel fills zeros there), issued under that step's MFMAs like every other
+// step's loads.  The epilogue's LDS transposition therefore stays inside the stage just consumed: 8 KiB per wave, 32-row passes
+// (PASS = 32) instead of 64-row ones; the row -> LDS -> row mapping of every body is the same, so every output is bit-identical.
+// vmcnt retires in order, and the next tile's K-step 0 was issued BEFORE the epilogue's stores: its wait is a counted one that leaves
+// the EPI_STORES youngest operations in flight.  Every wide epilogue issues at least that many after the DMA, 16 C stores per wave;
+// z loads, aux stores and column-sum atomics only add to the count, and a count too small only waits longer.  The barrier that
+// follows that wait is also what hands the epilogue's stage to K-step 1's DMA.
+// The epilogue's state is rebuilt per tile behind pin_lane, the next tile's origin and operand resources in front of the last K-step;
+// across the K loops live the tile-invariant loader offsets and fragment addresses, as in gemm_big_kernel, and the tile's origin.
+// Behind the wide epilogues only: gemm_big_kernel's narrow instantiations stand at 104 of 106 SGPRs, and with the loop's state the same
+// epilogue spilled SGPRs in every form tried (profiles/gemm_persistent_ab.txt); those forms keep one workgroup per tile.
+// The kernel's parameters, re-read from the kernarg segment (GemmParams is the only argument: offset 0) through a pointer the
+// compiler cannot see through.  What a tile's set-up and epilogue need of them (about 60 SGPRs) is invariant in the tile loop:
+// read from `p` it is hoisted above the loop, stays live across the K loops and spills.
+__device__ __forceinline__ const GemmParams& reload_params() {
+  auto q = __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(q));
+  return *(const GemmParams*)q;
+}
+
+template <bool B_KS, int WIDE_ACT>
+__global__ __launch_bounds__(512, 2) void gemm_big_loop_kernel(const GemmParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  XVIT_LDS char* smem = (XVIT_LDS char*)smem_raw;
+#ifdef XVIT_GEMM_CLOCK_PROBE
+  ClockProbe clock_probe;
+#endif
+  static_assert(WIDE_ACT >= 0, "the tile loop exists behind the wide epilogues only");
+  constexpr int EPI_STORES = 16;
+  const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;   // 2 x 4 waves
+  // dispatch slot -> tile origin: gemm_big_kernel's remap and super-column walk
+  auto tile_origin = [](const GemmParams& q, int slot, int& m0, int& n0) {
+    const int tile = xcd_logical(slot, q.ntm * q.ntn);
+    const int grp = min(tile / (q.ntm * q.ncg), (q.ntn - 1) / q.ncg);
+    const int rem = tile - grp * q.ntm * q.ncg;
+    const int gw = min(q.ncg, q.ntn - grp * q.ncg);
+    const int tm = rem / gw, tn = grp * q.ncg + (rem - tm * gw);
+    m0 = tm * TBM; n0 = tn * TBN;
+  };
+  // the operand resources of the tile whose first row / column are m0 / n0
+  auto tile_rsrc = [](const GemmParams& q, int m0, int n0, __amdgpu_buffer_rsrc_t& ra, __amdgpu_buffer_rsrc_t& rb) {
+    const OperandTile ta = operand_tile<false>(q.A, q.lda, m0, q.M, 0, q.K), tb = operand_tile<B_KS>(q.B, q.ldb, n0, q.N, 0, q.K);
+    ra = make_rsrc(ta.base, clamp_bytes(ta.bytes));
+    rb = make_rsrc(tb.base, clamp_bytes(tb.bytes));
+  };
+  TileLoader<false, TBM> la;   // the lanes' offsets do not depend on the tile: only the resources are rebuilt, per tile
+  TileLoader<B_KS, TBN> lb;
+  la.init(OperandTile{p.A, 0}, p.lda, wave, lane);
+  lb.init(OperandTile{p.B, 0}, p.ldb, wave, lane);
+  TileFrag<false, TBM, 8> fa;
+  TileFrag<B_KS, TBN, 4> fb;
+  fa.init(wr * 8, lane);
+  fb.init(wc * 4, lane);
+
+  int slot = blockIdx.x;   // < tiles
+  int stage = 0;           // the stage that holds K-step 0 of the current tile
+  int m0, n0;
+  tile_origin(p, slot, m0, n0);
+  tile_rsrc(p, m0, n0, la.rsrc, lb.rsrc);
+  la.issue_at(smem, wave, 0u);
+  lb.issue_at(smem + T_OPER, wave, 0u);
+  for (;;) {
+    const bool first = slot == (int)blockIdx.x;   // the workgroup's first tile: nothing but its DMA is in flight at its first wait
+    const int nk = (reload_params().K + BK - 1) / BK;   // >= 1; per tile, or the loop conditions derived from it pile up as invariants of the tile loop
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt + 1 < nk; ++kt) {
+      if (kt == 0 && !first) wait_vmcnt<EPI_STORES>();
+      else wait_vmcnt<0>();
+      __syncthreads();
+      XVIT_PROBE_MARK(0);
+      XVIT_LDS char* nxt = smem + ((stage + kt + 1) & 1) * T_STAGE;
+      const XVIT_LDS char* sa = smem + ((stage + kt) & 1) * T_STAGE;
+      big_tile_mma<false, B_KS>(sa, sa + T_OPER, fa, fb, acc, la, lb, la.rsrc, lb.rsrc, nxt, wave, (uint32_t)(kt + 1) * la.kstep, (uint32_t)(kt + 1) * lb.kstep);
+    }
+    // the last K-step: the free stage takes K-step 0 of the next tile (zeros after the workgroup's last tile)
+    bool more;
+    int nm0 = 0, nn0 = 0;
+    __amdgpu_buffer_rsrc_t ra = make_rsrc(nullptr, 0u), rb = ra;   // every access out of range: the DMA fills zeros, fetches nothing
+    {
+      const GemmParams& q = reload_params();
+      more = slot + (int)gridDim.x < q.ntm * q.ntn;
+      if (more) {
+        tile_origin(q, slot + (int)gridDim.x, nm0, nn0);
+        tile_rsrc(q, nm0, nn0, ra, rb);
+      }
+    }
+    if (nk == 1 && !first) wait_vmcnt<EPI_STORES>();
+    else wait_vmcnt<0>();
+    __syncthreads();
+    XVIT_PROBE_MARK(0);
+    {
+      const XVIT_LDS char* sa = smem + ((stage + nk - 1) & 1) * T_STAGE;
+      big_tile_mma<false, B_KS>(sa, sa + T_OPER, fa, fb, acc, la, lb, ra, rb, smem + ((stage + nk) & 1) * T_STAGE, wave, 0u, 0u);
+    }
+    XVIT_PROBE_MARK(1);
+    if (!more) wait_vmcnt<0>();   // nothing may still be on its way into LDS when the workgroup ends
+    __syncthreads();   // every wave is done reading the last stage: it becomes the transpose slices; the other one is being filled
+    {
+      const GemmParams& q = reload_params();
+      // the wave's place in the tile from a fresh copy of the thread id, for the same reason as reload_params()
+      const int te = pin_lane(tid), we = uniform(te >> 6);
+      XVIT_LDS char* slices = smem + ((stage + nk - 1) & 1) * T_STAGE;
+      wave_tile_epilogue_wide<WIDE_ACT, 32>(q, acc, slices, we, te & 63, m0 + (we >> 2) * 128, n0 + (we & 3) * 64, 0);
+    }
+    XVIT_PROBE_MARK(2);
+    if (!more) break;
+    la.rsrc = ra; lb.rsrc = rb;
+    m0 = nm0; n0 = nn0;
+    slot += (int)gridDim.x;
+    stage = (stage + nk) & 1;
+  }
 }
 
 // split-K second pass: sum the partial tiles in a fixed order (bit-reproducible), then the full epilogue
@@ -1146,6 +1286,38 @@ static std::atomic<int> g_gemm_epi{0};       // xvit_set_option("gemm_epilogue")
 static std::atomic<int> g_gemm_res_pf{0};    // xvit_set_option("gemm_res_prefetch"): 0 = fp32 residual loaded one region ahead, 1 = loaded in the epilogue body
 static std::atomic<int> g_gemm_group{0};     // xvit_set_option("gemm_group"): 0 = auto, n > 0 = column tiles per super-column of the 256x256 tile walk
 
+static std::atomic<int> g_gemm_persist{0};   // xvit_set_option("gemm_persistent"): 0 = auto, 1 = one workgroup per tile, n >= 2 = the tile loop on at most n workgroups
+
+static int cu_count() {   // of the current device, asked once
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 0;
+    return v;
+  }();
+  return n;
+}
+
+// Workgroups of gemm_big_loop_kernel for this 256x256-tile product with a wide epilogue, or 0 = gemm_big_kernel's launch.  The loop
+// exists for NT / NN without split-K or batch (the split-K weight gradients are about one tile per CU; the gathered patch embedding
+// is not an xvit_gemm).  xvit_set_option("gemm_persistent", n >= 2) takes it wherever it exists, on at most n workgroups.
+// Auto takes it for the (layout, epilogue, K) classes measured faster at M = 64638 (profiles/gemm_persistent_ab.txt: parent build
+// against this one, 4 alternations, every run of this build faster than every run of the parent; us per call):
+//   NT plain K = 768 (qkv 215.0 -> 209.1, kv with bias 134.9 -> 128.8), NT GELU saving gelu' K = 768 (FFN1 363.1 -> 354.1),
+//   NN plain K = 768 (out-proj dgrad 73.2 -> 68.8), NN x saved gelu' K = 768 (FFN2 dgrad 346.9 -> 328.1).
+// At K = 2304 / 3072 (NN plain: qkv dgrad 186.4 -> 183.4, FFN1 dgrad 239.6 -> 238.6) the runs of the two builds overlap: the
+// prologue is 2-3 % of such a tile; they keep gemm_big_kernel's launch, as do the two epilogues that exchange z instead of gelu'(z),
+// which the model does not use and nobody measured.  Shorter K than 768 has the larger prologue share and goes with K = 768.
+static int loop_workgroups(const xvit_gemm_args* a, const GemmParams& p, int grid_z) {
+  const int opt = g_gemm_persist.load(std::memory_order_relaxed);
+  if (opt == 1 || a->layout == XVIT_GEMM_TN || grid_z != 1) return 0;
+  const int tiles = p.ntm * p.ntn;
+  if (opt >= 2) return std::min(tiles, opt);
+  const int cus = cu_count();
+  if (cus <= 0 || tiles < 2 * cus) return 0;   // under two rounds there is no second tile to hide a prologue behind
+  if (p.K > 768 || (p.act != XVIT_ACT_NONE && !p.aux_deriv)) return 0;
+  return cus;
+}
+
 static bool use_big_tile(const xvit_gemm_args* a) {
   if (a->M < 256 || a->N < 256 || g_gemm_tile.load(std::memory_order_relaxed) == 1) return false;
   if (g_gemm_tile.load(std::memory_order_relaxed) == 2) return true;   // diagnostics: the 256x256 kernel on grids of any size
@@ -1177,6 +1349,11 @@ template <bool A_KS, bool B_KS, int WIDE_ACT, int GATHER = 0>
 static void launch_big(const GemmParams& p, int grid_z, hipStream_t s) {
   launch_lds<gemm_big_kernel<A_KS, B_KS, WIDE_ACT, GATHER>, T_LDS, 512>(dim3(p.ntm * p.ntn, 1, grid_z), s, p);
 }
+// The tile loop over p's tile grid on `wgs` workgroups (an NT / NN product with a wide epilogue, no split-K, no batch)
+template <bool B_KS, int WIDE_ACT>
+static void launch_loop(const GemmParams& p, int wgs, hipStream_t s) {
+  launch_lds<gemm_big_loop_kernel<B_KS, WIDE_ACT>, T_LDS, 512>(dim3(wgs, 1, 1), s, p);
+}
 template <bool A_KS, bool B_KS>
 static void launch_small(const GemmParams& p, int grid_z, hipStream_t s) {
   launch_lds<gemm_kernel<A_KS, B_KS>, GEMM_LDS, 256>(dim3(p.ntm * p.ntn, 1, grid_z), s, p);
@@ -1193,6 +1370,7 @@ extern "C" int xvit_set_option(const char* name, int value) {
   if (n == "gemm_tile") { XVIT_REQUIRE(value >= 0 && value <= 2, "xvit_set_option: gemm_tile must be 0 (auto), 1 (128x128 only) or 2 (256x256 whenever M, N >= 256)"); g_gemm_tile = value; return 0; }
   if (n == "gemm_group") { XVIT_REQUIRE(value >= 0 && value <= 4096, "xvit_set_option: gemm_group must be in [0, 4096]"); g_gemm_group = value; return 0; }
   if (n == "gemm_epilogue") { XVIT_REQUIRE(value == 0 || value == 1, "xvit_set_option: gemm_epilogue must be 0 (auto) or 1 (narrow)"); g_gemm_epi = value; return 0; }
+  if (n == "gemm_persistent") { XVIT_REQUIRE(value >= 0 && value <= 4096, "xvit_set_option: gemm_persistent must be 0 (auto), 1 (one workgroup per tile) or 2..4096 (the tile loop on at most that many workgroups)"); g_gemm_persist = value; return 0; }
   if (n == "gemm_res_prefetch") { XVIT_REQUIRE(value == 0 || value == 1, "xvit_set_option: gemm_res_prefetch must be 0 (one region ahead) or 1 (in the body)"); g_gemm_res_pf = value; return 0; }
   if (n == "attn_peel") { XVIT_REQUIRE(value >= 0 && value <= 2, "xvit_set_option: attn_peel must be 0 (token 0 stays on the tile grid), 1 (auto: large grids) or 2 (whenever N = 64 m + 1)"); set_attn_peel(value); return 0; }
   set_error("xvit_set_option: unknown option '%s'", name);
@@ -1265,12 +1443,13 @@ extern "C" int xvit_gemm(const xvit_gemm_args* a, xvit_stream_t stream) {
     // NONE or GELU, dgrads NONE or GELU'; wgrads store fp32; with dropout the narrow kernels run)
     const bool wide = !p.c_f32 && !p.slab && !p.res && p.seg_rows == 0 && !p.narrow_epi && p.drop_p == 0.f && a->layout != XVIT_GEMM_TN &&
                       ((p.N | (int)p.ldc | (int)p.ldaux) & 7) == 0 && (a->layout == XVIT_GEMM_NT ? p.act != XVIT_ACT_DGELU : p.act != XVIT_ACT_GELU);
-    if (wide && a->layout == XVIT_GEMM_NT && p.act == XVIT_ACT_NONE) launch_big<false, false, XVIT_ACT_NONE>(p, gz, s);
-    else if (wide && a->layout == XVIT_GEMM_NT && p.aux_deriv) launch_big<false, false, ACT_GELU_D>(p, gz, s);
-    else if (wide && a->layout == XVIT_GEMM_NT) launch_big<false, false, XVIT_ACT_GELU>(p, gz, s);
-    else if (wide && p.act == XVIT_ACT_NONE) launch_big<false, true, XVIT_ACT_NONE>(p, gz, s);
-    else if (wide && p.aux_deriv) launch_big<false, true, ACT_MULAUX>(p, gz, s);
-    else if (wide) launch_big<false, true, XVIT_ACT_DGELU>(p, gz, s);
+    const int lw = wide ? loop_workgroups(a, p, gz) : 0;   // > 0: the tile loop on that many workgroups
+    if (wide && a->layout == XVIT_GEMM_NT && p.act == XVIT_ACT_NONE) lw ? launch_loop<false, XVIT_ACT_NONE>(p, lw, s) : launch_big<false, false, XVIT_ACT_NONE>(p, gz, s);
+    else if (wide && a->layout == XVIT_GEMM_NT && p.aux_deriv) lw ? launch_loop<false, ACT_GELU_D>(p, lw, s) : launch_big<false, false, ACT_GELU_D>(p, gz, s);
+    else if (wide && a->layout == XVIT_GEMM_NT) lw ? launch_loop<false, XVIT_ACT_GELU>(p, lw, s) : launch_big<false, false, XVIT_ACT_GELU>(p, gz, s);
+    else if (wide && p.act == XVIT_ACT_NONE) lw ? launch_loop<true, XVIT_ACT_NONE>(p, lw, s) : launch_big<false, true, XVIT_ACT_NONE>(p, gz, s);
+    else if (wide && p.aux_deriv) lw ? launch_loop<true, ACT_MULAUX>(p, lw, s) : launch_big<false, true, ACT_MULAUX>(p, gz, s);
+    else if (wide) lw ? launch_loop<true, XVIT_ACT_DGELU>(p, lw, s) : launch_big<false, true, XVIT_ACT_DGELU>(p, gz, s);
     else if (a->layout == XVIT_GEMM_NT) launch_big<false, false, -1>(p, gz, s);
     else if (a->layout == XVIT_GEMM_NN) launch_big<false, true, -1>(p, gz, s);
     else launch_big<true, true, -1>(p, gz, s);
@@ -1447,4 +1626,5 @@ extern "C" int xvit_patch_embed_dgrad(const void* dx, int64_t lddx, const void* 
 
 #ifdef XVIT_GEMM_CLOCK_PROBE
 extern "C" int xvit_dbg_read_clk(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(xvit::xvit_dbg_clk), (size_t)n * 16); }
+extern "C" int xvit_dbg_read_seg(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(xvit::xvit_dbg_seg), (size_t)n * 24); }
 #endif

@@ -40,7 +40,10 @@ const char* xvit_last_error_string(void);
  *   "gemm_group"     0 = automatic, n > 0 = column tiles per super-column of the 256x256 kernel's tile walk
  *   "gemm_epilogue"  0 = automatic, 1 = always the 8-byte-per-lane epilogue (bf16 outputs normally use 16 bytes per lane)
  *   "gemm_res_prefetch"  0 = the 256x256 kernel's plain bias + residual epilogue loads its fp32 residual one 16-row region ahead of
- *                    the stores, 1 = inside the epilogue body, like every other epilogue */
+ *                    the stores, 1 = inside the epilogue body, like every other epilogue
+ *   "gemm_persistent"  the 256x256 kernel's tile loop (NT / NN, no split-K or batch, 16-byte-per-lane bf16 epilogue): 0 = automatic
+ *                    (one workgroup per CU walks the tiles where that was measured faster), 1 = always one workgroup per tile,
+ *                    n >= 2 = the loop wherever it exists, on at most n workgroups */
 int xvit_set_option(const char* name, int value);
 /* Dropout under HIP-graph capture.  The reference seeds its dropout masks from the host RNG at every call (nn.Dropout,
  * model_cross.py:27,47,95,101,170; it trains with p = 0.1 .. 0.25, main_mist.py:71-77); a captured step would freeze the seeds passed

@@ -9,6 +9,8 @@
    with the probe build — the shader cycles each workgroup took and the clock it ran at (clock64 / wall_clock64).
 2. The same 256 tiles all reading ONE A panel and ONE B panel (stride-0 batch): no HBM / fabric traffic to speak of.
 3. The model's Linear shapes at configs[1] (M = 54016): clock and cycles per tile, split into the K loop and the rest.
+4. The K = 768 shapes at M = 64638 with the probe build's stamps: prologue, K loop and epilogue of a tile (XVIT_PROBE_ONLY=4
+   runs this section alone).
 tools/mfma_clock_probe.hip is the companion: the bare MFMA loop from registers."""
 import ctypes
 import os
@@ -47,6 +49,51 @@ def timed(fn, reps):
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / reps * 1e3
 
+
+def segments(n):
+    """Per-workgroup medians of the first tile's segments in shader cycles: (entry -> first barrier passed, K loop, epilogue)."""
+    n = min(n, 4096)
+    buf = (ctypes.c_longlong * (3 * n))()
+    lib.xvit_dbg_read_seg(buf, n)
+    rows = [(buf[3 * i], buf[3 * i + 1] - buf[3 * i], buf[3 * i + 2] - buf[3 * i + 1]) for i in range(n) if buf[3 * i] > 0]
+    return [sorted(r[j] for r in rows)[len(rows) // 2] for j in range(3)]
+
+
+def section4():
+    """4. Where a tile's time goes at M = 64638 (batch 126), K = 768: the exposed prologue (kernel entry to the first barrier
+    passed: tile arithmetic, loader set-up, one LDS-DMA round trip), the K loop, and the epilogue up to its last store issued."""
+    M, d, f = 64638, 768, 3072
+    print(f"--- 4. segments of one tile at M = {M} (medians over workgroups; gemm_persistent = 1: one tile per workgroup)")
+    ops.set_option("gemm_persistent", 1)
+
+    def bf(*s):
+        return torch.randn(*s, device=dev).bfloat16()
+    shapes = []
+    A = bf(M, d)
+    C = torch.empty(M, 3 * d, dtype=torch.bfloat16, device=dev); W = bf(3 * d, d)
+    shapes.append(("qkv forward (NT)", 3 * d, lambda A=A, W=W, C=C: ops.gemm(ops.NT, A, W, C)))
+    C1 = torch.empty(M, f, dtype=torch.bfloat16, device=dev); z = torch.empty_like(C1); W1 = bf(f, d); b1 = torch.randn(f, device=dev)
+    shapes.append(("FFN1 forward (NT, GELU, a + gelu')", f, lambda: ops.gemm(ops.NT, A, W1, C1, bias=b1, aux=z, act=ops.ACT_GELU, aux_mode=1)))
+    W2 = bf(d, f); cs = torch.zeros(f, device=dev)
+    shapes.append(("FFN2 dgrad (NN, x gelu', colsum)", f, lambda: ops.gemm(ops.NN, A, W2, C1, aux=z, act=ops.ACT_DGELU, aux_mode=1, colsum=cs)))
+    C3 = torch.empty(M, d, dtype=torch.float32, device=dev); res = torch.randn(M, d, device=dev); W3 = bf(d, d); b3 = torch.randn(d, device=dev)
+    shapes.append(("out-proj forward (NT, bias + res, fp32)", d, lambda: ops.gemm(ops.NT, A, W3, C3, bias=b3, residual=res)))
+    for name, N, fn in shapes:
+        us = timed(fn, 10)
+        tiles = ((M + 255) // 256) * (N // 256)
+        line = f"{name:40s} N={N:4d}: {us:7.1f} us, {tiles} tiles"
+        if HAVE_CLK:
+            mhz, cyc, _, _ = clocks(tiles)
+            pro, loop, epi = segments(tiles)
+            tot = pro + loop + epi
+            line += f" | {mhz:5.0f} MHz | prologue {pro:6d} cyc {pro / mhz:5.2f} us ({100.0 * pro / tot:4.1f} %) | K loop {loop:6d} cyc {loop / mhz:5.2f} us | epilogue {epi:6d} cyc {epi / mhz:5.2f} us ({100.0 * epi / tot:4.1f} %) | tile {tot:6d} cyc (lifetime {cyc:7.0f})"
+        print(line, flush=True)
+    ops.set_option("gemm_persistent", 0)
+
+
+if os.environ.get("XVIT_PROBE_ONLY") == "4":
+    section4()
+    sys.exit(0)
 
 QUICK = os.environ.get("XVIT_PROBE_QUICK") == "1"      # section 1, NT, 16 and 256 tiles only (energy decomposition builds)
 ops.set_option("gemm_tile", 2)
@@ -101,3 +148,5 @@ for (N, Kk, act, name) in ((2304, 768, ops.ACT_NONE, "qkv"), (768, 768, ops.ACT_
         ks = Kk // 64
         line += f" | {mhz:5.0f} MHz, {cyc:7.0f} cycles per tile ({cmin} .. {cmax}); {ks} K-steps x 2500 = {ks * 2500}, so {cyc - ks * 2500:6.0f} outside the K loop"
     print(line, flush=True)
+
+section4()

@@ -3,7 +3,8 @@
 wgrad), timed per tile kernel, variants interleaved in one process (HIP events, random bf16 operands).  Prints the time,
 the algorithmic TFLOP/s and the algorithmic HBM GB/s (compulsory operand + epilogue bytes) of every case.
 
-    python tools/gemm_model_bench.py [batch] [variant ...]     variants: auto narrow tile128 tile256 auxz g1..g12
+    python tools/gemm_model_bench.py [batch] [variant ...]     variants: auto narrow tile128 tile256 auxz g1..g12 oneper
+"oneper" = xvit_set_option("gemm_persistent", 1): one workgroup per 256x256 tile everywhere (auto: the tile loop where it is chosen).
 """
 import os
 import sys
@@ -77,7 +78,12 @@ def cases():
     return out
 
 
-VARIANTS = {"auto": (("gemm_tile", 0), ("gemm_epilogue", 0), ("gemm_group", 0)), "auxz": (("gemm_tile", 0), ("gemm_epilogue", 0), ("gemm_group", 0)), "narrow": (("gemm_tile", 0), ("gemm_epilogue", 1)), "tile128": (("gemm_tile", 1), ("gemm_epilogue", 0)), "tile256": (("gemm_tile", 2), ("gemm_epilogue", 0)),
+try:                                   # a library from before the tile loop (XVIT_LIB=...: across-build runs) has no such option
+    ops.set_option("gemm_persistent", 0)
+    LOOP = (("gemm_persistent", 0),)
+except RuntimeError:
+    LOOP = ()
+VARIANTS = {"auto": (("gemm_tile", 0), ("gemm_epilogue", 0), ("gemm_group", 0)) + LOOP, "oneper": (("gemm_tile", 0), ("gemm_epilogue", 0), ("gemm_group", 0), ("gemm_persistent", 1)), "auxz": (("gemm_tile", 0), ("gemm_epilogue", 0), ("gemm_group", 0)), "narrow": (("gemm_tile", 0), ("gemm_epilogue", 1)), "tile128": (("gemm_tile", 1), ("gemm_epilogue", 0)), "tile256": (("gemm_tile", 2), ("gemm_epilogue", 0)),
             **{f"g{n}": (("gemm_tile", 0), ("gemm_epilogue", 0), ("gemm_group", n)) for n in (1, 2, 3, 4, 6, 12)}}
 
 
@@ -108,6 +114,8 @@ def main():
         print(f"{label:22s} x{w}  ideal {ideal:6.0f} us | " + " | ".join(f"{v}: {best[v]:7.1f} us {flops / best[v] / 1e6:6.0f} TF {byt / best[v] / 1e3:5.0f} GB/s" for v in names), flush=True)
     print("per-step GEMM time (weighted by launches per step, ms): " + "  ".join(f"{v}: {total[v] / 1e3:.2f}" for v in names))
     ops.set_option("gemm_tile", 0); ops.set_option("gemm_epilogue", 0); ops.set_option("gemm_group", 0)
+    for k_, v_ in LOOP:
+        ops.set_option(k_, v_)
 
 
 if __name__ == "__main__":
