@@ -1,5 +1,6 @@
 // Patch dropout (PatchDropout, Liu et al. 2023): train on a random subset of K of the P patch tokens of every sequence, plus CLS.
 //   xvit_token_select_draw   which patches each sequence keeps (counter hash, capturable, no host read-back)
+//   xvit_token_select_ranked the same, ranked by per-patch foreground counts (token_occupancy.hip): tissue first, or the most occupied
 //   xvit_patchify_select     the stored patch matrix of the kept rows only
 //   xvit_embed_select_fwd    + pos of the KEPT patch, and the CLS row
 //   xvit_embed_select_bwd    dpos / dcls through the selection, in a fixed order
@@ -11,32 +12,66 @@ namespace xvit {
 constexpr int kDrawBlock = 1024;
 static_assert(XVIT_TOKEN_SELECT_MAX_P == 8 * kDrawBlock, "the draw kernel is instantiated for up to 8 patches per thread");
 
+// How a sequence's patches are ordered: by the counter hash alone (xvit_token_select_draw), or by occupancy (xvit_token_select_ranked):
+// foreground before background and the hash inside each class, or the most occupied first.
+enum { kRankHash = -1, kRankRandom = XVIT_TOKEN_RANK_RANDOM, kRankTop = XVIT_TOKEN_RANK_TOP };
+
 // One workgroup per sequence.  The keys of the sequence sit in LDS; thread t owns the patches t, t + 1024, ... and ranks them in ONE
 // sweep over the LDS array (every lane reads the same address: a broadcast) by counting the (key, p) pairs below its own.  The pairs are
 // distinct, so the ranks are a permutation and "kept" is rank < K.  The ascending position of a kept patch is the number of kept patches
 // in front of it: a ballot prefix inside each wave, the waves' totals through LDS, 1024 patches per round.  PER: patches a thread
-// ranks (P <= PER * 1024).
-template <int PER>
-__global__ __launch_bounds__(kDrawBlock) void token_select_draw_kernel(int* __restrict__ keep_idx, int* __restrict__ slot, int B, int P, int K, int shared,
-                                                                        uint64_t seed, const uint64_t* __restrict__ epoch) {
+// ranks (P <= PER * 1024).  RANK: the key is the hash, or ~count for kRankTop (a larger count ranks first, ties to the smaller p);
+// kRankRandom puts one class bit per patch (1: background) from a bit mask in LDS above the hash.  The count of a patch is occ[s, p],
+// or with `shared` the sum over the S / B modalities of its sample, saturated at 2^32 - 1.
+template <int PER, int RANK>
+__global__ __launch_bounds__(kDrawBlock) void token_select_kernel(const int* __restrict__ occ, int* __restrict__ keep_idx, int* __restrict__ slot, int* __restrict__ n_fg,
+                                                                   int S, int B, int P, int K, int shared, int min_count, uint64_t seed,
+                                                                   const uint64_t* __restrict__ epoch) {
   __shared__ uint32_t keys[PER * kDrawBlock];
+  __shared__ uint64_t background[RANK == kRankRandom ? PER * kDrawBlock / kWave : 1];   // bit p % 64 of word p / 64
   __shared__ int wave_tot[kDrawBlock / kWave];
   const int s = blockIdx.x, tid = threadIdx.x;
-  const uint64_t sd = drop_seed_at(seed, epoch);
   const uint64_t u = shared ? (uint64_t)(s % B) : (uint64_t)s;
-  for (int p = tid; p < P; p += kDrawBlock) keys[p] = hash32(sd, u * (uint64_t)P + (uint64_t)p);
+  if constexpr (RANK != kRankTop) {
+    const uint64_t sd = drop_seed_at(seed, epoch);
+    for (int p = tid; p < P; p += kDrawBlock) keys[p] = hash32(sd, u * (uint64_t)P + (uint64_t)p);
+  }
+  if constexpr (RANK != kRankHash) {
+    const int first = shared ? s % B : s, last = shared ? S : s + 1;   // the sequences whose counts add up, B apart
+    int total_fg = 0;
+    for (int p0 = 0; p0 < P; p0 += kDrawBlock) {     // whole waves: the ballot below needs every lane
+      const int p = p0 + tid;
+      uint64_t c = 0;
+      if (p < P)
+        for (int q = first; q < last; q += B) c += (uint32_t)occ[(int64_t)q * P + p];
+      const bool fg = p < P && c >= (uint64_t)min_count;
+      if constexpr (RANK == kRankTop) {
+        if (p < P) keys[p] = ~(c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c);
+      } else {
+        const uint64_t vote = __ballot(!fg);
+        if ((tid & (kWave - 1)) == 0) background[p / kWave] = vote;
+      }
+      if (n_fg) compact_round<kDrawBlock>(fg, wave_tot, total_fg);   // uniform: n_fg is an argument
+    }
+    if (n_fg && tid == 0) n_fg[s] = total_fg;
+  }
   __syncthreads();
 
+  // (key, p) as one integer: ties on the key go to the smaller p
+  auto pair = [&](int p) -> uint64_t {
+    if constexpr (RANK == kRankRandom) return ((background[p / kWave] >> (p % kWave)) & 1ull) << 63 | (uint64_t)keys[p] << 31 | (uint32_t)p;
+    else return ((uint64_t)keys[p] << 32) | (uint32_t)p;
+  };
   uint64_t mine[PER];
   int below[PER];
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int p = tid + i * kDrawBlock;
-    mine[i] = p < P ? ((uint64_t)keys[p] << 32) | (uint32_t)p : 0;   // (key, p) as one integer: ties on the key go to the smaller p; 0: nothing is below
+    mine[i] = p < P ? pair(p) : 0;   // 0: nothing is below
     below[i] = 0;
   }
   for (int q = 0; q < P; ++q) {
-    const uint64_t other = ((uint64_t)keys[q] << 32) | (uint32_t)q;
+    const uint64_t other = pair(q);
 #pragma unroll
     for (int i = 0; i < PER; ++i)
       below[i] += other < mine[i] ? 1 : 0;
@@ -119,21 +154,41 @@ __global__ void embed_select_bwd_kernel(const float* __restrict__ dx, const int*
 
 using namespace xvit;
 
-extern "C" int xvit_token_select_draw(int32_t* keep_idx, int32_t* slot, int S, int B, int P, int K, int shared, uint64_t seed, xvit_stream_t stream) {
-  XVIT_REQUIRE(S > 0 && B > 0 && P > 0, "xvit_token_select_draw: bad sizes (S=%d B=%d P=%d)", S, B, P);
-  XVIT_REQUIRE(K >= 1, "xvit_token_select_draw: K=%d, at least one patch must be kept", K);
-  XVIT_REQUIRE(K <= P, "xvit_token_select_draw: K=%d exceeds the P=%d patches of a sequence", K, P);
-  XVIT_REQUIRE(P <= XVIT_TOKEN_SELECT_MAX_P, "xvit_token_select_draw: P=%d too long (the keys of a sequence sit in LDS: P <= %d)", P, XVIT_TOKEN_SELECT_MAX_P);
-  XVIT_REQUIRE(keep_idx && slot, "xvit_token_select_draw: null pointer");
-  auto launch = [&](auto per) {
-    hipLaunchKernelGGL((token_select_draw_kernel<decltype(per)::value>), dim3(S), dim3(kDrawBlock), 0, (hipStream_t)stream, keep_idx, slot, B, P, K, shared ? 1 : 0, seed,
-                       drop_epoch_ptr());
+// Both draws: what they refuse alike, under the caller's name, and the launch of the instantiation for P and the ranking.
+static int token_select(const char* who, int rank, const int32_t* occ, int32_t* keep_idx, int32_t* slot, int32_t* n_fg, int S, int B, int P, int K, int shared,
+                        int min_count, uint64_t seed, xvit_stream_t stream) {
+  XVIT_REQUIRE(S > 0 && B > 0 && P > 0, "%s: bad sizes (S=%d B=%d P=%d)", who, S, B, P);
+  XVIT_REQUIRE(K >= 1, "%s: K=%d, at least one patch must be kept", who, K);
+  XVIT_REQUIRE(K <= P, "%s: K=%d exceeds the P=%d patches of a sequence", who, K, P);
+  XVIT_REQUIRE(P <= XVIT_TOKEN_SELECT_MAX_P, "%s: P=%d too long (the keys of a sequence sit in LDS: P <= %d)", who, P, XVIT_TOKEN_SELECT_MAX_P);
+  XVIT_REQUIRE(keep_idx && slot, "%s: null pointer", who);
+  auto launch = [&](auto per, auto r) {
+    hipLaunchKernelGGL((token_select_kernel<decltype(per)::value, decltype(r)::value>), dim3(S), dim3(kDrawBlock), 0, (hipStream_t)stream, occ, keep_idx, slot, n_fg, S, B, P,
+                       K, shared ? 1 : 0, min_count, seed, drop_epoch_ptr());
   };
-  if (P <= kDrawBlock) launch(Int<1>{});
-  else if (P <= 2 * kDrawBlock) launch(Int<2>{});
-  else if (P <= 4 * kDrawBlock) launch(Int<4>{});
-  else launch(Int<8>{});
-  return check_launch("xvit_token_select_draw");
+  auto by_length = [&](auto r) {
+    if (P <= kDrawBlock) launch(Int<1>{}, r);
+    else if (P <= 2 * kDrawBlock) launch(Int<2>{}, r);
+    else if (P <= 4 * kDrawBlock) launch(Int<4>{}, r);
+    else launch(Int<8>{}, r);
+  };
+  if (rank == kRankHash) by_length(Int<kRankHash>{});
+  else if (rank == kRankRandom) by_length(Int<kRankRandom>{});
+  else by_length(Int<kRankTop>{});
+  return check_launch(who);
+}
+
+extern "C" int xvit_token_select_draw(int32_t* keep_idx, int32_t* slot, int S, int B, int P, int K, int shared, uint64_t seed, xvit_stream_t stream) {
+  return token_select("xvit_token_select_draw", kRankHash, nullptr, keep_idx, slot, nullptr, S, B, P, K, shared, 0, seed, stream);
+}
+
+extern "C" int xvit_token_select_ranked(const int32_t* occ, int32_t* keep_idx, int32_t* slot, int32_t* n_fg, int S, int B, int P, int K, int shared, int mode,
+                                        int min_count, uint64_t seed, xvit_stream_t stream) {
+  XVIT_REQUIRE(occ, "xvit_token_select_ranked: null occupancy");
+  XVIT_REQUIRE(mode == XVIT_TOKEN_RANK_RANDOM || mode == XVIT_TOKEN_RANK_TOP, "xvit_token_select_ranked: unknown mode %d", mode);
+  XVIT_REQUIRE(min_count >= 0, "xvit_token_select_ranked: min_count=%d must be >= 0", min_count);
+  XVIT_REQUIRE(!shared || (B > 0 && S % B == 0), "xvit_token_select_ranked: with shared, S=%d must be a multiple of B=%d", S, B);
+  return token_select("xvit_token_select_ranked", mode, occ, keep_idx, slot, n_fg, S, B, P, K, shared, min_count, seed, stream);
 }
 
 extern "C" int xvit_patchify_select(const void* img, int img_dtype, void* out_bf16, const int32_t* keep_idx, int B, int M, int D, int H, int W, int dp, int hp,

@@ -11,9 +11,11 @@ own nn.Module signatures (vsahni3/cross-attention-ViT: model_cross.py, model.py)
     xvit.augment.ContrastAugment()(img)              # random Gaussian blur, bias field and gamma on the augmented volumes, one fused kernel
     xvit.MaskedVolumeModel(config)                   # masked-volume (MAE) pretraining of a ModelCross encoder
     config.mixup_alpha / config.cutmix_alpha         # Mixup / CutMix with a soft-target loss in ModelCross.train() (fine-tuning)
+    config.patch_select = "foreground"               # patch dropout ranked by per-patch foreground; eval_patch_dropout shortens eval() too
+    xvit.token_occupancy(img, patch_size)            # the per-patch foreground counts that ranking reads
 """
 from . import _lib  # noqa: F401
-from .functional import invalidate_shadows  # noqa: F401
+from .functional import invalidate_shadows, token_occupancy  # noqa: F401   (token_occupancy: per-patch foreground counts, stand-alone)
 from .model import Block, Encoder, Mlp, MultiHeadAttention  # noqa: F401
 from .modelv3 import ModelVIT, Transformer  # noqa: F401
 from .model_cross import (Attention, CrossAttention, CrossAttentionBlock, FeedForward, ModelCross,  # noqa: F401

@@ -85,7 +85,8 @@ CROP_BOXES_ONLY, CROP_CENTER, CROP_FIT = 0, 1, 2       # XVIT_CROP_*
 AUG_CROP_SCALE = 31                                    # XVIT_AUG_CROP_SCALE
 MAE_MAX_PD = 8192                                      # XVIT_MAE_MAX_PD: the largest patch (voxels) xvit_mae_loss_fwd holds in LDS
 TOKEN_SELECT_MAX_P = 8192                              # XVIT_TOKEN_SELECT_MAX_P: the longest sequence xvit_token_select_draw ranks in LDS
-EPOCH_MAX_C, EPOCH_MAX_B = 64, 8192                    # XVIT_EPOCH_MAX_C, XVIT_EPOCH_MAX_B: the limits of xvit_epoch_metrics_update
+TOKEN_RANK_RANDOM, TOKEN_RANK_TOP = 0, 1               # XVIT_TOKEN_RANK_*: the modes of xvit_token_select_ranked
+EPOCH_MAX_C, EPOCH_MAX_B = 64, 8192                   # XVIT_EPOCH_MAX_C, XVIT_EPOCH_MAX_B: the limits of xvit_epoch_metrics_update
 EPOCH_STATE_HEAD = 8                                   # XVIT_EPOCH_STATE_HEAD: int64 counters in front of the C x C confusion
 EPOCH_STORED, EPOCH_SEEN, EPOCH_STEPS, EPOCH_IGNORED, EPOCH_NONFINITE, EPOCH_OVERFLOW = 0, 1, 2, 3, 4, 5   # XVIT_EPOCH_*: the counters
 EPOCH_RANK_PASS = 1024                                 # XVIT_EPOCH_RANK_PASS: sorted elements per pass of xvit_epoch_rank_stats' walk
@@ -141,6 +142,8 @@ SIGNATURES = {
     "xvit_embed_select_fwd": [vp, vp, vp, vp, i32, i32, i32, vp],
     "xvit_embed_select_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "xvit_token_select_complement": [vp, vp, vp, i32, i32, i32, vp],
+    "xvit_patch_occupancy": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "xvit_token_select_ranked": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, u64, vp],
     "xvit_mae_unshuffle_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "xvit_mae_unshuffle_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "xvit_token_rows_gather": [vp, vp, vp, i32, i32, i32, i32, vp],

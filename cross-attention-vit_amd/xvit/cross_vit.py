@@ -11,6 +11,7 @@ parameter containers with the reference's names — their torch forward is never
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -362,6 +363,26 @@ class ModelCross(EpochStatsMixin, _Base):
         # int32 [M, B, K]: the patch indices the last forward kept (None: it kept them all).  The tensor a capture leaves here is the
         # graph's own and follows its replays; any later forward call replaces the attribute, not that tensor
         self.last_token_keep = None
+        # foreground-ranked selection (off unless the config says patch_select="foreground"): the draw keeps patches that hold foreground
+        # before the others, by per-patch counts of the voxels above a threshold on the tensor the model receives.  train(): a random
+        # subset of the foreground patches; eval() with eval_patch_dropout > 0: the most occupied patches, without randomness
+        self.patch_select = getattr(config, "patch_select", "random")
+        self.patch_foreground_above = float(getattr(config, "patch_foreground_above", 0.0))
+        self.patch_foreground_min_fraction = float(getattr(config, "patch_foreground_min_fraction", 0.05))
+        self.eval_patch_dropout = float(getattr(config, "eval_patch_dropout", 0.0))
+        if self.patch_select not in ("random", "foreground"):
+            raise ValueError(f"patch_select must be 'random' or 'foreground', got {self.patch_select!r}")
+        if not 0.0 <= self.eval_patch_dropout < 1.0:
+            raise ValueError(f"eval_patch_dropout must be in [0, 1), got {self.eval_patch_dropout}")
+        if self.eval_patch_dropout > 0.0 and self.patch_select == "random":
+            raise ValueError("eval_patch_dropout > 0 needs patch_select='foreground': a random subset at validation time is not offered")
+        if not 0.0 <= self.patch_foreground_min_fraction <= 1.0:
+            raise ValueError(f"patch_foreground_min_fraction must be in [0, 1], got {self.patch_foreground_min_fraction}")
+        if not math.isfinite(self.patch_foreground_above):
+            raise ValueError(f"patch_foreground_above must be finite, got {self.patch_foreground_above}")
+        # int32 [M, B, P] and [M, B]: the per-patch foreground counts the last forward ranked by and how many patches of each sequence
+        # were foreground (None: it ranked nothing); a capture's tensors are the graph's own, as above
+        self.last_token_occupancy = self.last_token_foreground = None
         # Mixup / CutMix (not in the reference; off unless the config carries a positive alpha): in train() every sample's volumes and label
         # are mixed with a partner's, the loss takes the two-label target; eval() mixes nothing
         self.mixup_alpha, self.cutmix_alpha = float(getattr(config, "mixup_alpha", 0.0)), float(getattr(config, "cutmix_alpha", 0.0))
@@ -402,6 +423,23 @@ class ModelCross(EpochStatsMixin, _Base):
         slot = torch.empty(M * B, P, dtype=torch.int32, device=img.device)
         return XF.ops.token_select_draw(keep_idx, slot, B, self.patch_dropout_shared if shared is None else bool(shared), XF.drop_seeds(1)[0])
 
+    def _rank_token_keep(self, img, rate, seed):
+        """Foreground-ranked selection: the per-patch foreground counts of img, then the draw ranked by them -> (keep_idx, slot) as
+        _draw_token_keep returns them.  train(): foreground patches first, in the plain draw's order under `seed` inside each class;
+        eval(): the K most occupied patches, no seed.  Two launches, no host read-back; every tensor is allocated by the forward, so a
+        capture owns its own.  Leaves the counts and the number of foreground patches in last_token_occupancy / last_token_foreground."""
+        from ._lib import TOKEN_RANK_RANDOM, TOKEN_RANK_TOP
+        B, M, P = img.shape[0], self.num_modalities, self.pos_embedding.shape[1] - 1
+        K = XF.patch_keep_count(P, rate)
+        occ = XF.ops.patch_occupancy(img.contiguous(), self.patch_size, self.patch_foreground_above)
+        keep_idx = torch.empty(M * B, K, dtype=torch.int32, device=img.device)
+        slot = torch.empty(M * B, P, dtype=torch.int32, device=img.device)
+        n_fg = torch.empty(M * B, dtype=torch.int32, device=img.device)
+        min_count = XF.foreground_min_count(math.prod(self.patch_size), self.patch_foreground_min_fraction, M if self.patch_dropout_shared else 1)
+        XF.ops.token_select_ranked(occ, keep_idx, slot, B, self.patch_dropout_shared, TOKEN_RANK_RANDOM if self.training else TOKEN_RANK_TOP, min_count, seed, n_fg)
+        self.last_token_occupancy, self.last_token_foreground = occ.view(M, B, P), n_fg.view(M, B)
+        return keep_idx, slot
+
     def _draw_mix(self, img):
         """Mixup / CutMix: draw, on the current stream and without a host read-back, one record per sample -> table fp32 [B, 16]
         (include/xvit.h).  Allocated by every forward, like keep_idx: under capture it lives in the graph's own pool and every replay
@@ -418,6 +456,7 @@ class ModelCross(EpochStatsMixin, _Base):
         if img.shape[1] != self.num_modalities:
             raise ValueError(f"expected {self.num_modalities} modalities, got {img.shape[1]}")
         self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
+        self.last_token_occupancy = self.last_token_foreground = None             # the caller's keep: nothing is ranked here
         x = list(XF.PatchEmbedFn.apply(img, self.patch_to_embedding.weight, self.patch_to_embedding.bias,
                                        self.cls_token, self.pos_embedding, self.patch_size, _p(self, self.dropout), False, keep))
         for k, blk in enumerate(self.transformer):
@@ -435,12 +474,18 @@ class ModelCross(EpochStatsMixin, _Base):
             raise ValueError(f"expected {self.num_modalities} modalities, got {img.shape[1]}")
         if img.is_cuda and torch.is_grad_enabled():
             XF.arena_begin(img.device)                   # the backward's small zeroed vectors: one fill per step (functional._zeros)
-        keep = self._draw_token_keep(img) if self.training and self.patch_dropout > 0.0 else None
-        self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
+        drop = self.patch_dropout if self.training else self.eval_patch_dropout
+        ranked = drop > 0.0 and self.patch_select == "foreground"
+        keep = self._draw_token_keep(img) if drop > 0.0 and not ranked else None
+        token_seed = XF.drop_seeds(1)[0] if ranked and self.training else 0            # eval() ranks without a seed and leaves the seed stream alone
         mix = self._draw_mix(img) if self.training and (self.mixup_alpha > 0.0 or self.cutmix_alpha > 0.0) else None   # its seed: after the token draw's
         self.last_mix = mix
         if mix is not None:
             img = XF.mix_volumes(img, mix)
+        self.last_token_occupancy = self.last_token_foreground = None
+        if ranked:
+            keep = self._rank_token_keep(img, drop, token_seed)                          # behind the mix: it counts the volume the embedding reads
+        self.last_token_keep = None if keep is None else keep[0].view(self.num_modalities, img.shape[0], -1)
         tokens = XF.PatchEmbedFn.apply(img, self.patch_to_embedding.weight, self.patch_to_embedding.bias,
                                        self.cls_token, self.pos_embedding, self.patch_size, _p(self, self.dropout), False, keep)
         x = list(tokens)

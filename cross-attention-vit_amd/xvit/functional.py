@@ -780,6 +780,24 @@ def patch_keep_count(P, p):
     return K - K % 64 if K >= 64 else K
 
 
+def token_occupancy(img, patch_size, above=0.0):
+    """How much foreground every patch holds: img [B, M, 1, D, H, W] (fp32 | bf16, on the GPU) -> int32 [M, B, P], the voxels of each
+    patch whose value is > above (ops.patch_occupancy: strict compare, NaN never counts; patch order of the token sequence).  This is
+    what ModelCross ranks by under patch_select="foreground", on the tensor the model receives."""
+    if img.dim() != 6 or img.shape[2] != 1:
+        raise ValueError(f"token_occupancy: expected [B, M, 1, D, H, W], got {tuple(img.shape)}")
+    if not math.isfinite(float(above)):
+        raise ValueError(f"token_occupancy: the threshold must be finite, got {above}")
+    return ops.patch_occupancy(img.contiguous(), tuple(int(p) for p in patch_size), float(above)).view(img.shape[1], img.shape[0], -1)
+
+
+def foreground_min_count(pd, fraction, modalities=1):
+    """The least count that makes a patch foreground: max(1, ceil(fraction * pd * modalities)), modalities = M where the counts of a
+    sample's modalities are summed (patch_dropout_shared), else 1.  Exact for every fraction that is written with a few decimals: the
+    product is rounded to the nearest 1e-9 before the ceiling."""
+    return max(1, int(math.ceil(round(float(fraction) * int(pd) * int(modalities), 9))))
+
+
 class PatchEmbedFn(Function):
     """img [B, M, 1, D, H, W] -> tokens fp32 [M, B, N, d] = cat(cls, patches W^T + b) + pos.
     keep = (keep_idx int32 [M*B, K], slot int32 [M*B, P]) (patch dropout, ops.token_select_draw): the tokens of the kept patches only,

@@ -148,6 +148,9 @@ def _check(model, img, who):
         raise TypeError(f"{who}: need a ModelCross or a ModelVIT, got {type(model).__name__}")
     if model.training:
         raise RuntimeError(f"{who}: the model is in training mode (dropout would make the maps random); call model.eval() first")
+    if getattr(model, "eval_patch_dropout", 0.0) > 0.0:
+        raise RuntimeError(f"{who}: the model's eval() forward keeps a subset of the patch tokens (eval_patch_dropout = {model.eval_patch_dropout}) and the "
+                           "maps are defined on the full grid; set model.eval_patch_dropout = 0 for the maps")
     if os.environ.get("XVIT_ATTN_FP8", "0") == "1":
         raise RuntimeError(f"{who}: the maps are defined on the bf16 attention forward; unset XVIT_ATTN_FP8")
     if not (img.is_cuda and model.pos_embedding.is_cuda):

@@ -643,6 +643,36 @@ def token_select_draw(keep_idx, slot, B, shared, seed):
     return keep_idx, slot
 
 
+def patch_occupancy(img, patch, above, out=None):
+    """img [B, M, 1, D, H, W] fp32|bf16 contiguous -> int32 [M*B, P]: the voxels of every patch whose value is > above
+    (xvit_patch_occupancy; NaN never counts, sequence s = m B + b, patch order of patchify)."""
+    assert img.dim() == 6 and img.shape[2] == 1 and img.is_contiguous()
+    B, M, _, D, H, W = img.shape
+    dp, hp, wp = patch
+    P = _patch_counts(img.shape, patch)[0]
+    out = out if out is not None else torch.empty(M * B, P, dtype=torch.int32, device=img.device)
+    _i32c(out, (M * B, P), "out")
+    _run("patch_occupancy", img.numel() * float(img.element_size()) + M * B * P * 4.0, "byte",
+         lambda: _lib.load().xvit_patch_occupancy(_ptr(img), _dt(img), _ptr(out), B, M, D, H, W, dp, hp, wp, float(above), _stream()), "xvit_patch_occupancy")
+    return out
+
+
+def token_select_ranked(occ, keep_idx, slot, B, shared, mode, min_count, seed, n_fg=None):
+    """The draw ranked by occupancy (xvit_token_select_ranked): occ int32 [S, P] (patch_occupancy) -> keep_idx int32 [S, K] and slot
+    int32 [S, P] as token_select_draw fills them.  mode _lib.TOKEN_RANK_RANDOM: patches with at least min_count voxels (summed over the
+    modalities of a sample with `shared`) first, the draw's own order inside each class; _lib.TOKEN_RANK_TOP: the K most occupied,
+    without seed or epoch.  n_fg int32 [S] (optional) receives the number of foreground patches of every sequence."""
+    S, K = keep_idx.shape
+    P = slot.shape[1]
+    _i32c(occ, (S, P), "occ"), _i32c(keep_idx, (S, K), "keep_idx"), _i32c(slot, (S, P), "slot")
+    if n_fg is not None:
+        _i32c(n_fg, (S,), "n_fg")
+    _run("token_select_ranked", float(S) * (2 * P + K) * 4, "byte",
+         lambda: _lib.load().xvit_token_select_ranked(_ptr(occ), _ptr(keep_idx), _ptr(slot), _ptr(n_fg), S, int(B), P, K, int(bool(shared)), int(mode),
+                                                      int(min_count), int(seed), _stream()), "xvit_token_select_ranked")
+    return keep_idx, slot
+
+
 def patchify_select(img, patch, keep_idx, out=None):
     """img [B, M, 1, D, H, W] fp32|bf16 contiguous, keep_idx int32 [M*B, K] -> bf16 [M, B*(K+1), pd]: the rows of
     patchify(img, patch, pad_cls_row=True) that keep_idx names (a zero row in front of every sequence), only the kept voxels read."""

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 318 /* 0.3.18: xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 319 /* 0.3.19: xvit_patch_occupancy, xvit_token_select_ranked and XVIT_TOKEN_RANK_RANDOM / XVIT_TOKEN_RANK_TOP (foreground-ranked token selection for training and eval()); 0.3.18:xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply, xvit_volume_stats and xvit_volume_bbox only */ };
@@ -650,6 +650,36 @@ int xvit_patchify_select(const void* img, int img_dtype, void* out_bf16, const i
                          int K, xvit_stream_t stream);
 int xvit_embed_select_fwd(float* x, const float* cls, const float* pos, const int32_t* keep_idx, int S, int K, int d, xvit_stream_t stream);
 int xvit_embed_select_bwd(const float* dx, const int32_t* slot, float* dpos, float* dcls, int S, int P, int K, int d, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Foreground-ranked token selection (csrc/token_occupancy.hip, csrc/token_select.hip): the draw of patch dropout ranked by how much
+ * foreground a patch holds, so that tissue is kept before air; without randomness it also serves eval().  Integer work throughout: the
+ * results are the same bits at every run.  Nothing is read back to the host.
+ *
+ * xvit_patch_occupancy: img [B, M, 1, D, H, W] contiguous, bf16 or fp32 -> occ int32 [M * B, P]: occ[s, t] is the number of voxels of
+ * patch t of sequence s = m * B + b whose fp32 value v satisfies v > above.  The compare is strict and is xvit_volume_bbox's
+ * foreground_above rule: NaN is never counted, +inf is, -0.0 > 0.0 is false.  Patch order as above, t = (h * Wn + w) * Dn + d.  One pass
+ * in memory order, every voxel read once: 16 bytes per lane where wp % 8 == 0 and img is 16-byte aligned (xvit_patchify_select's
+ * switch), else one voxel per lane, with the same integers.  No global atomics and no workspace; every element of occ is written exactly
+ * once.  Refused: null pointers, an unknown dtype, sizes that the patch does not divide, a non-finite `above`, and P, dp*hp*wp or M * B
+ * at or beyond 2^31.
+ *
+ * xvit_token_select_ranked: occ int32 [S, P] -> keep_idx [S, K] and slot [S, P] as xvit_token_select_draw writes them.  The count of
+ * patch p of sequence s is c[p] = occ[s, p]; with `shared` (S = M * B) it is the sum of occ[m * B + b, p] over the M = S / B modalities
+ * of sample b = s mod B, saturated at 2^32 - 1, so that all modalities of a sample get the same result.  A patch is foreground when
+ * c[p] >= min_count; n_fg [S] (NULL: not wanted) receives the number of foreground patches of every sequence.
+ *   XVIT_TOKEN_RANK_RANDOM  keeps the K smallest of (not foreground, hash32(seed', u * P + p), p), with the hash, seed' and u of
+ *                           xvit_token_select_draw: foreground patches first, and inside each class the order of that draw.  Where all
+ *                           patches of a sequence fall in one class the result is xvit_token_select_draw's, bit for bit.
+ *   XVIT_TOKEN_RANK_TOP     keeps the K smallest of (-c[p], p): the most occupied patches, ties to the smaller index.  Reads neither the
+ *                           seed nor the dropout epoch.
+ * Refused: what xvit_token_select_draw refuses, a null occ, an unknown mode, min_count < 0, and `shared` with S not a multiple of B. */
+#define XVIT_TOKEN_RANK_RANDOM 0
+#define XVIT_TOKEN_RANK_TOP    1
+int xvit_patch_occupancy(const void* img, int img_dtype, int32_t* occ, int B, int M, int D, int H, int W, int dp, int hp, int wp, float above,
+                         xvit_stream_t stream);
+int xvit_token_select_ranked(const int32_t* occ, int32_t* keep_idx, int32_t* slot, int32_t* n_fg /* NULL: not wanted */, int S, int B, int P, int K, int shared,
+                             int mode, int min_count, uint64_t seed, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Masked-volume pretraining (csrc/mae.hip; MAE, He et al. 2022) on top of patch dropout: the encoder runs on the K kept patches of every

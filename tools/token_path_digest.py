@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One sha256 per case of the raw bytes the token-path kernels write (csrc/misc.hip's patchify / unpatchify / cls_row / embed_bwd,
-token_select.hip, mae.hip, and the mean + cross-entropy tail of mix.hip), on the smallest inputs that reach each of their paths.  None of
+token_select.hip, token_occupancy.hip, mae.hip, and the mean + cross-entropy tail of mix.hip), on the smallest inputs that reach each of their paths.  None of
 these kernels uses atomics, so two builds of the library compute the same thing exactly when their printouts are equal:
 
     XVIT_LIB=/path/to/other/libxvit_hip.so python tools/token_path_digest.py > other.txt
@@ -175,11 +175,35 @@ def cross_entropies():
             say(f"mean_ce_mix {name} {tag}", *ops.mean_ce_mix(logits_m, labels, table.to(DEV), eps))
 
 
+def occupancies():
+    B, M = VOL[:2]
+    for patch, dt in itertools.product(PATCHES, (F32, BF16)):
+        P = ops._patch_counts(VOL, patch)[0]
+        for off, above in itertools.product((0, 16 // dt.itemsize, 1), (0.0, -0.5)):   # the special values against 0: -0.0, the NaNs and -inf are not counted
+            say(f"patch_occupancy {short(dt)} patch {patch} offset {off} above {above}",
+                ops.patch_occupancy(rand(VOL, dt, special=True, off=off), patch, above, out=fill((M * B, P), -7, I32)))
+
+
+def rankeds():
+    for (P, K), (S, B), shared, mode, epoch in itertools.product(((1, 1), (65, 1), (1025, 512), (4096, 1024)), ((1, 1), (6, 3)), (False, True),
+                                                                 (_lib.TOKEN_RANK_RANDOM, _lib.TOKEN_RANK_TOP), (None, 5)):
+        occ = torch.randint(0, 9, (S, P), generator=GEN).to(I32).to(DEV)       # few distinct counts: ties everywhere
+        counter = None if epoch is None else fill((1,), epoch, torch.int64)
+        ops.set_dropout_epoch(counter)
+        try:
+            n_fg = fill((S,), -7, I32)
+            keep, slot = ops.token_select_ranked(occ, fill((S, K), -7, I32), fill((S, P), -7, I32), B, shared, mode, 5, 0x5EED0123, n_fg)
+        finally:
+            ops.set_dropout_epoch(None)
+        say(f"token_select_ranked P {P} K {K} S {S} B {B} shared {int(shared)} mode {mode} epoch {epoch}", keep, slot, n_fg)
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         raise SystemExit("token_path_digest: needs a GPU")
     print(f"token_path_digest: {_lib.LIB_PATH}, library version {_lib.load().xvit_version()}", file=sys.stderr)
-    for part in (patchifies, patchify_selects, draws, complements, unshuffles, losses, embeds, cross_entropies):
+    # new parts go at the end: every part draws from the one generator, so the cases in front keep their inputs
+    for part in (patchifies, patchify_selects, draws, complements, unshuffles, losses, embeds, cross_entropies, occupancies, rankeds):
         part()
     torch.cuda.synchronize()
     print(f"token_path_digest: {CASES} cases", file=sys.stderr)
