@@ -13,6 +13,7 @@ import contextvars
 import math
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -64,7 +65,6 @@ class _ShadowCache:
                 return v
         self.casts += len(params)
         if not all(isinstance(p, torch.nn.Parameter) for p in params):
-            self.casts += 0
             return self._cast(params)
         key = tuple(id(p) for p in params)
         tag = tuple((p._version, p.data_ptr()) for p in params)
@@ -231,9 +231,9 @@ def drop_seeds(n):
     return tuple(out)
 
 
-def _dp(p, seed):
-    """(p, seed) pair for the kernels, or None when dropout is off."""
-    return (p, seed) if p > 0.0 else None
+def _seeds(n, on):
+    """The n seeds of a Function's dropout sites: drawn (drop_seeds) only when dropout is on, zeros otherwise."""
+    return drop_seeds(n) if on else (0,) * n
 
 
 # ------------------------------------------------------------------------------------------
@@ -433,6 +433,10 @@ def _attn_fwd(qkv, B, N, H, scale, p=0.0, seed=0):
     return ops.attn_fwd(qkv, B, N, H, scale, dropout=(p, seed))
 
 
+# what block_forward saves for block_backward, in save_for_backward's order
+BlockSaved = namedtuple("BlockSaved", "x mu1 rs1 h1 qkv o lse x1 mu2 rs2 h2 z a")
+
+
 def block_forward(x, B, N, H, eps, scale, ln1w, ln1b, wqkv_s, bqkv, wo_s, bo, ln2w, ln2b, w1_s, b1, w2_s, b2, p_out=0.0, p_ffn=0.0, seeds=(0, 0, 0), p_attn=0.0, seed_attn=0):
     """x fp32 [B*N, d] -> (x2 fp32 [B*N, d], saved activations).  Dropout sites (reference
     model_cross.py:47,25,27 / model.py:177,114,116): after the out-projection (p_out), after GELU and
@@ -443,12 +447,36 @@ def block_forward(x, B, N, H, eps, scale, ln1w, ln1b, wqkv_s, bqkv, wo_s, bo, ln
     rec = ATTN_RECORDER.get()
     if rec is not None:
         rec.self_block(ln1w, qkv, lse, B, N, H, scale)
-    x1 = _linear(o, wo_s, bias=bo, residual=x, out_dtype=torch.float32, dropout=_dp(p_out, seeds[0]))
+    x1 = _linear(o, wo_s, bias=bo, residual=x, out_dtype=torch.float32, dropout=(p_out, seeds[0]))
     h2, mu2, rs2 = ops.layernorm_fwd(x1, ln2w, ln2b, eps)
     z = torch.empty(x.shape[0], w1_s.shape[0], dtype=torch.bfloat16, device=x.device)
-    a = _linear(h2, w1_s, bias=b1, act=ops.ACT_GELU, aux=z, dropout=_dp(p_ffn, seeds[1]), aux_mode=AUX_MODE)     # z: gelu'(pre-activation)
-    x2 = _linear(a, w2_s, bias=b2, residual=x1, out_dtype=torch.float32, dropout=_dp(p_ffn, seeds[2]))
-    return x2, (x, mu1, rs1, h1, qkv, o, lse, x1, mu2, rs2, h2, z, a)
+    a = _linear(h2, w1_s, bias=b1, act=ops.ACT_GELU, aux=z, dropout=(p_ffn, seeds[1]), aux_mode=AUX_MODE)     # z: gelu'(pre-activation)
+    x2 = _linear(a, w2_s, bias=b2, residual=x1, out_dtype=torch.float32, dropout=(p_ffn, seeds[2]))
+    return x2, BlockSaved(x, mu1, rs1, h1, qkv, o, lse, x1, mu2, rs2, h2, z, a)
+
+
+def _ffn_ln2_backward(dy, g, res_bias, x1, mu2, rs2, h2, z, a, ln2w, w1_s, w2_s, p_res, p_ffn, seeds, aux_mode, dy_b16=None):
+    """The FFN + LayerNorm-2 half of a block's and of a fusion's backward: dy fp32 [rows, d], the gradient of x1 + FFN(LN2(x1)) ->
+    (dx1 fp32, dx1b its bf16 copy, masked at the residual site, (dyb, dz)).  p_res / p_ffn: the dropout rates of the residual site in
+    front of LayerNorm-2 and of the FFN; seeds = (residual site, after GELU, FFN output); dy_b16: dy's bf16 copy where the producer supplied
+    one.  g receives w2 and w1 and accumulates b1, b2, ln2w, ln2b and g[res_bias], the bias of the Linear in front of the residual site.
+    Without dropout the two bias gradients are column sums LN2's backward produces anyway.
+    Lifetime: _wgrad may issue on the companion stream, so its operands must stay referenced until the caller's _join_wgrads.  a and h2 are
+    the caller's saved tensors; dyb, dz and dx1b, born here, are returned: the caller binds all three to locals, which live to its return."""
+    s_res, s_act, s_out = seeds
+    dyb = _masked(dy_b16 if dy_b16 is not None else ops.cast_bf16(dy), p_ffn, s_out)        # d(FFN out) = dy * mask
+    dz = _dgrad(dyb, w2_s, act=ops.ACT_DGELU, aux=z, colsum=g["b1"], dropout=(p_ffn, s_act), aux_mode=aux_mode)
+    g["w2"] = _wgrad(dyb, a, w2_s)
+    dh2 = _dgrad(dz, w1_s)
+    g["w1"] = _wgrad(dz, h2, w1_s)
+    dx1, dx1b = ops.layernorm_bwd(dh2, x1, mu2, rs2, ln2w, g["ln2w"], g["ln2b"], dres=dy, want_bf16=True,
+                                  dxsum=g[res_bias] if p_res == 0.0 else None, dressum=g["b2"] if p_ffn == 0.0 else None)
+    if p_ffn > 0.0:
+        ops.colsum(dyb, out=g["b2"], accumulate=True)
+    if p_res > 0.0:
+        dx1b = _masked(dx1b, p_res, s_res)
+        ops.colsum(dx1b, out=g[res_bias], accumulate=True)
+    return dx1, dx1b, (dyb, dz)
 
 
 def block_backward(dy, saved, B, N, H, scale, ln1w, wqkv_s, has_bqkv, wo_s, ln2w, w1_s, w2_s, p_out=0.0, p_ffn=0.0, seeds=(0, 0, 0), p_attn=0.0, seed_attn=0,
@@ -457,38 +485,60 @@ def block_backward(dy, saved, B, N, H, scale, ln1w, wqkv_s, has_bqkv, wo_s, ln2w
     LN2 backward (column sums of its dres and dx), b1 out of the GELU' dgrad epilogue.  dy_b16: the bf16 copy of dy when the producer
     supplied one (b16_of); want_dx_b16: also return dx in bf16 (g["dx_b16"]) for the block in front.  rec: the attention-map recorder
     the forward saw (ATTN_RECORDER), handed the attention output's gradient."""
-    x, mu1, rs1, h1, qkv, o, lse, x1, mu2, rs2, h2, z, a = saved
-    d, f = x.shape[1], z.shape[1]
+    s = saved
+    x, qkv, o = s.x, s.qkv, s.o
+    d, f = x.shape[1], s.z.shape[1]
     zero = _zeros(6 * d + f, x)                               # every atomically-accumulated vector of this block
     g = dict(zip(("ln2w", "ln2b", "bo", "b2", "ln1w", "ln1b"), zero[:6 * d].split(d)))
     g["b1"] = zero[6 * d:]
-    dyb = _masked(dy_b16 if dy_b16 is not None else ops.cast_bf16(dy), p_ffn, seeds[2])        # d(FFN out) = dy * mask
-    # FFN
-    dz = _dgrad(dyb, w2_s, act=ops.ACT_DGELU, aux=z, colsum=g["b1"], dropout=_dp(p_ffn, seeds[1]), aux_mode=AUX_MODE)
-    g["w2"] = _wgrad(dyb, a, w2_s)
-    dh2 = _dgrad(dz, w1_s)
-    g["w1"] = _wgrad(dz, h2, w1_s)
-    # without dropout the two bias gradients are column sums LN2's backward produces anyway
-    dx1, dx1b = ops.layernorm_bwd(dh2, x1, mu2, rs2, ln2w, g["ln2w"], g["ln2b"], dres=dy, want_bf16=True,
-                                  dxsum=g["bo"] if p_out == 0.0 else None, dressum=g["b2"] if p_ffn == 0.0 else None)
-    if p_ffn > 0.0:
-        ops.colsum(dyb, out=g["b2"], accumulate=True)
-    if p_out > 0.0:
-        dx1b = _masked(dx1b, p_out, seeds[0])
-        ops.colsum(dx1b, out=g["bo"], accumulate=True)
+    # _held: the FFN wgrads' operands, referenced until _join_wgrads below
+    dx1, dx1b, _held = _ffn_ln2_backward(dy, g, "bo", s.x1, s.mu2, s.rs2, s.h2, s.z, s.a, ln2w, w1_s, w2_s, p_out, p_ffn, seeds, AUX_MODE, dy_b16)
     # attention
     do = _dgrad(dx1b, wo_s)
     if rec is not None:
         rec.self_block_grad(ln1w, do)
     g["wo"] = _wgrad(dx1b, o, wo_s)
-    dqkv = ops.attn_bwd(qkv, o, do, lse, B, N, H, scale, dropout=(p_attn, seed_attn))
+    dqkv = ops.attn_bwd(qkv, o, do, s.lse, B, N, H, scale, dropout=(p_attn, seed_attn))
     dh1 = _dgrad(dqkv, wqkv_s)
-    g["wqkv"] = _wgrad(dqkv, h1, wqkv_s)
+    g["wqkv"] = _wgrad(dqkv, s.h1, wqkv_s)
     if has_bqkv:
         g["bqkv"] = ops.colsum(dqkv)
-    dx, g["dx_b16"] = ops.layernorm_bwd(dh1, x, mu1, rs1, ln1w, g["ln1w"], g["ln1b"], dres=dx1, want_bf16=want_dx_b16)
+    dx, g["dx_b16"] = ops.layernorm_bwd(dh1, x, s.mu1, s.rs1, ln1w, g["ln1w"], g["ln1b"], dres=dx1, want_bf16=want_dx_b16)
     _join_wgrads(x.device)
     return dx, g
+
+
+def _block_fn_forward(ctx, x, ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2, H, eps, scale, p_out, p_ffn, p_attn, branch, feeds_a_block=False):
+    """The forward of both block Functions.  wqkv: the Parameters whose rows make the fused q | k | v weight, bqkv: their biases or None.
+    branch: a block of ModelCross's branches (SelfAttentionBlockFn): its backward takes part in the bf16 hand-off, hands the attention
+    output's gradient to the recorder and parks dx / dy while a graph is captured."""
+    B, N, d = x.shape
+    ctx.branch, ctx.feeds_a_block = branch, bool(feeds_a_block)
+    sh = (SHADOWS.get(*wqkv), SHADOWS.get(wo), SHADOWS.get(w1), SHADOWS.get(w2))
+    bqkv = torch.cat(bqkv).detach() if bqkv is not None else None
+    seeds = _seeds(3, p_out > 0.0 or p_ffn > 0.0)
+    seed_attn = _seeds(1, p_attn > 0.0)[0]
+    x2, saved = block_forward(_f32c(x).reshape(B * N, d), B, N, H, eps, scale, ln1w, ln1b, sh[0], bqkv, sh[1], bo, ln2w, ln2b, sh[2], b1, sh[3], b2,
+                              p_out, p_ffn, seeds, p_attn, seed_attn)
+    ctx.drop = (p_out, p_ffn, seeds, p_attn, seed_attn)
+    ctx.meta = (B, N, H, scale, d, x.dtype)
+    ctx.save_for_backward(ln1w, ln2w, *sh, *saved)
+    rec = ATTN_RECORDER.get() if branch else None
+    if rec is not None:
+        ctx.rec = rec
+    return x2.reshape(B, N, d)
+
+
+def _block_fn_backward(ctx, dy):
+    """The backward of both block Functions -> (dx in x's dtype and shape, grads dict of block_backward)."""
+    B, N, H, scale, d, xdt = ctx.meta
+    ln1w, ln2w, wqkv_s, wo_s, w1_s, w2_s, *saved = ctx.saved_tensors
+    branch = ctx.branch
+    dx, g = block_backward(_f32c(dy).reshape(B * N, -1), BlockSaved(*saved), B, N, H, scale, ln1w, wqkv_s, not branch, wo_s, ln2w, w1_s, w2_s, *ctx.drop,
+                           dy_b16=b16_of(dy, (B * N, d)) if branch else None, want_dx_b16=ctx.feeds_a_block and B16_HANDOFF, rec=getattr(ctx, "rec", None))
+    if branch:
+        keep(dx, dy)
+    return attach_b16(dx.reshape(B, N, -1).to(xdt), g["dx_b16"]), g
 
 
 class SelfAttentionBlockFn(Function):
@@ -498,31 +548,13 @@ class SelfAttentionBlockFn(Function):
     def forward(ctx, x, ln1w, ln1b, wqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2, H, eps, p=0.0, feeds_a_block=False):
         """feeds_a_block: the gradient this node returns for x goes to another SelfAttentionBlockFn (the block in front of it in a
         branch): hand it on in bf16 as well (attach_b16)."""
-        B, N, d = x.shape
-        scale = (d // H) ** -0.5
-        ctx.feeds_a_block = bool(feeds_a_block)
-        sh = (SHADOWS.get(wqkv), SHADOWS.get(wo), SHADOWS.get(w1), SHADOWS.get(w2))
-        seeds = drop_seeds(3) if p > 0.0 else (0, 0, 0)
-        x2, saved = block_forward(_f32c(x).reshape(B * N, d), B, N, H, eps, scale, ln1w, ln1b, sh[0], None, sh[1], bo, ln2w, ln2b, sh[2], b1, sh[3], b2,
-                                  p, p, seeds)
-        ctx.drop = (p, p, seeds)
-        ctx.meta = (B, N, H, scale, x.dtype)
-        ctx.save_for_backward(ln1w, ln2w, *sh, *saved)
-        rec = ATTN_RECORDER.get()
-        if rec is not None:
-            ctx.rec = rec
-        return x2.reshape(B, N, d)
+        scale = (x.shape[2] // H) ** -0.5
+        return _block_fn_forward(ctx, x, ln1w, ln1b, (wqkv,), None, wo, bo, ln2w, ln2b, w1, b1, w2, b2, H, eps, scale, p, p, 0.0, True, feeds_a_block)
 
     @staticmethod
     def backward(ctx, dy):
-        B, N, H, scale, xdt = ctx.meta
-        ln1w, ln2w, wqkv_s, wo_s, w1_s, w2_s, *saved = ctx.saved_tensors
-        d = ln1w.shape[0]
-        dx, g = block_backward(_f32c(dy).reshape(B * N, -1), saved, B, N, H, scale, ln1w, wqkv_s, False, wo_s, ln2w, w1_s, w2_s, *ctx.drop,
-                               dy_b16=b16_of(dy, (B * N, d)), want_dx_b16=ctx.feeds_a_block and B16_HANDOFF, rec=getattr(ctx, "rec", None))
-        keep(dx, dy)
-        out = attach_b16(dx.reshape(B, N, -1).to(xdt), g["dx_b16"])
-        return (out, g["ln1w"], g["ln1b"], g["wqkv"], g["wo"], g["bo"], g["ln2w"], g["ln2b"], g["w1"], g["b1"], g["w2"], g["b2"], None, None, None, None)
+        dx, g = _block_fn_backward(ctx, dy)
+        return (dx, g["ln1w"], g["ln1b"], g["wqkv"], g["wo"], g["bo"], g["ln2w"], g["ln2b"], g["w1"], g["b1"], g["w2"], g["b2"], None, None, None, None)
 
 
 class EncoderBlockFn(Function):
@@ -530,32 +562,27 @@ class EncoderBlockFn(Function):
 
     @staticmethod
     def forward(ctx, x, ln1w, ln1b, wq, bq, wk, bk, wv, bv, wo, bo, ln2w, ln2b, w1, b1, w2, b2, H, eps, p_out=0.0, p_ffn=0.0, p_attn=0.0):
-        B, N, d = x.shape
-        scale = 1.0 / float(d // H) ** 0.5
-        sh = (SHADOWS.get(wq, wk, wv), SHADOWS.get(wo), SHADOWS.get(w1), SHADOWS.get(w2))
-        bqkv = torch.cat((bq, bk, bv)).detach()
-        seeds = drop_seeds(3) if (p_out > 0.0 or p_ffn > 0.0) else (0, 0, 0)
-        seed_attn = drop_seeds(1)[0] if p_attn > 0.0 else 0
-        x2, saved = block_forward(_f32c(x).reshape(B * N, d), B, N, H, eps, scale, ln1w, ln1b, sh[0], bqkv, sh[1], bo, ln2w, ln2b, sh[2], b1, sh[3], b2,
-                                  p_out, p_ffn, seeds, p_attn, seed_attn)
-        ctx.drop = (p_out, p_ffn, seeds, p_attn, seed_attn)
-        ctx.meta = (B, N, H, scale, d, x.dtype)
-        ctx.save_for_backward(ln1w, ln2w, *sh, *saved)
-        return x2.reshape(B, N, d)
+        scale = 1.0 / float(x.shape[2] // H) ** 0.5
+        return _block_fn_forward(ctx, x, ln1w, ln1b, (wq, wk, wv), (bq, bk, bv), wo, bo, ln2w, ln2b, w1, b1, w2, b2, H, eps, scale, p_out, p_ffn, p_attn, False)
 
     @staticmethod
     def backward(ctx, dy):
-        B, N, H, scale, d, xdt = ctx.meta
-        ln1w, ln2w, wqkv_s, wo_s, w1_s, w2_s, *saved = ctx.saved_tensors
-        dx, g = block_backward(_f32c(dy).reshape(B * N, -1), saved, B, N, H, scale, ln1w, wqkv_s, True, wo_s, ln2w, w1_s, w2_s, *ctx.drop)
+        dx, g = _block_fn_backward(ctx, dy)
+        d = g["bo"].shape[0]
         wq, wk, wv = g["wqkv"].split(d, dim=0)
         bq, bk, bv = g["bqkv"].split(d)
-        return (dx.reshape(B, N, -1).to(xdt), g["ln1w"], g["ln1b"], wq, bq, wk, bk, wv, bv, g["wo"], g["bo"], g["ln2w"], g["ln2b"], g["w1"], g["b1"], g["w2"], g["b2"], None, None, None, None, None)
+        return (dx, g["ln1w"], g["ln1b"], wq, bq, wk, bk, wv, bv, g["wo"], g["bo"], g["ln2w"], g["ln2b"], g["w1"], g["b1"], g["w2"], g["b2"], None, None, None, None, None)
 
 
 # ------------------------------------------------------------------------------------------
 # cross-attention fusion (model_cross.py:104-114 CrossAttentionBlock, :135-142 routing)
 # ------------------------------------------------------------------------------------------
+
+
+# what cross_forward saves for cross_backward, in save_for_backward's order: the type tells which form of the fusion ran (the literal order or
+# the low-rank one); xi: the token tensor or a packed copy of its CLS rows
+DenseSaved = namedtuple("DenseSaved", "xi xj mu rs hn kv q oc p y mu2 rs2 h2 z a")
+LowRankSaved = namedtuple("LowRankSaved", "xi xj mu rs hn R e rz S qf q oc y mu2 rs2 h2 z a")
 
 
 def cross_forward(xi, xj, B, N, H, eps, ln1w, ln1b, wq, bq, wkv_s, bkv, wp, bp, ln2w, ln2b, w1, b1, w2, b2, p=0.0, seeds=(0, 0, 0, 0), pack_cls=False, wk=None, wv=None, bv=None):
@@ -593,7 +620,6 @@ def cross_forward(xi, xj, B, N, H, eps, ln1w, ln1b, wq, bq, wkv_s, bkv, wp, bp, 
             e, rz = ops.cls_softmax_fwd(sc, H, scale)
             ops.gemm(ops.TN, e, hn3, S)                                            # [16, N] x [N, d] per sample
             ocf, oc = ops.head_cols(S, wv, H, row_scale=rz, bias=bv, want_bf16=True)
-        kv, pr = (R, e, rz, S, qf), None                                           # what the backward needs instead of kv / p
     else:
         kv = _linear(hn, wkv_s, bias=bkv)
         # dropout sites (model_cross.py:97,101,25,27): probabilities, proj output, after GELU, FFN output
@@ -604,93 +630,81 @@ def cross_forward(xi, xj, B, N, H, eps, ln1w, ln1b, wq, bq, wkv_s, bkv, wp, bp, 
             rec.fusion(ln1w, B, N, H, e=e, rz=rz, bv=bv)
         else:
             rec.fusion(ln1w, B, N, H, p=pr)
-    y, _, _ = ops.linear_f32(ocf, wp, bp, residual=cls_in, dropout=_dp(p, seeds[1]))
+    y, _, _ = ops.linear_f32(ocf, wp, bp, residual=cls_in, dropout=(p, seeds[1]))
     h2f, h2, mu2, rs2 = ops.layernorm_fwd_f32(y, ln2w, ln2b, eps)
-    af, a, z = ops.linear_f32(h2f, w1, b1, act=ops.ACT_GELU, want_z=True, want_bf16=True, dropout=_dp(p, seeds[2]))
-    y2, _, _ = ops.linear_f32(af, w2, b2, residual=y, dropout=_dp(p, seeds[3]))
+    af, a, z = ops.linear_f32(h2f, w1, b1, act=ops.ACT_GELU, want_z=True, want_bf16=True, dropout=(p, seeds[2]))
+    y2, _, _ = ops.linear_f32(af, w2, b2, residual=y, dropout=(p, seeds[3]))
     # the backward needs xi only for its CLS rows (row 0 of the normed concat): a packed [B, d] copy when the caller is about
     # to overwrite them in place (CrossFusionFn), else xi itself
     keep_xi = ops.rows_combine(torch.empty(B, d, dtype=torch.float32, device=xi.device), a=cls_in) if pack_cls else xi
-    if lowrank:
-        return y2, (keep_xi, xj, mu, rs, hn, *kv, qb, oc, y, mu2, rs2, h2, z, a)
-    return y2, (keep_xi, xj, mu, rs, hn, kv, qb, oc, pr, y, mu2, rs2, h2, z, a)
+    if lowrank:                                                                    # (R, e, rz, S, qf) is what the backward needs instead of kv / p
+        return y2, LowRankSaved(keep_xi, xj, mu, rs, hn, R, e, rz, S, qf, qb, oc, y, mu2, rs2, h2, z, a)
+    return y2, DenseSaved(keep_xi, xj, mu, rs, hn, kv, qb, oc, pr, y, mu2, rs2, h2, z, a)
 
 
 def cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_s, pd=0.0, seeds=(0, 0, 0, 0), wk=None, wv=None, want_dcat_b16=False, rec=None):
     """dy2 fp32 [B, d] -> (dcat fp32 [B*N, d] = grad of the normed concat input, dcls_res fp32 [B, d], grads); want_dcat_b16: g["dcat_b16"] is
     dcat's bf16 copy, written by the same LayerNorm backward (attach_b16).  rec: the attention-map recorder the forward saw (ATTN_RECORDER),
     handed the attention output's gradient doc and dp[b, n, h] = dO_h . (v_h[n] - bv_h) (low-rank form) or v (literal order)."""
-    lowrank = len(saved) == 18                                            # the forward ran the low-rank form: (R, e, rz, S, qf) instead of (kv, p)
-    if lowrank:
-        xi, xj, mu, rs, hn, R, e, rz, S, qf, q, oc, y, mu2, rs2, h2, z, a = saved
-    else:
-        xi, xj, mu, rs, hn, kv, q, oc, p, y, mu2, rs2, h2, z, a = saved       # xi: the token tensor or a packed copy of its CLS rows
-    d, f = xi.shape[1], z.shape[1]
+    s = saved
+    lowrank = isinstance(s, LowRankSaved)
+    xi, hn = s.xi, s.hn
+    d, f = xi.shape[1], s.z.shape[1]
     scale = (d // H) ** -0.5
     zero = _zeros(7 * d + f, xi)
     g = dict(zip(("ln2w", "ln2b", "bp", "b2", "ln1w", "ln1b", "bk0"), zero[:7 * d].split(d)))
     g["b1"] = zero[7 * d:]
     bk0 = g.pop("bk0")                                                    # stays zero: wk.bias has no gradient (softmax shift invariance)
-    dyb = _masked(ops.cast_bf16(dy2), pd, seeds[3])
-    dz = _dgrad(dyb, w2_s, act=ops.ACT_DGELU, aux=z, colsum=g["b1"], dropout=_dp(pd, seeds[2]))
-    g["w2"] = _wgrad(dyb, a, w2_s)
-    dh2 = _dgrad(dz, w1_s)
-    g["w1"] = _wgrad(dz, h2, w1_s)
-    nd = pd == 0.0
-    dy, dyb1 = ops.layernorm_bwd(dh2, y, mu2, rs2, ln2w, g["ln2w"], g["ln2b"], dres=dy2, want_bf16=True,
-                                 dxsum=g["bp"] if nd else None, dressum=g["b2"] if nd else None)
-    if not nd:
-        ops.colsum(dyb, out=g["b2"], accumulate=True)
-        dyb1 = _masked(dyb1, pd, seeds[1])
-        ops.colsum(dyb1, out=g["bp"], accumulate=True)
-    g["wp"] = _wgrad(dyb1, oc, wp_s)
+    # _held: the FFN wgrads' operands, referenced until _join_wgrads in _cross_backward_tail, which returns into this frame
+    dy, dyb1, _held = _ffn_ln2_backward(dy2, g, "bp", s.y, s.mu2, s.rs2, s.h2, s.z, s.a, ln2w, w1_s, w2_s, pd, pd, seeds[1:], 0)
+    g["wp"] = _wgrad(dyb1, s.oc, wp_s)
     if lowrank:
         # d(attention output) in fp32: it meets Wv_h as an fp32 row (xvit_head_rows)
         doc = torch.empty(B, d, dtype=torch.float32, device=xi.device)
         ops.gemm(ops.NN, dyb1, wp_s, doc, split_k=_skinny_split(B, d, d))
         hn3 = hn.view(B, N, d)
         Yb = torch.empty(B, 16, d, dtype=torch.bfloat16, device=xi.device)
-        ops.head_rows(doc, wv, R[H:].transpose(0, 1), H, out_bf16=Yb)             # Y[b, h] = dO_h Wv_h: dp[b, n, h] = hn[b, n] . Y[b, h]
+        ops.head_rows(doc, wv, s.R[H:].transpose(0, 1), H, out_bf16=Yb)             # Y[b, h] = dO_h Wv_h: dp[b, n, h] = hn[b, n] . Y[b, h]
         dp = torch.empty(B, N, 16, dtype=torch.float32, device=xi.device)
         ops.gemm(ops.NT, hn3, Yb, dp)
         if rec is not None:
             rec.fusion_grad(ln1w, B, N, H, doc, dp=dp)
-        drop = pd > 0.0                                                            # rz is then the forward's stat block (rz, rz / (1 - p), bv's weight)
-        coef, dsb = ops.cls_softmax_bwd(e, rz[0] if drop else rz, dp, H, scale, dropout=(pd, seeds[0]))   # (ds | p') per token and head
-        dhn = ops.xattn_kv_dgrad(coef, R, B, N, H, d)                              # dhn[n] = sum_h ds U_h + p Y_h
+        rz, drop = s.rz, pd > 0.0                                                  # rz is then the forward's stat block (rz, rz / (1 - p), bv's weight)
+        coef, dsb = ops.cls_softmax_bwd(s.e, rz[0] if drop else rz, dp, H, scale, dropout=(pd, seeds[0]))   # (ds | p') per token and head
+        dhn = ops.xattn_kv_dgrad(coef, s.R, B, N, H, d)                              # dhn[n] = sum_h ds U_h + p Y_h
         T = torch.empty(B, 16, d, dtype=torch.float32, device=xi.device)
         ops.gemm(ops.TN, dsb, hn3, T)                                              # T[b, h] = sum_n ds hn[b, n]
         dq, _ = ops.head_cols(T, wk, H)                                            # dq_h = Wk_h T_h  (the bk term carries sum_n ds = 0)
-        g["wk"] = ops.head_wgrad(qf, T, H, out=_grad_out(wk, (d, d), xi.device))
-        g["wv"] = ops.head_wgrad(doc, S, H, row_scale=rz[1] if drop else rz, out=_grad_out(wv, (d, d), xi.device))
+        g["wk"] = ops.head_wgrad(s.qf, T, H, out=_grad_out(wk, (d, d), xi.device))
+        g["wv"] = ops.head_wgrad(doc, s.S, H, row_scale=rz[1] if drop else rz, out=_grad_out(wv, (d, d), xi.device))
         g["bv"] = ops.head_bias_grad(doc, rz[2], H) if drop else ops.colsum(doc)
         g["bk"] = bk0                                                              # analytically zero: sum_n ds[n] = 0
-        return _cross_backward_tail(g, dq, dhn, hn, q, xi, xj, mu, rs, ln1w, wq_s, B, N, d, dy, want_dcat_b16)
+        return _cross_backward_tail(g, dq, dhn, s, ln1w, wq_s, B, N, d, dy, want_dcat_b16)
     # the reference's literal order (XVIT_XATTN_FORM=dense, small eager batches under "auto", more than 16 heads): the K/V projection's
     # gradient through the [B N, 2 d] tensor — a K = 2 d dgrad GEMM, a wgrad GEMM and a column-sum pass
     doc = _dgrad(dyb1, wp_s)
     if rec is not None:
-        rec.fusion_grad(ln1w, B, N, H, doc, v=kv[:, d:])
-    dq, dkv = ops.cls_xattn_bwd(q, kv, p, doc, B, N, H, scale, dropout=(pd, seeds[0]))
+        rec.fusion_grad(ln1w, B, N, H, doc, v=s.kv[:, d:])
+    dq, dkv = ops.cls_xattn_bwd(s.q, s.kv, s.p, doc, B, N, H, scale, dropout=(pd, seeds[0]))
     dhn = _dgrad(dkv, wkv_s)                                # [B*N, d] bf16
     g["wkv"] = _wgrad(dkv, hn)
     g["bkv"] = ops.colsum(dkv)
     g["wk"], g["wv"] = g["wkv"].split(d, dim=0)
     g["bk"], g["bv"] = g["bkv"].split(d)
-    return _cross_backward_tail(g, dq, dhn, hn, q, xi, xj, mu, rs, ln1w, wq_s, B, N, d, dy, want_dcat_b16)
+    return _cross_backward_tail(g, dq, dhn, s, ln1w, wq_s, B, N, d, dy, want_dcat_b16)
 
 
-def _cross_backward_tail(g, dq, dhn, hn, q, xi, xj, mu, rs, ln1w, wq_s, B, N, d, dy, want_dcat_b16=False):
-    """The query path's gradient joins the CLS rows of dhn, then the LayerNorm over the normed concat."""
+def _cross_backward_tail(g, dq, dhn, s, ln1w, wq_s, B, N, d, dy, want_dcat_b16=False):
+    """The query path's gradient joins the CLS rows of dhn, then the LayerNorm over the normed concat.  s: the saved activations of either form."""
     dqb = ops.cast_bf16(dq)
     dhq = _dgrad(dqb, wq_s)                                 # [B, d] bf16: the query path reaches row 0 only
     dhn0 = dhn.reshape(B, N * d)[:, :d]
     ops.rows_combine(dhn0, a=dhn0, b=dhq)                   # B rows: merge the two paths into the CLS rows (fp32 add, one bf16 rounding)
-    hn0 = hn.reshape(B, N * d)[:, :d]
+    hn0 = s.hn.reshape(B, N * d)[:, :d]
     g["wq"] = _wgrad(dqb, hn0, wq_s)
     g["bq"] = ops.colsum(dq)
-    dcat, g["dcat_b16"] = ops.layernorm_bwd(dhn, xj, mu, rs, ln1w, g["ln1w"], g["ln1b"], x_alt=xi, seq_len=N, want_bf16=want_dcat_b16)
-    _join_wgrads(xi.device)
+    dcat, g["dcat_b16"] = ops.layernorm_bwd(dhn, s.xj, s.mu, s.rs, ln1w, g["ln1w"], g["ln1b"], x_alt=s.xi, seq_len=N, want_bf16=want_dcat_b16)
+    _join_wgrads(dhn.device)
     return dcat, dy, g
 
 
@@ -706,7 +720,7 @@ class CrossFusionFn(Function):
         sh = (SHADOWS.get(wq), SHADOWS.get(wk, wv), SHADOWS.get(wp), SHADOWS.get(w1), SHADOWS.get(w2))
         bkv = torch.cat((bk, bv)).detach()
         xi2, xj2 = _f32c(xi).reshape(B if narrow else B * N, d), _f32c(xj).reshape(B * N, d)
-        seeds = drop_seeds(4) if p > 0.0 else (0, 0, 0, 0)
+        seeds = _seeds(4, p > 0.0)
         # concat: the output is x_i with its CLS rows replaced by the fused token (model_cross.py:142) — by default a copy, as
         # the reference's torch.cat.  `exclusive` (set by MultiScaleBlock when ModelCross drives it, never by a direct caller):
         # x_i was produced inside the block, nobody else holds it or reads its CLS rows (the other fusions take its PATCH rows,
@@ -719,7 +733,7 @@ class CrossFusionFn(Function):
         y2, saved = cross_forward(xi2, xj2, B, N, H, eps, ln1w, ln1b, wq.detach(), bq, sh[1], bkv, wp.detach(), bp, ln2w, ln2b, w1.detach(), b1,
                                   w2.detach(), b2, p, seeds, pack_cls=inplace, wk=wk.detach(), wv=wv.detach(), bv=bv.detach())
         ctx.drop = (p, seeds)
-        ctx.meta = (B, N, H, d, concat, inplace, narrow)
+        ctx.meta = (B, N, H, d, concat, inplace, narrow, type(saved))       # type(saved): which form of the fusion ran
         ctx.save_for_backward(ln1w, ln2w, *sh, wk.detach(), wv.detach(), *saved)
         rec = ATTN_RECORDER.get()
         if rec is not None:
@@ -735,12 +749,12 @@ class CrossFusionFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        B, N, H, d, concat, inplace, narrow = ctx.meta
+        B, N, H, d, concat, inplace, narrow, form = ctx.meta
         ln1w, ln2w, wq_s, wkv_s, wp_s, w1_s, w2_s, wk_m, wv_m, *saved = ctx.saved_tensors
         dout = _f32c(dout)
         dy2 = ops.rows_combine(torch.empty(B, d, dtype=torch.float32, device=dout.device), a=dout[:, 0])
         # a cls-only fusion's patch-row gradient is (up to the CLS rows) the whole gradient of the partner's last block: hand it on in bf16 too
-        dcat, dcls_res, g = cross_backward(dy2, saved, B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_s, *ctx.drop, wk=wk_m, wv=wv_m,
+        dcat, dcls_res, g = cross_backward(dy2, form(*saved), B, N, H, ln1w, wq_s, wkv_s, wp_s, ln2w, w1_s, w2_s, *ctx.drop, wk=wk_m, wv=wv_m,
                                            want_dcat_b16=not concat and B16_HANDOFF, rec=getattr(ctx, "rec", None))
         dcat = dcat.reshape(B, N, d)
         # cls row -> x_i (normed-concat path + the un-normed residual path); patch rows -> x_j
@@ -809,7 +823,6 @@ class PatchEmbedFn(Function):
         Bn, M = img.shape[0], img.shape[1]
         d, pd = w.shape
         w_s = SHADOWS.get(w)
-        ctx.slot = None
         if keep is not None:
             return PatchEmbedFn._forward_selected(ctx, img, w_s, b, cls, pos, patch, p, concat, keep)
         # a bf16 volume tensor feeds the GEMM's loaders directly (no [rows, pd] patch matrix in HBM: -2 GB of traffic and
@@ -832,15 +845,22 @@ class PatchEmbedFn(Function):
             x = torch.empty(M * Bn * N, d, dtype=torch.float32, device=img.device)
             ops.gemm(ops.NT, patches, w_s, x, bias=b, residual=pos2, res_row_mod=N, res_row_off=0)
         ops.cls_row_fwd(cls.detach().reshape(d), pos2, x, M * Bn, N, d)
-        seed = drop_seeds(1)[0] if p > 0.0 else 0
+        rec = ATTN_RECORDER.get()
+        if rec is not None and getattr(rec, "input_grad", False):
+            ctx.rec = rec                      # xvit.interpret.input_attributions: the fp32 volume gradient goes to the recorder
+        return PatchEmbedFn._finish(ctx, x, img, patches, w_s, M, N, p, patch, concat, fused, None)     # fused: `patches` is the volume tensor itself
+
+    @staticmethod
+    def _finish(ctx, x, img, patches, w_s, M, N, p, patch, concat, fused, slot):
+        """Where both forward paths end: the embedding dropout in place on x [M*B*N, d], what the backward needs, the outputs."""
+        Bn, d = img.shape[0], x.shape[1]
+        seed = _seeds(1, p > 0.0)[0]
         if p > 0.0:                       # self.dropout on the embedded tokens (model_cross.py:198)
             ops.dropout(x, p, seed, out=x)
         ctx.meta = (M, Bn, N, d, p, seed, patch if fused else None)
         ctx.vol = (tuple(img.shape), img.dtype, patch, concat)    # the input gradient needs the volume's geometry only, never its values
-        rec = ATTN_RECORDER.get()
-        if rec is not None and getattr(rec, "input_grad", False):
-            ctx.rec = rec                      # xvit.interpret.input_attributions: the fp32 volume gradient goes to the recorder
-        ctx.save_for_backward(patches, w_s)     # fused: the volume tensor itself
+        ctx.slot = slot                   # `keep` arrives as a tuple, so slot is no Function input and cannot go through save_for_backward
+        ctx.save_for_backward(patches, w_s)
         if concat:
             return x.reshape(Bn, N, d)
         # one output per modality (views of one buffer): slicing a stacked [M, B, N, d] output in the caller would cost
@@ -863,19 +883,11 @@ class PatchEmbedFn(Function):
         K, P = keep_idx.shape[1], slot.shape[1]
         if P != ops._patch_counts(img.shape, patch)[0] or pos.numel() != (P + 1) * d:
             raise RuntimeError(f"PatchEmbedFn: keep was drawn for {P} patches per sequence, which is not this volume's patch grid")
-        N = K + 1
         patches = ops.patchify_select(img.contiguous(), patch, keep_idx).reshape(-1, pd)       # [M*B*N, pd], row 0 of each sequence = 0
-        x = torch.empty(M * Bn * N, d, dtype=torch.float32, device=img.device)
+        x = torch.empty(M * Bn * (K + 1), d, dtype=torch.float32, device=img.device)
         ops.gemm(ops.NT, patches, w_s, x, bias=b)
         ops.embed_select_fwd(x, cls.detach().reshape(d), pos.detach().reshape(P + 1, d), keep_idx)
-        seed = drop_seeds(1)[0] if p > 0.0 else 0
-        if p > 0.0:
-            ops.dropout(x, p, seed, out=x)
-        ctx.meta = (M, Bn, N, d, p, seed, None)
-        ctx.vol = (tuple(img.shape), img.dtype, patch, concat)
-        ctx.slot = slot                       # `keep` arrives as a tuple, so slot is no Function input and cannot go through save_for_backward
-        ctx.save_for_backward(patches, w_s)
-        return tuple(x.reshape(M, Bn, N, d).unbind(0))
+        return PatchEmbedFn._finish(ctx, x, img, patches, w_s, M, K + 1, p, patch, concat, False, slot)
 
     @staticmethod
     def backward(ctx, *dxs):
@@ -1039,8 +1051,8 @@ class HeadFn(Function):
         # one row per sample: fp32 operands throughout (see cross_forward); bf16 copies only feed the backward chain
         hf, h, mu, rs = ops.layernorm_fwd_f32(x2, lnw, lnb, eps)
         w0_s = SHADOWS.get(w0)
-        seeds = drop_seeds(2) if p > 0.0 else (0, 0)
-        af, a, z = ops.linear_f32(hf, w0.detach(), b0.detach(), act=ops.ACT_GELU, want_z=True, want_bf16=True, dropout=_dp(p, seeds[0]))   # mlp_head[m][0..2]
+        seeds = _seeds(2, p > 0.0)
+        af, a, z = ops.linear_f32(hf, w0.detach(), b0.detach(), act=ops.ACT_GELU, want_z=True, want_bf16=True, dropout=(p, seeds[0]))   # mlp_head[m][0..2]
         logits, _, _ = ops.linear_f32(af, w3.detach(), b3.detach())
         if p > 0.0:                                                                     # mlp_head[m][4]: dropout on the logits
             ops.dropout(logits, p, seeds[1], out=logits)
@@ -1071,6 +1083,15 @@ class HeadFn(Function):
         return dx, dg, dbeta, dW0, db0, dW3, db3, None, None
 
 
+def _mean_ce_backward(ctx, dlogits, dloss):
+    """d loss / d logits_m of both cross-entropy Functions: the kernel's dl scaled by the loss's gradient, plus the mean logits' share."""
+    (dl,) = ctx.saved_tensors
+    g = dl * dloss
+    if dlogits is not None:
+        g = g + (dlogits / ctx.M).unsqueeze(0)
+    return g
+
+
 class MeanCrossEntropyFn(Function):
     """(logits_m [M,B,C], labels) -> (mean logits [B,C], CE loss)."""
 
@@ -1083,11 +1104,7 @@ class MeanCrossEntropyFn(Function):
 
     @staticmethod
     def backward(ctx, dlogits, dloss):
-        (dl,) = ctx.saved_tensors
-        g = dl * dloss
-        if dlogits is not None:
-            g = g + (dlogits / ctx.M).unsqueeze(0)
-        return g, None, None
+        return _mean_ce_backward(ctx, dlogits, dloss), None, None
 
 
 class MeanMixCrossEntropyFn(Function):
@@ -1103,11 +1120,7 @@ class MeanMixCrossEntropyFn(Function):
 
     @staticmethod
     def backward(ctx, dlogits, dloss):
-        (dl,) = ctx.saved_tensors
-        g = dl * dloss
-        if dlogits is not None:
-            g = g + (dlogits / ctx.M).unsqueeze(0)
-        return g, None, None, None
+        return _mean_ce_backward(ctx, dlogits, dloss), None, None, None
 
 
 def mix_volumes(img, table):
@@ -1141,10 +1154,8 @@ class LayerNormFn(Function):
     def backward(ctx, dy):
         x2, mu, rs, w = ctx.saved_tensors
         d = x2.shape[1]
-        dyb = dy.reshape(-1, d)
-        dyb = dyb if dyb.dtype == torch.bfloat16 else ops.cast_bf16(_f32c(dyb))
         dg, db = _zeros(d, x2), _zeros(d, x2)
-        dx, _ = ops.layernorm_bwd(dyb.contiguous(), x2, mu, rs, w, dg, db)
+        dx, _ = ops.layernorm_bwd(_as_bf16_2d(dy), x2, mu, rs, w, dg, db)
         return dx.reshape(ctx.shape), dg, db, None
 
 
@@ -1162,8 +1173,8 @@ class LinearFn(Function):
     def forward(ctx, x, w, b, out_f32, p=0.0):
         x2 = _as_bf16_2d(x)
         w_s = SHADOWS.get(w)
-        seed = drop_seeds(1)[0] if p > 0.0 else 0
-        y = _linear(x2, w_s, bias=b, out_dtype=torch.float32 if out_f32 else torch.bfloat16, dropout=_dp(p, seed))
+        seed = _seeds(1, p > 0.0)[0]
+        y = _linear(x2, w_s, bias=b, out_dtype=torch.float32 if out_f32 else torch.bfloat16, dropout=(p, seed))
         ctx.save_for_backward(x2, w_s)
         ctx.meta = (x.shape, x.dtype, b is not None, p, seed)
         return y.reshape(*x.shape[:-1], w.shape[0])
@@ -1189,9 +1200,9 @@ class FeedForwardFn(Function):
         x2 = _as_bf16_2d(x)
         w1_s, w2_s = SHADOWS.get(w1), SHADOWS.get(w2)
         z = torch.empty(x2.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
-        seeds = drop_seeds(2) if p > 0.0 else (0, 0)
-        a = _linear(x2, w1_s, bias=b1, act=ops.ACT_GELU, aux=z, dropout=_dp(p, seeds[0]), aux_mode=AUX_MODE)
-        y = _linear(a, w2_s, bias=b2, out_dtype=torch.float32, dropout=_dp(p, seeds[1]))
+        seeds = _seeds(2, p > 0.0)
+        a = _linear(x2, w1_s, bias=b1, act=ops.ACT_GELU, aux=z, dropout=(p, seeds[0]), aux_mode=AUX_MODE)
+        y = _linear(a, w2_s, bias=b2, out_dtype=torch.float32, dropout=(p, seeds[1]))
         ctx.save_for_backward(x2, z, a, w1_s, w2_s)
         ctx.meta = (x.shape, x.dtype, p, seeds)
         return y.reshape(*x.shape[:-1], w2.shape[0])
@@ -1203,7 +1214,7 @@ class FeedForwardFn(Function):
         dyb = _as_bf16_2d(dy)
         if p > 0.0:
             dyb = ops.dropout(dyb, p, seeds[1])
-        dz = _dgrad(dyb, w2_s, act=ops.ACT_DGELU, aux=z, dropout=_dp(p, seeds[0]), aux_mode=AUX_MODE)
+        dz = _dgrad(dyb, w2_s, act=ops.ACT_DGELU, aux=z, dropout=(p, seeds[0]), aux_mode=AUX_MODE)
         dx = _dgrad(dz, w1_s).reshape(shape)
         dW1, dW2 = _wgrad(dz, x2), _wgrad(dyb, a)
         _join_wgrads(dyb.device)
@@ -1217,7 +1228,7 @@ class AttentionCoreFn(Function):
     def forward(ctx, qkv, H, scale, p=0.0):
         B, N, d3 = qkv.shape
         q2 = _as_bf16_2d(qkv)
-        seed = drop_seeds(1)[0] if p > 0.0 else 0
+        seed = _seeds(1, p > 0.0)[0]
         o, lse = _attn_fwd(q2, B, N, H, scale, p, seed)
         ctx.save_for_backward(q2, o, lse)
         ctx.meta = (B, N, H, scale, qkv.dtype, p, seed)
@@ -1238,7 +1249,7 @@ class ClsAttentionCoreFn(Function):
     def forward(ctx, q, kv, H, scale, pd=0.0):
         B, N, d2 = kv.shape
         qb, kvb = _as_bf16_2d(q), _as_bf16_2d(kv)
-        seed = drop_seeds(1)[0] if pd > 0.0 else 0
+        seed = _seeds(1, pd > 0.0)[0]
         o, p = ops.cls_xattn_fwd(qb, kvb, B, N, H, scale, dropout=(pd, seed))
         ctx.save_for_backward(qb, kvb, p)
         ctx.meta = (B, N, H, scale, q.dtype, kv.dtype, pd, seed)

@@ -4,6 +4,7 @@ is not on the GPU is an error."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 
@@ -28,6 +29,18 @@ def _stream() -> int:
     return _raw_stream(_cur_dev())
 
 
+class _Entries:
+    """The library's entry points as attributes: each is looked up in _lib.load() at its first use and bound here, so a launch
+    costs one attribute read."""
+
+    def __getattr__(self, sym):
+        fn = getattr(_lib.load(), sym)
+        setattr(self, sym, fn)
+        return fn
+
+
+_L = _Entries()
+
 # Optional live per-kernel timing (bench.py): when PROFILE is a list, every wrapper brackets its
 # launch with HIP events recorded on the launch stream and appends
 # (kernel family, algorithmic work, "flop" | "byte", start_event, end_event).
@@ -50,7 +63,7 @@ GEMM_TILE = 0            # mirror of xvit_set_option("gemm_tile") for the family
 def set_option(name: str, value: int):
     """xvit_set_option (include/xvit.h): process-wide tuning knobs, e.g. ("gemm_tile", 1) forces the 128x128 kernel."""
     global GEMM_TILE
-    _lib.check(_lib.load().xvit_set_option(name.encode(), int(value)), "xvit_set_option")
+    _lib.check(_L.xvit_set_option(name.encode(), int(value)), "xvit_set_option")
     if name == "gemm_tile":
         GEMM_TILE = int(value)
 
@@ -64,22 +77,49 @@ def set_dropout_epoch(counter):
     global _DROP_EPOCH
     if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
         raise RuntimeError("set_dropout_epoch: need a one-element int64 GPU tensor (or None)")
-    _lib.check(_lib.load().xvit_set_dropout_epoch(counter.data_ptr() if counter is not None else None), "xvit_set_dropout_epoch")
+    _lib.check(_L.xvit_set_dropout_epoch(counter.data_ptr() if counter is not None else None), "xvit_set_dropout_epoch")
     _DROP_EPOCH = counter
 
 
 PROFILE_SHAPES = False   # append the GEMM shape/epilogue to the family name (bench.py --detail)
 
 
-def _run(name, work, kind, rc_fn, what):
+def _launch(sym, *args):
+    """One entry point of the library on the current stream (its last argument), nothing recorded in PROFILE."""
+    rc = getattr(_L, sym)(*args, _raw_stream(_cur_dev()))
+    if rc:
+        _lib.check(rc, sym)
+
+
+def _call(sym, family, work, kind, *args):
+    """_launch, bracketed by two events and recorded under `family` when PROFILE is a list."""
     if PROFILE is None:
-        _lib.check(rc_fn(), what)
+        rc = getattr(_L, sym)(*args, _raw_stream(_cur_dev()))
+        if rc:
+            _lib.check(rc, sym)
         return
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
-    _lib.check(rc_fn(), what)
+    _launch(sym, *args)
     e.record()
-    PROFILE.append((name, float(work), kind, s, e))
+    PROFILE.append((family, float(work), kind, s, e))
+
+
+# torch.empty of the two dtypes the kernels write: _f32(rows, d, device=x.device)
+_f32 = functools.partial(torch.empty, dtype=torch.float32)
+_b16 = functools.partial(torch.empty, dtype=torch.bfloat16)
+
+
+def _ws(nbytes, like):
+    """fp32 workspace of `nbytes` (an xvit_*_workspace_bytes answer) on like's device, None for 0."""
+    return _f32(nbytes // 4, device=like.device) if nbytes else None
+
+
+def _drop(dropout):
+    """None or (p, seed) -> the kernels' (p, seed) arguments: (0.0, 0) when dropout is off."""
+    if dropout is None or not dropout[0] > 0.0:
+        return 0.0, 0
+    return float(dropout[0]), int(dropout[1])
 
 
 def _ptr(t) -> int | None:
@@ -113,11 +153,16 @@ def _rows2d(t):
     return t.stride(0)
 
 
+def _ld(t):
+    """_rows2d of an optional tensor (0 for None)."""
+    return _rows2d(t) if t is not None else 0
+
+
 def gemm_workspace_bytes(layout, M, N, K, split_k, batch=1):
     """Bytes of fp32 workspace ops.gemm(..., split_k=split_k, workspace=...) needs for this product (0 when split_k <= 1)."""
     a = GemmArgs()
     a.layout, a.M, a.N, a.K, a.split_k, a.batch = layout, M, N, K, split_k, batch
-    return _lib.load().xvit_gemm_workspace_bytes(C.byref(a))
+    return _L.xvit_gemm_workspace_bytes(C.byref(a))
 
 
 def gemm(layout, A, B, C_out, *, bias=None, residual=None, aux=None, act=ACT_NONE, accumulate=False,
@@ -166,13 +211,12 @@ def gemm(layout, A, B, C_out, *, bias=None, residual=None, aux=None, act=ACT_NON
     if colsum is not None:
         assert colsum.dtype == torch.float32
         a.colsum = _ptr(colsum)
-    if dropout is not None and dropout[0] > 0.0:   # (p, seed)
-        a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1])
+    a.dropout_p, a.dropout_seed = _drop(dropout)
     ws = None
     if split_k > 1:
-        need = _lib.load().xvit_gemm_workspace_bytes(C.byref(a))
+        need = _L.xvit_gemm_workspace_bytes(C.byref(a))
         if need:
-            ws = workspace if workspace is not None else torch.empty(need // 4, dtype=torch.float32, device=C_out.device)
+            ws = workspace if workspace is not None else _ws(need, C_out)
             if not (ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() * 4 >= need):
                 raise RuntimeError(f"xvit: gemm workspace must be a contiguous fp32 tensor of at least {need} bytes")
             a.workspace, a.workspace_bytes = _ptr(ws), need
@@ -184,8 +228,7 @@ def gemm(layout, A, B, C_out, *, bias=None, residual=None, aux=None, act=ACT_NON
     if PROFILE is not None and PROFILE_SHAPES:
         epi = ("+b" if bias is not None else "") + ("+gelu" if act == ACT_GELU else "+dgelu" if act == ACT_DGELU else "") + ("+res" if residual is not None else "")
         tag += f"[{a.M}x{a.N}x{a.K}{epi}{'' if a.c_dtype == BF16 else ',f32'}{',s%d' % split_k if split_k > 1 else ''}]"
-    _run(tag, 2.0 * a.M * a.N * a.K * a.batch, "flop",
-         lambda: _lib.load().xvit_gemm(C.byref(a), _stream()), "xvit_gemm")
+    _call("xvit_gemm", tag, 2.0 * a.M * a.N * a.K * a.batch, "flop", C.byref(a))
     return C_out
 
 
@@ -203,26 +246,21 @@ def _alt_ld(x, x_alt, seq_len):
 
 def layernorm_fwd(x, gamma, beta, eps, *, x_alt=None, seq_len=0, out=None):
     """x fp32 [rows, d] (row stride free) -> (y bf16 [rows, d], mean, rstd)."""
-    rows, d = x.shape
-    y = out if out is not None else torch.empty(rows, d, dtype=torch.bfloat16, device=x.device)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    ld_alt = _alt_ld(x, x_alt, seq_len)
-    _run("layernorm_fwd", rows * d * 6.0, "byte",
-         lambda: _lib.load().xvit_layernorm_fwd(_ptr(x), _ptr(x_alt), _rows2d(x), seq_len, ld_alt, _ptr(gamma), _ptr(beta), eps,
-                                                _ptr(y), _rows2d(y), None, 0, _ptr(mean), _ptr(rstd), rows, d, _stream()), "xvit_layernorm_fwd")
+    (rows, d), dev = x.shape, x.device
+    y = out if out is not None else _b16(rows, d, device=dev)
+    mean, rstd = _f32(rows, device=dev), _f32(rows, device=dev)
+    _call("xvit_layernorm_fwd", "layernorm_fwd", rows * d * 6.0, "byte", _ptr(x), _ptr(x_alt), _rows2d(x), seq_len, _alt_ld(x, x_alt, seq_len),
+          _ptr(gamma), _ptr(beta), eps, _ptr(y), _rows2d(y), None, 0, _ptr(mean), _ptr(rstd), rows, d)
     return y, mean, rstd
 
 
 def layernorm_fwd_f32(x, gamma, beta, eps, want_bf16=True):
     """x fp32 [rows, d] (row stride free) -> (y fp32, y bf16 | None, mean, rstd): the single-token CLS path keeps fp32 operands."""
-    rows, d = x.shape
-    yf = torch.empty(rows, d, dtype=torch.float32, device=x.device)
-    yb = torch.empty(rows, d, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().xvit_layernorm_fwd(_ptr(x), None, _rows2d(x), 0, 0, _ptr(gamma), _ptr(beta), eps, _ptr(yb), d, _ptr(yf), d,
-                                              _ptr(mean), _ptr(rstd), rows, d, _stream()), "xvit_layernorm_fwd")
+    (rows, d), dev = x.shape, x.device
+    yf = _f32(rows, d, device=dev)
+    yb = _b16(rows, d, device=dev) if want_bf16 else None
+    mean, rstd = _f32(rows, device=dev), _f32(rows, device=dev)
+    _launch("xvit_layernorm_fwd", _ptr(x), None, _rows2d(x), 0, 0, _ptr(gamma), _ptr(beta), eps, _ptr(yb), d, _ptr(yf), d, _ptr(mean), _ptr(rstd), rows, d)
     return yf, yb, mean, rstd
 
 
@@ -241,149 +279,130 @@ def linear_f32(x, W, bias=None, *, act=ACT_NONE, residual=None, want_z=False, wa
         xp[:, :K].copy_(x)
         wp[:, :K].copy_(W)
         x, W, K = xp, wp, K16
-    y = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    yb = torch.empty(M, N, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
-    zb = torch.empty(M, N, dtype=torch.bfloat16, device=x.device) if want_z else None
-    lib = _lib.load()
-    need = lib.xvit_linear_f32_workspace_bytes(M, N, K)
-    ws = torch.empty(need // 4, dtype=torch.float32, device=x.device) if need else None
-    dp, seed = (float(dropout[0]), int(dropout[1])) if dropout is not None and dropout[0] > 0.0 else (0.0, 0)
-    _run("linear_f32", 2.0 * M * N * K, "flop",
-         lambda: lib.xvit_linear_f32(_ptr(x), _rows2d(x), _ptr(W), _rows2d(W), _ptr(bias), _ptr(y), N, M, N, K, act, _ptr(zb), N,
-                                     _ptr(residual), _rows2d(residual) if residual is not None else 0, _ptr(yb), N, dp, seed, _ptr(ws), need, _stream()),
-         "xvit_linear_f32")
+    dev = x.device
+    y = _f32(M, N, device=dev)
+    yb = _b16(M, N, device=dev) if want_bf16 else None
+    zb = _b16(M, N, device=dev) if want_z else None
+    need = _L.xvit_linear_f32_workspace_bytes(M, N, K)
+    ws = _ws(need, x)
+    _call("xvit_linear_f32", "linear_f32", 2.0 * M * N * K, "flop", _ptr(x), _rows2d(x), _ptr(W), _rows2d(W), _ptr(bias), _ptr(y), N, M, N, K, act,
+          _ptr(zb), N, _ptr(residual), _ld(residual), _ptr(yb), N, *_drop(dropout), _ptr(ws), need)
     return y, yb, zb
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, *, x_alt=None, seq_len=0, dres=None, want_bf16=False, dxsum=None, dressum=None):
     """-> (dx fp32, dx_bf16 | None); dgamma/dbeta (fp32, [d]) are accumulated into; so are the optional
     column sums dxsum (of dx) and dressum (of dres)."""
-    rows, d = x.shape
-    dx = torch.empty(rows, d, dtype=torch.float32, device=x.device)
-    dxb = torch.empty(rows, d, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
+    (rows, d), dev = x.shape, x.device
+    dx = _f32(rows, d, device=dev)
+    dxb = _b16(rows, d, device=dev) if want_bf16 else None
     nbytes = rows * d * (2.0 + 4.0 + 4.0 + (4.0 if dres is not None else 0.0) + (2.0 if want_bf16 else 0.0))
-    ws, ws_bytes = None, 0
-    if DETERMINISTIC:
-        ws_bytes = _lib.load().xvit_layernorm_bwd_workspace_bytes(rows, d)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-    ld_alt = _alt_ld(x, x_alt, seq_len)
-    _run("layernorm_bwd", nbytes, "byte", lambda: _lib.load().xvit_layernorm_bwd(
-        _ptr(dy), _rows2d(dy), _ptr(x), _ptr(x_alt), _rows2d(x), seq_len, ld_alt, _ptr(mean), _ptr(rstd), _ptr(gamma),
-        _ptr(dres), _rows2d(dres) if dres is not None else 0, _ptr(dx), d, _ptr(dxb), d,
-        _ptr(dgamma), _ptr(dbeta), _ptr(dxsum), _ptr(dressum), rows, d, _ptr(ws), ws_bytes, _stream()), "xvit_layernorm_bwd")
+    ws_bytes = _L.xvit_layernorm_bwd_workspace_bytes(rows, d) if DETERMINISTIC else 0
+    ws = _ws(ws_bytes, x)
+    _call("xvit_layernorm_bwd", "layernorm_bwd", nbytes, "byte", _ptr(dy), _rows2d(dy), _ptr(x), _ptr(x_alt), _rows2d(x), seq_len, _alt_ld(x, x_alt, seq_len),
+          _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dres), _ld(dres), _ptr(dx), d, _ptr(dxb), d,
+          _ptr(dgamma), _ptr(dbeta), _ptr(dxsum), _ptr(dressum), rows, d, _ptr(ws), ws_bytes)
     return dx, dxb
 
 
-def attn_fwd(qkv, B, N, H, scale, dropout=(0.0, 0)):
-    """qkv bf16 [B*N, 3d] (q | k | v along columns) -> (o bf16 [B*N, d], lse fp32 [B, H, N]).  dropout = (p, seed): dropout
-    on the attention probabilities (model.py:169); the mask is that of ops.dropout on a [B, H, N, N] tensor with that seed."""
+def _attn_fwd(sym, family, qkv, B, N, H, scale, *tail):
+    """The two forward attention entry points: their outputs and the q | k | v operand arguments; `tail`: what follows scale."""
     d = qkv.shape[1] // 3
     dh = d // H
-    o = torch.empty(B * N, d, dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    o, lse = _b16(B * N, d, device=qkv.device), _f32(B, H, N, device=qkv.device)
     ld = _rows2d(qkv)
-    p = qkv.data_ptr()
-    lib = _lib.load()
-    need = lib.xvit_attn_fwd_workspace_bytes(B, H, N) if dropout[0] == 0.0 else 0    # > 0: the CLS-peel form (include/xvit.h)
-    ws = torch.empty(need // 4, dtype=torch.float32, device=qkv.device) if need else None
-    _run("attn_fwd", 4.0 * B * H * N * N * dh, "flop",
-         lambda: lib.xvit_attn_fwd(p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(o), N * d, d, _ptr(lse), B, H, N, dh, scale,
-                                   float(dropout[0]), int(dropout[1]), _ptr(ws), need, _stream()),
-         "xvit_attn_fwd")
+    p = _ptr(qkv)
+    _call(sym, family, 4.0 * B * H * N * N * dh, "flop", p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(o), N * d, d, _ptr(lse), B, H, N, dh, scale, *tail)
     return o, lse
 
 
-def attn_rollout_step(qkv, lse, r, B, N, H, scale):
-    """One attention-rollout step through a self-attention block (xvit_attn_rollout_step): qkv bf16 [B*N, 3d] and lse fp32 [B, H, N] of
-    the block's forward, r fp32 [B, N] -> r_out fp32 [B, N] = r / 2 + (r . mean_h P_h) / 2.  P is recomputed from q, k and lse, never stored."""
+def attn_fwd(qkv, B, N, H, scale, dropout=None):
+    """qkv bf16 [B*N, 3d] (q | k | v along columns) -> (o bf16 [B*N, d], lse fp32 [B, H, N]).  dropout = (p, seed): dropout
+    on the attention probabilities (model.py:169); the mask is that of ops.dropout on a [B, H, N, N] tensor with that seed."""
+    p, seed = _drop(dropout)
+    need = _L.xvit_attn_fwd_workspace_bytes(B, H, N) if p == 0.0 else 0    # > 0: the CLS-peel form (include/xvit.h)
+    ws = _ws(need, qkv)
+    return _attn_fwd("xvit_attn_fwd", "attn_fwd", qkv, B, N, H, scale, p, seed, _ptr(ws), need)
+
+
+def attn_fwd_fp8(qkv, B, N, H, scale):
+    """MX-fp8 forward attention (xvit_attn_fwd_fp8): qkv bf16 [B*N, 3d] -> (o bf16 [B*N, d], lse fp32 [B, H, N]); opt-in."""
+    need = _L.xvit_attn_fp8_workspace_bytes(B, H, N, qkv.shape[1] // 3 // H)
+    ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
+    return _attn_fwd("xvit_attn_fwd_fp8", "attn_fwd_fp8", qkv, B, N, H, scale, _ptr(ws), need)
+
+
+def _attn_map_step(qkv, lse, r, B, N, H, scale, do=None):
+    """attn_rollout_step, or attn_relevance_step when the attention output's gradient `do` is given."""
     d = qkv.shape[1] // 3
+    dh = d // H
     assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, N)
     assert r.dtype == torch.float32 and r.is_contiguous() and tuple(r.shape) == (B, N)
     out = torch.empty_like(r)
     ld = _rows2d(qkv)
     p = _ptr(qkv)
-    _run("attn_rollout", 2.0 * B * H * N * N * (d // H), "flop",
-         lambda: _lib.load().xvit_attn_rollout_step(p, p + 2 * d, N * ld, ld, _ptr(lse), _ptr(r), _ptr(out), B, H, N, d // H, scale, _stream()),
-         "xvit_attn_rollout_step")
+    tail = (_ptr(r), _ptr(out), B, H, N, dh, scale)
+    if do is None:
+        _call("xvit_attn_rollout_step", "attn_rollout", 2.0 * B * H * N * N * dh, "flop", p, p + 2 * d, N * ld, ld, _ptr(lse), *tail)
+    else:
+        assert do.dtype == torch.bfloat16 and tuple(do.shape) == (B * N, d)
+        ldo = _rows2d(do)
+        _call("xvit_attn_relevance_step", "attn_relevance", 4.0 * B * H * N * N * dh, "flop", p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(lse),
+              _ptr(do), N * ldo, ldo, *tail)
     return out
+
+
+def attn_rollout_step(qkv, lse, r, B, N, H, scale):
+    """One attention-rollout step through a self-attention block (xvit_attn_rollout_step): qkv bf16 [B*N, 3d] and lse fp32 [B, H, N] of
+    the block's forward, r fp32 [B, N] -> r_out fp32 [B, N] = r / 2 + (r . mean_h P_h) / 2.  P is recomputed from q, k and lse, never stored."""
+    return _attn_map_step(qkv, lse, r, B, N, H, scale)
 
 
 def attn_relevance_step(qkv, lse, do, r, B, N, H, scale):
     """One class-specific relevance step through a self-attention block (xvit_attn_relevance_step): qkv bf16 [B*N, 3d] and lse fp32
     [B, H, N] of the block's forward, do bf16 [B*N, d] the gradient of its attention output, r fp32 [B, N] -> r_out fp32 [B, N] =
     r + r . mean_h relu(P_h * dP_h), dP_h = dO_h V_h^T.  P and dP are recomputed, never stored."""
-    d = qkv.shape[1] // 3
-    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, N)
-    assert r.dtype == torch.float32 and r.is_contiguous() and tuple(r.shape) == (B, N)
-    assert do.dtype == torch.bfloat16 and tuple(do.shape) == (B * N, d)
-    out = torch.empty_like(r)
-    ld, ldo = _rows2d(qkv), _rows2d(do)
-    p = _ptr(qkv)
-    _run("attn_relevance", 4.0 * B * H * N * N * (d // H), "flop",
-         lambda: _lib.load().xvit_attn_relevance_step(p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(lse), _ptr(do), N * ldo, ldo, _ptr(r), _ptr(out),
-                                                      B, H, N, d // H, scale, _stream()),
-         "xvit_attn_relevance_step")
-    return out
+    return _attn_map_step(qkv, lse, r, B, N, H, scale, do)
 
 
-def attn_fwd_fp8(qkv, B, N, H, scale):
-    """MX-fp8 forward attention (xvit_attn_fwd_fp8): qkv bf16 [B*N, 3d] -> (o bf16 [B*N, d], lse fp32 [B, H, N]); opt-in."""
-    d = qkv.shape[1] // 3
-    dh = d // H
-    o = torch.empty(B * N, d, dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-    ld = _rows2d(qkv)
-    need = _lib.load().xvit_attn_fp8_workspace_bytes(B, H, N, dh)
-    ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
-    p = _ptr(qkv)
-    _run("attn_fwd_fp8", 4.0 * B * H * N * N * dh, "flop",
-         lambda: _lib.load().xvit_attn_fwd_fp8(p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(o), N * d, d, _ptr(lse), B, H, N, dh, scale, _ptr(ws), need, _stream()),
-         "xvit_attn_fwd_fp8")
-    return o, lse
-
-
-def attn_bwd(qkv, o, d_o, lse, B, N, H, scale, dropout=(0.0, 0)):
+def attn_bwd(qkv, o, d_o, lse, B, N, H, scale, dropout=None):
     """-> dqkv bf16 [B*N, 3d]."""
     d = qkv.shape[1] // 3
     dh = d // H
     dqkv = torch.empty_like(qkv)
-    lib = _lib.load()
-    need = lib.xvit_attn_bwd_workspace_bytes(B, H, N)
-    ws = torch.empty(need // 4, dtype=torch.float32, device=qkv.device)   # rowsum(do*o) | -lse*log2e | CLS-peel partials
+    need = _L.xvit_attn_bwd_workspace_bytes(B, H, N)
+    ws = _ws(need, qkv)                    # rowsum(do*o) | -lse*log2e | CLS-peel partials
     ld = _rows2d(qkv)
     assert dqkv.stride(0) == ld and _rows2d(o) == d and _rows2d(d_o) == d
     p, g = qkv.data_ptr(), dqkv.data_ptr()
-    _run("attn_bwd", 10.0 * B * H * N * N * dh, "flop",
-         lambda: lib.xvit_attn_bwd(p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(o), _ptr(d_o), N * d, d, _ptr(lse), _ptr(ws), need,
-                                   g, g + 2 * d, g + 4 * d, B, H, N, dh, scale, float(dropout[0]), int(dropout[1]), _stream()), "xvit_attn_bwd")
+    _call("xvit_attn_bwd", "attn_bwd", 10.0 * B * H * N * N * dh, "flop", p, p + 2 * d, p + 4 * d, N * ld, ld, _ptr(o), _ptr(d_o), N * d, d, _ptr(lse),
+          _ptr(ws), need, g, g + 2 * d, g + 4 * d, B, H, N, dh, scale, *_drop(dropout))
     return dqkv
 
 
-def cls_xattn_fwd(q, kv, B, N, H, scale, dropout=(0.0, 0), want_f32=False):
+def cls_xattn_fwd(q, kv, B, N, H, scale, dropout=None, want_f32=False):
     """q bf16 or fp32 [B, d]; kv bf16 [B*N, 2d] (k | v) -> (o bf16 [B, d], p fp32 [B, H, N]) (+ o fp32 with want_f32)."""
-    d = q.shape[1]
-    o = torch.empty(B, d, dtype=torch.bfloat16, device=q.device)
-    of = torch.empty(B, d, dtype=torch.float32, device=q.device) if want_f32 else None
-    p = torch.empty(B, H, N, dtype=torch.float32, device=q.device)
+    d, dev = q.shape[1], q.device
+    o = _b16(B, d, device=dev)
+    of = _f32(B, d, device=dev) if want_f32 else None
+    p = _f32(B, H, N, device=dev)
     ld = _rows2d(kv)
     kp = kv.data_ptr()
     qb, qf = (q, None) if q.dtype == torch.bfloat16 else (None, q)
-    _run("cls_xattn_fwd", B * N * 2.0 * d * 2, "byte",
-         lambda: _lib.load().xvit_cls_xattn_fwd(_ptr(qb), _rows2d(qb) if qb is not None else 0, _ptr(qf), _rows2d(qf) if qf is not None else 0,
-                                                kp, kp + 2 * d, N * ld, ld, _ptr(o), d, _ptr(of), d, _ptr(p), B, H, N, d // H, scale,
-                                                float(dropout[0]), int(dropout[1]), _stream()), "xvit_cls_xattn_fwd")
+    _call("xvit_cls_xattn_fwd", "cls_xattn_fwd", B * N * 2.0 * d * 2, "byte", _ptr(qb), _ld(qb), _ptr(qf), _ld(qf),
+          kp, kp + 2 * d, N * ld, ld, _ptr(o), d, _ptr(of), d, _ptr(p), B, H, N, d // H, scale, *_drop(dropout))
     return (o, p, of) if want_f32 else (o, p)
 
 
-def cls_xattn_bwd(q, kv, p, d_o, B, N, H, scale, dropout=(0.0, 0), low_rank=False):
+def cls_xattn_bwd(q, kv, p, d_o, B, N, H, scale, dropout=None, low_rank=False):
     """-> (dq fp32 [B, d], dkv bf16 [B*N, 2d])   or, low_rank: (dq, coef fp32 [B, N, 2H]) with dk[n] = coef[.., h] q_h and
     dv[n] = coef[.., H + h] dO_h (include/xvit.h): the input of xattn_kv_dgrad."""
     d = q.shape[1]
-    dq = torch.empty(B, d, dtype=torch.float32, device=q.device)
+    dq = _f32(B, d, device=q.device)
     ld = _rows2d(kv)
     kp = kv.data_ptr()
     if low_rank:
-        out = torch.empty(B, N, 2 * H, dtype=torch.float32, device=q.device)
+        out = _f32(B, N, 2 * H, device=q.device)
         gk = gv = None
         work = B * N * 2.0 * d * 2
     else:
@@ -391,11 +410,14 @@ def cls_xattn_bwd(q, kv, p, d_o, B, N, H, scale, dropout=(0.0, 0), low_rank=Fals
         assert out.stride(0) == ld
         gk, gv = out.data_ptr(), out.data_ptr() + 2 * d
         work = B * N * 2.0 * d * 2 * 2
-    _run("cls_xattn_bwd", work, "byte",
-         lambda: _lib.load().xvit_cls_xattn_bwd(_ptr(q), _rows2d(q), kp, kp + 2 * d, N * ld, ld, _ptr(p), _ptr(d_o), _rows2d(d_o), _ptr(dq), d,
-                                                gk, gv, _ptr(out) if low_rank else None, B, H, N, d // H, scale, float(dropout[0]), int(dropout[1]), _stream()),
-         "xvit_cls_xattn_bwd")
+    _call("xvit_cls_xattn_bwd", "cls_xattn_bwd", work, "byte", _ptr(q), _rows2d(q), kp, kp + 2 * d, N * ld, ld, _ptr(p), _ptr(d_o), _rows2d(d_o), _ptr(dq), d,
+          gk, gv, _ptr(out) if low_rank else None, B, H, N, d // H, scale, *_drop(dropout))
     return dq, out
+
+
+def _st0(t):
+    """Stride of dim 0 of an optional tensor (0 for None)."""
+    return t.stride(0) if t is not None else 0
 
 
 def head_rows(x, W, out, H, out_bf16=None):
@@ -406,10 +428,8 @@ def head_rows(x, W, out, H, out_bf16=None):
     assert x.dtype == torch.float32 and W.dtype == torch.float32 and out.dtype == torch.float32 and out.shape[-1] == d and out.stride(-1) == 1
     ob = out_bf16
     assert ob is None or (ob.dtype == torch.bfloat16 and ob.stride(-1) == 1)
-    _run("head_linear", 2.0 * B * d * 64, "flop",
-         lambda: _lib.load().xvit_head_rows(_ptr(x), _rows2d(x), _ptr(W), _rows2d(W), _ptr(out), out.stride(0), out.stride(1), _ptr(ob),
-                                            ob.stride(0) if ob is not None else 0, ob.stride(1) if ob is not None else 0, ob.shape[1] if ob is not None else 0,
-                                            B, H, d, _stream()), "xvit_head_rows")
+    _call("xvit_head_rows", "head_linear", 2.0 * B * d * 64, "flop", _ptr(x), _rows2d(x), _ptr(W), _rows2d(W), _ptr(out), out.stride(0), out.stride(1),
+          _ptr(ob), *((ob.stride(0), ob.stride(1), ob.shape[1]) if ob is not None else (0, 0, 0)), B, H, d)
     return out
 
 
@@ -418,12 +438,10 @@ def head_cols(t, W, H, row_scale=None, bias=None, want_bf16=False, bias_scale=No
     B, _, d = t.shape
     assert t.dtype == torch.float32 and t.stride(2) == 1 and W.dtype == torch.float32
     assert bias_scale is None or (bias_scale.dtype == torch.float32 and bias_scale.stride(-1) == 1 and bias_scale.shape == (B, H))
-    out = torch.empty(B, d, dtype=torch.float32, device=t.device)
-    ob = torch.empty(B, d, dtype=torch.bfloat16, device=t.device) if want_bf16 else None
-    _run("head_linear", 2.0 * B * d * 64, "flop",
-         lambda: _lib.load().xvit_head_cols(_ptr(t), t.stride(0), t.stride(1), _ptr(W), _rows2d(W), _ptr(row_scale), row_scale.stride(0) if row_scale is not None else 0,
-                                            _ptr(bias), _ptr(bias_scale), bias_scale.stride(0) if bias_scale is not None else 0, _ptr(out), d, _ptr(ob), d, B, H, d,
-                                            _stream()), "xvit_head_cols")
+    out = _f32(B, d, device=t.device)
+    ob = _b16(B, d, device=t.device) if want_bf16 else None
+    _call("xvit_head_cols", "head_linear", 2.0 * B * d * 64, "flop", _ptr(t), t.stride(0), t.stride(1), _ptr(W), _rows2d(W), _ptr(row_scale), _st0(row_scale),
+          _ptr(bias), _ptr(bias_scale), _st0(bias_scale), _ptr(out), d, _ptr(ob), d, B, H, d)
     return out, ob
 
 
@@ -431,11 +449,10 @@ def head_wgrad(x, t, H, row_scale=None, out=None):
     """dW[64h+e, :] = sum_b x[b, 64h+e] row_scale[b, h] t[b, h, :] (xvit_head_wgrad) -> fp32 [d, d]."""
     B, d = x.shape
     assert x.dtype == torch.float32 and t.dtype == torch.float32 and t.stride(2) == 1 and t.shape[0] == B and t.shape[2] == d
-    dW = out if out is not None else torch.empty(d, d, dtype=torch.float32, device=x.device)
+    dW = out if out is not None else _f32(d, d, device=x.device)
     assert dW.shape == (d, d) and dW.is_contiguous() and dW.dtype == torch.float32
-    _run("head_linear", 2.0 * B * d * 64, "flop",
-         lambda: _lib.load().xvit_head_wgrad(_ptr(x), _rows2d(x), _ptr(t), t.stride(0), t.stride(1), _ptr(row_scale), row_scale.stride(0) if row_scale is not None else 0,
-                                             _ptr(dW), d, B, H, d, _stream()), "xvit_head_wgrad")
+    _call("xvit_head_wgrad", "head_linear", 2.0 * B * d * 64, "flop", _ptr(x), _rows2d(x), _ptr(t), t.stride(0), t.stride(1), _ptr(row_scale), _st0(row_scale),
+          _ptr(dW), d, B, H, d)
     return dW
 
 
@@ -444,13 +461,12 @@ def cls_softmax_fwd(s, H, scale, dropout=None):
     dropout = (p, seed) on the probabilities (model_cross.py:97): -> (e, stat fp32 [3, B, H] = (rz, rz / (1 - p), rz / (1 - p) * sum_n e_kept), e_kept bf16 [B, N, 16])."""
     B, N, ld = s.shape
     assert s.dtype == torch.float32 and s.is_contiguous() and ld == 16
-    e = torch.empty(B, N, 16, dtype=torch.bfloat16, device=s.device)
-    drop = dropout is not None and dropout[0] > 0.0
-    rz = torch.empty((3, B, H) if drop else (B, H), dtype=torch.float32, device=s.device)
+    e = _b16(B, N, 16, device=s.device)
+    p, seed = _drop(dropout)
+    drop = p > 0.0
+    rz = _f32(*((3, B, H) if drop else (B, H)), device=s.device)
     em = torch.empty_like(e) if drop else None
-    _run("cls_softmax", B * N * 16 * 6.0, "byte",
-         lambda: _lib.load().xvit_cls_softmax_fwd(_ptr(s), ld, _ptr(e), 16, _ptr(rz), B, H, N, scale, _ptr(em), float(dropout[0]) if drop else 0.0,
-                                                  int(dropout[1]) if drop else 0, _stream()), "xvit_cls_softmax_fwd")
+    _call("xvit_cls_softmax_fwd", "cls_softmax", B * N * 16 * 6.0, "byte", _ptr(s), ld, _ptr(e), 16, _ptr(rz), B, H, N, scale, _ptr(em), p, seed)
     return (e, rz, em) if drop else (e, rz)
 
 
@@ -458,8 +474,8 @@ def head_bias_grad(x, w, H):
     """out[j] = sum_b x[b, j] w[b, j // 64] (xvit_head_bias_grad): bv's gradient when the weights in front of it are w, not one."""
     B, d = x.shape
     assert x.dtype == torch.float32 and w.dtype == torch.float32 and w.shape == (B, H) and x.stride(1) == 1 and w.stride(1) == 1
-    out = torch.empty(d, dtype=torch.float32, device=x.device)
-    _run("head_linear", 2.0 * B * d, "flop", lambda: _lib.load().xvit_head_bias_grad(_ptr(x), x.stride(0), _ptr(w), w.stride(0), _ptr(out), B, H, d, _stream()), "xvit_head_bias_grad")
+    out = _f32(d, device=x.device)
+    _call("xvit_head_bias_grad", "head_linear", 2.0 * B * d, "flop", _ptr(x), x.stride(0), _ptr(w), w.stride(0), _ptr(out), B, H, d)
     return out
 
 
@@ -467,23 +483,20 @@ def cls_softmax_bwd(e, rz, dp, H, scale, dropout=None):
     """-> (coef fp32 [B, N, 2H] = (ds | p'), ds bf16 [B, N, 16]); p = e rz, ds = scale p (dp~ - sum_n p dp~); with dropout = (p, seed) dp~ = m dp / (1 - p) and
     p' = m p / (1 - p) (the forward's mask, regenerated), else dp~ = dp, p' = p.  rz: fp32 [B, H] (row 0 of the forward's stat block under dropout)."""
     B, N, _ = e.shape
-    drop = dropout is not None and dropout[0] > 0.0
     assert rz.shape == (B, H) and rz.is_contiguous()
     assert e.dtype == torch.bfloat16 and e.is_contiguous() and dp.dtype == torch.float32 and dp.is_contiguous() and dp.shape == (B, N, 16)
-    coef = torch.empty(B, N, 2 * H, dtype=torch.float32, device=e.device)
-    dsb = torch.empty(B, N, 16, dtype=torch.bfloat16, device=e.device)
-    _run("cls_softmax", B * N * (16 * 8.0 + 2 * H * 4.0), "byte",
-         lambda: _lib.load().xvit_cls_softmax_bwd(_ptr(e), 16, _ptr(rz), _ptr(dp), 16, _ptr(coef), _ptr(dsb), 16, B, H, N, scale, float(dropout[0]) if drop else 0.0,
-                                                  int(dropout[1]) if drop else 0, _stream()), "xvit_cls_softmax_bwd")
+    coef = _f32(B, N, 2 * H, device=e.device)
+    dsb = _b16(B, N, 16, device=e.device)
+    _call("xvit_cls_softmax_bwd", "cls_softmax", B * N * (16 * 8.0 + 2 * H * 4.0), "byte", _ptr(e), 16, _ptr(rz), _ptr(dp), 16, _ptr(coef), _ptr(dsb), 16,
+          B, H, N, scale, *_drop(dropout))
     return coef, dsb
 
 
 def xattn_kv_dgrad(coef, R, B, N, H, d):
     """dhn[b, n, :] (bf16) = sum_j coef[b, n, j] R[j, b, :] (xvit_xattn_kv_dgrad); coef fp32 [B, N, 2H], R fp32 [2H, B, d]."""
     assert coef.is_contiguous() and R.is_contiguous() and R.shape == (2 * H, B, d)
-    dhn = torch.empty(B * N, d, dtype=torch.bfloat16, device=coef.device)
-    _run("xattn_kv_dgrad", B * N * d * 2.0 + B * N * 2 * H * 4.0, "byte",
-         lambda: _lib.load().xvit_xattn_kv_dgrad(_ptr(coef), _ptr(R), _ptr(dhn), d, B, H, N, d, _stream()), "xvit_xattn_kv_dgrad")
+    dhn = _b16(B * N, d, device=coef.device)
+    _call("xvit_xattn_kv_dgrad", "xattn_kv_dgrad", B * N * d * 2.0 + B * N * 2 * H * 4.0, "byte", _ptr(coef), _ptr(R), _ptr(dhn), d, B, H, N, d)
     return dhn
 
 
@@ -512,9 +525,8 @@ def patchify(img, patch, pad_cls_row=False, concat=False):
     dp, hp, wp = patch
     P, pd = _patch_counts(img.shape, patch)
     place, lead = _patch_place(B, M, P, pad_cls_row, concat)
-    out = torch.empty(*lead, pd, dtype=torch.bfloat16, device=img.device)
-    _run("patchify", img.numel() * (img.element_size() + 2.0), "byte",
-         lambda: _lib.load().xvit_patchify(_ptr(img), _dt(img), _ptr(out), B, M, D, H, W, dp, hp, wp, *place, _stream()), "xvit_patchify")
+    out = _b16(*lead, pd, device=img.device)
+    _call("xvit_patchify", "patchify", img.numel() * (img.element_size() + 2.0), "byte", _ptr(img), _dt(img), _ptr(out), B, M, D, H, W, dp, hp, wp, *place)
     return out
 
 
@@ -539,7 +551,7 @@ def patch_embed_supported(img, patch, d, cls_rows=1):
         return False
     if img.dim() != 6 or img.shape[2] != 1 or img.dtype != torch.bfloat16 or not img.is_contiguous() or not img.is_cuda:
         return False
-    return _lib.load().xvit_patch_embed_supported(C.byref(_patch_geom(img, patch, cls_rows)), int(d)) == 1
+    return _L.xvit_patch_embed_supported(C.byref(_patch_geom(img, patch, cls_rows)), int(d)) == 1
 
 
 def patch_embed_fwd(img, patch, w_b, bias, pos, cls_rows=1):
@@ -550,12 +562,9 @@ def patch_embed_fwd(img, patch, w_b, bias, pos, cls_rows=1):
     P, pd = _patch_counts(img.shape, patch)
     d = w_b.shape[0]
     assert w_b.dtype == torch.bfloat16 and w_b.shape[1] == pd and (pos is None or pos.shape == (cls_rows + P, d))
-    rows = M * B * (cls_rows + P)
-    x = torch.empty(rows, d, dtype=torch.float32, device=img.device)
-    _run("gemm_big_nt", 2.0 * M * B * P * d * pd, "flop",
-         lambda: _lib.load().xvit_patch_embed_fwd(_ptr(img), C.byref(g), _ptr(w_b), w_b.stride(0), _ptr(bias) if bias is not None else None,
-                                                  _ptr(pos) if pos is not None else None, pos.stride(0) if pos is not None else 0, _ptr(x), x.stride(0), d, _stream()),
-         "xvit_patch_embed_fwd")
+    x = _f32(M * B * (cls_rows + P), d, device=img.device)
+    _call("xvit_patch_embed_fwd", "gemm_big_nt", 2.0 * M * B * P * d * pd, "flop", _ptr(img), C.byref(g), _ptr(w_b), w_b.stride(0), _ptr(bias),
+          _ptr(pos), _st0(pos), _ptr(x), x.stride(0), d)
     return x
 
 
@@ -566,13 +575,12 @@ def patch_embed_wgrad(img, patch, dx_b, cls_rows=1, out=None):
     P, pd = _patch_counts(img.shape, patch)
     d = dx_b.shape[1]
     assert dx_b.dtype == torch.bfloat16 and dx_b.shape[0] == M * B * (cls_rows + P) and dx_b.is_contiguous()
-    need = _lib.load().xvit_patch_embed_wgrad_workspace_bytes(C.byref(g), d)
+    need = _L.xvit_patch_embed_wgrad_workspace_bytes(C.byref(g), d)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=img.device)
-    dW = out if out is not None else torch.empty(d, pd, dtype=torch.float32, device=img.device)
+    dW = out if out is not None else _f32(d, pd, device=img.device)
     assert dW.shape == (d, pd) and dW.is_contiguous() and dW.dtype == torch.float32
-    _run("gemm_big_tn+splitk", 2.0 * M * B * P * d * pd, "flop",
-         lambda: _lib.load().xvit_patch_embed_wgrad(_ptr(img), C.byref(g), _ptr(dx_b), dx_b.stride(0), _ptr(dW), dW.stride(0), d, _ptr(ws), need, _stream()),
-         "xvit_patch_embed_wgrad")
+    _call("xvit_patch_embed_wgrad", "gemm_big_tn+splitk", 2.0 * M * B * P * d * pd, "flop", _ptr(img), C.byref(g), _ptr(dx_b), dx_b.stride(0),
+          _ptr(dW), dW.stride(0), d, _ptr(ws), need)
     return dW
 
 
@@ -583,7 +591,7 @@ def patch_embed_dgrad_supported(shape, patch, d, cls_rows=1):
         return False
     if len(shape) != 6 or shape[2] != 1:
         return False
-    return _lib.load().xvit_patch_embed_dgrad_supported(C.byref(_patch_geom_of(tuple(shape), patch, cls_rows)), int(d)) == 1
+    return _L.xvit_patch_embed_dgrad_supported(C.byref(_patch_geom_of(tuple(shape), patch, cls_rows)), int(d)) == 1
 
 
 def patch_embed_dgrad(dx_b, w_b, shape, patch, dtype=torch.float32, cls_rows=1, out=None):
@@ -598,9 +606,8 @@ def patch_embed_dgrad(dx_b, w_b, shape, patch, dtype=torch.float32, cls_rows=1, 
     assert w_b.dtype == torch.bfloat16 and w_b.shape == (d, pd) and w_b.stride(1) == 1
     out = out if out is not None else torch.empty(shape, dtype=dtype, device=dx_b.device)
     assert tuple(out.shape) == shape and out.is_contiguous()
-    _run("patch_embed_dgrad", 2.0 * M * B * P * d * pd, "flop",
-         lambda: _lib.load().xvit_patch_embed_dgrad(_ptr(dx_b), dx_b.stride(0), _ptr(w_b), w_b.stride(0), C.byref(g), d, _ptr(out), _dt(out), _stream()),
-         "xvit_patch_embed_dgrad")
+    _call("xvit_patch_embed_dgrad", "patch_embed_dgrad", 2.0 * M * B * P * d * pd, "flop", _ptr(dx_b), dx_b.stride(0), _ptr(w_b), w_b.stride(0), C.byref(g), d,
+          _ptr(out), _dt(out))
     return out
 
 
@@ -613,17 +620,16 @@ def unpatchify(patches, out, patch, pad_cls_row=False, concat=False):
     P, pd = _patch_counts(out.shape, patch)
     place, lead = _patch_place(B, M, P, pad_cls_row, concat)
     assert patches.dtype == torch.float32 and patches.is_contiguous() and patches.numel() == math.prod(lead) * pd
-    _run("unpatchify", out.numel() * (4.0 + out.element_size()), "byte",
-         lambda: _lib.load().xvit_unpatchify(_ptr(patches), _ptr(out), _dt(out), B, M, D, H, W, dp, hp, wp, *place[:3], _stream()), "xvit_unpatchify")
+    _call("xvit_unpatchify", "unpatchify", out.numel() * (4.0 + out.element_size()), "byte", _ptr(patches), _ptr(out), _dt(out), B, M, D, H, W, dp, hp, wp, *place[:3])
     return out
 
 
 def cls_row_fwd(cls, pos, x, MB, N, d):
-    _lib.check(_lib.load().xvit_cls_row_fwd(_ptr(cls), _ptr(pos), _ptr(x), MB, N, d, _stream()), "xvit_cls_row_fwd")
+    _launch("xvit_cls_row_fwd", _ptr(cls), _ptr(pos), _ptr(x), MB, N, d)
 
 
 def embed_bwd(dx, dpos, dcls, MB, N, d):
-    _run("embed_bwd", float(MB) * N * d * 4, "byte", lambda: _lib.load().xvit_embed_bwd(_ptr(dx), _ptr(dpos), _ptr(dcls), MB, N, d, _stream()), "xvit_embed_bwd")
+    _call("xvit_embed_bwd", "embed_bwd", float(MB) * N * d * 4, "byte", _ptr(dx), _ptr(dpos), _ptr(dcls), MB, N, d)
 
 
 def _i32c(t, shape, what):
@@ -638,8 +644,7 @@ def token_select_draw(keep_idx, slot, B, shared, seed):
     S, K = keep_idx.shape
     P = slot.shape[1]
     _i32c(keep_idx, (S, K), "keep_idx"), _i32c(slot, (S, P), "slot")
-    _run("token_select_draw", float(S) * (P + K) * 4, "byte",
-         lambda: _lib.load().xvit_token_select_draw(_ptr(keep_idx), _ptr(slot), S, int(B), P, K, int(bool(shared)), int(seed), _stream()), "xvit_token_select_draw")
+    _call("xvit_token_select_draw", "token_select_draw", float(S) * (P + K) * 4, "byte", _ptr(keep_idx), _ptr(slot), S, int(B), P, K, int(bool(shared)), int(seed))
     return keep_idx, slot
 
 
@@ -652,8 +657,8 @@ def patch_occupancy(img, patch, above, out=None):
     P = _patch_counts(img.shape, patch)[0]
     out = out if out is not None else torch.empty(M * B, P, dtype=torch.int32, device=img.device)
     _i32c(out, (M * B, P), "out")
-    _run("patch_occupancy", img.numel() * float(img.element_size()) + M * B * P * 4.0, "byte",
-         lambda: _lib.load().xvit_patch_occupancy(_ptr(img), _dt(img), _ptr(out), B, M, D, H, W, dp, hp, wp, float(above), _stream()), "xvit_patch_occupancy")
+    _call("xvit_patch_occupancy", "patch_occupancy", img.numel() * float(img.element_size()) + M * B * P * 4.0, "byte",
+          _ptr(img), _dt(img), _ptr(out), B, M, D, H, W, dp, hp, wp, float(above))
     return out
 
 
@@ -667,9 +672,8 @@ def token_select_ranked(occ, keep_idx, slot, B, shared, mode, min_count, seed, n
     _i32c(occ, (S, P), "occ"), _i32c(keep_idx, (S, K), "keep_idx"), _i32c(slot, (S, P), "slot")
     if n_fg is not None:
         _i32c(n_fg, (S,), "n_fg")
-    _run("token_select_ranked", float(S) * (2 * P + K) * 4, "byte",
-         lambda: _lib.load().xvit_token_select_ranked(_ptr(occ), _ptr(keep_idx), _ptr(slot), _ptr(n_fg), S, int(B), P, K, int(bool(shared)), int(mode),
-                                                      int(min_count), int(seed), _stream()), "xvit_token_select_ranked")
+    _call("xvit_token_select_ranked", "token_select_ranked", float(S) * (2 * P + K) * 4, "byte", _ptr(occ), _ptr(keep_idx), _ptr(slot), _ptr(n_fg),
+          S, int(B), P, K, int(bool(shared)), int(mode), int(min_count), int(seed))
     return keep_idx, slot
 
 
@@ -682,10 +686,10 @@ def patchify_select(img, patch, keep_idx, out=None):
     pd = _patch_counts(img.shape, patch)[1]
     K = keep_idx.shape[1]
     _i32c(keep_idx, (M * B, K), "keep_idx")
-    out = out if out is not None else torch.empty(M, B * (K + 1), pd, dtype=torch.bfloat16, device=img.device)
+    out = out if out is not None else _b16(M, B * (K + 1), pd, device=img.device)
     assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, B * (K + 1), pd)
-    _run("patchify_select", M * B * K * pd * (img.element_size() + 2.0), "byte",
-         lambda: _lib.load().xvit_patchify_select(_ptr(img), _dt(img), _ptr(out), _ptr(keep_idx), B, M, D, H, W, dp, hp, wp, K, _stream()), "xvit_patchify_select")
+    _call("xvit_patchify_select", "patchify_select", M * B * K * pd * (img.element_size() + 2.0), "byte",
+          _ptr(img), _dt(img), _ptr(out), _ptr(keep_idx), B, M, D, H, W, dp, hp, wp, K)
     return out
 
 
@@ -696,8 +700,7 @@ def embed_select_fwd(x, cls, pos, keep_idx):
     assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] == S * (K + 1)
     assert cls.dtype == torch.float32 and cls.numel() == d and cls.is_contiguous() and pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape[1] == d
     _i32c(keep_idx, (S, K), "keep_idx")
-    _run("embed_select_fwd", float(x.numel()) * 12, "byte",
-         lambda: _lib.load().xvit_embed_select_fwd(_ptr(x), _ptr(cls), _ptr(pos), _ptr(keep_idx), S, K, d, _stream()), "xvit_embed_select_fwd")
+    _call("xvit_embed_select_fwd", "embed_select_fwd", float(x.numel()) * 12, "byte", _ptr(x), _ptr(cls), _ptr(pos), _ptr(keep_idx), S, K, d)
     return x
 
 
@@ -709,8 +712,7 @@ def embed_select_bwd(dx, slot, dpos, dcls, K):
     assert dx.dtype == torch.float32 and dx.is_contiguous() and dx.shape[0] == S * (K + 1)
     assert dpos.dtype == torch.float32 and dpos.is_contiguous() and tuple(dpos.shape) == (P + 1, d) and dcls.dtype == torch.float32 and dcls.numel() == d
     _i32c(slot, (S, P), "slot")
-    _run("embed_select_bwd", float(dx.numel()) * 4, "byte",
-         lambda: _lib.load().xvit_embed_select_bwd(_ptr(dx), _ptr(slot), _ptr(dpos), _ptr(dcls), S, P, int(K), d, _stream()), "xvit_embed_select_bwd")
+    _call("xvit_embed_select_bwd", "embed_select_bwd", float(dx.numel()) * 4, "byte", _ptr(dx), _ptr(slot), _ptr(dpos), _ptr(dcls), S, P, int(K), d)
 
 
 def token_select_complement(slot, K, drop_idx=None, mslot=None):
@@ -722,8 +724,7 @@ def token_select_complement(slot, K, drop_idx=None, mslot=None):
     drop_idx = drop_idx if drop_idx is not None else torch.empty(S, max(P - K, 0), dtype=torch.int32, device=slot.device)
     mslot = mslot if mslot is not None else torch.empty(S, P, dtype=torch.int32, device=slot.device)
     _i32c(drop_idx, (S, P - K), "drop_idx"), _i32c(mslot, (S, P), "mslot")
-    _run("token_select_complement", float(S) * (3 * P - K) * 4, "byte",
-         lambda: _lib.load().xvit_token_select_complement(_ptr(slot), _ptr(drop_idx), _ptr(mslot), S, P, K, _stream()), "xvit_token_select_complement")
+    _call("xvit_token_select_complement", "token_select_complement", float(S) * (3 * P - K) * 4, "byte", _ptr(slot), _ptr(drop_idx), _ptr(mslot), S, P, K)
     return drop_idx, mslot
 
 
@@ -739,11 +740,10 @@ def mae_unshuffle_fwd(xe, mask_token, dpos, dmod, slot, out=None):
     P, M = slot.shape[1], dmod.shape[0]
     assert S % M == 0, f"mae_unshuffle_fwd: {S} sequences do not divide into {M} modalities"
     _f32v(xe, (S, K1, dd), "xe"), _f32v(mask_token, (dd,), "mask_token"), _f32v(dpos, (P + 1, dd), "dpos"), _f32v(dmod, (M, dd), "dmod"), _i32c(slot, (S, P), "slot")
-    y = out if out is not None else torch.empty(S, P + 1, dd, dtype=torch.float32, device=xe.device)
+    y = out if out is not None else _f32(S, P + 1, dd, device=xe.device)
     _f32v(y, (S, P + 1, dd), "y")
-    _run("mae_unshuffle_fwd", float(S) * (P + K1) * dd * 4, "byte",
-         lambda: _lib.load().xvit_mae_unshuffle_fwd(_ptr(xe), _ptr(mask_token), _ptr(dpos), _ptr(dmod), _ptr(slot), _ptr(y), S, S // M, P, K1 - 1, dd, _stream()),
-         "xvit_mae_unshuffle_fwd")
+    _call("xvit_mae_unshuffle_fwd", "mae_unshuffle_fwd", float(S) * (P + K1) * dd * 4, "byte",
+          _ptr(xe), _ptr(mask_token), _ptr(dpos), _ptr(dmod), _ptr(slot), _ptr(y), S, S // M, P, K1 - 1, dd)
     return y
 
 
@@ -755,12 +755,11 @@ def mae_unshuffle_bwd(dy, keep_idx, slot, M, out=None):
     _f32v(dy, (S, P1, dd), "dy"), _i32c(keep_idx, (S, K), "keep_idx"), _i32c(slot, (S, P1 - 1), "slot")
     assert S % M == 0
     if out is None:
-        out = tuple(torch.empty(*shape, dtype=torch.float32, device=dy.device) for shape in ((S, K + 1, dd), (dd,), (M, P1, dd), (S, dd)))
+        out = tuple(_f32(*shape, device=dy.device) for shape in ((S, K + 1, dd), (dd,), (M, P1, dd), (S, dd)))
     dxe, dmask, ddpos_m, part = out
     _f32v(dxe, (S, K + 1, dd), "dxe"), _f32v(dmask, (dd,), "dmask_token"), _f32v(ddpos_m, (M, P1, dd), "ddpos_m"), _f32v(part, (S, dd), "scratch")
-    _run("mae_unshuffle_bwd", float(S) * (2 * P1 + K + 1) * dd * 4, "byte",
-         lambda: _lib.load().xvit_mae_unshuffle_bwd(_ptr(dy), _ptr(keep_idx), _ptr(slot), _ptr(dxe), _ptr(dmask), _ptr(ddpos_m), _ptr(part), S, S // M, P1 - 1, K, dd, _stream()),
-         "xvit_mae_unshuffle_bwd")
+    _call("xvit_mae_unshuffle_bwd", "mae_unshuffle_bwd", float(S) * (2 * P1 + K + 1) * dd * 4, "byte",
+          _ptr(dy), _ptr(keep_idx), _ptr(slot), _ptr(dxe), _ptr(dmask), _ptr(ddpos_m), _ptr(part), S, S // M, P1 - 1, K, dd)
     return dxe, dmask, ddpos_m
 
 
@@ -769,10 +768,9 @@ def token_rows_gather(x, drop_idx, out=None):
     S, P1, dd = x.shape
     Rm = drop_idx.shape[1]
     _f32v(x, (S, P1, dd), "x"), _i32c(drop_idx, (S, Rm), "drop_idx")
-    g = out if out is not None else torch.empty(S * Rm, dd, dtype=torch.float32, device=x.device)
+    g = out if out is not None else _f32(S * Rm, dd, device=x.device)
     _f32v(g, (S * Rm, dd), "g")
-    _run("token_rows_gather", float(S) * Rm * dd * 8, "byte",
-         lambda: _lib.load().xvit_token_rows_gather(_ptr(x), _ptr(drop_idx), _ptr(g), S, P1 - 1, Rm, dd, _stream()), "xvit_token_rows_gather")
+    _call("xvit_token_rows_gather", "token_rows_gather", float(S) * Rm * dd * 8, "byte", _ptr(x), _ptr(drop_idx), _ptr(g), S, P1 - 1, Rm, dd)
     return g
 
 
@@ -782,10 +780,9 @@ def token_rows_scatter(dg, mslot, Rm, out=None):
     S, P = mslot.shape
     dd = dg.shape[1]
     _f32v(dg, (S * Rm, dd), "dg"), _i32c(mslot, (S, P), "mslot")
-    dx = out if out is not None else torch.empty(S, P + 1, dd, dtype=torch.float32, device=dg.device)
+    dx = out if out is not None else _f32(S, P + 1, dd, device=dg.device)
     _f32v(dx, (S, P + 1, dd), "dx")
-    _run("token_rows_scatter", float(S) * (P + 1 + Rm) * dd * 4, "byte",
-         lambda: _lib.load().xvit_token_rows_scatter(_ptr(dg), _ptr(mslot), _ptr(dx), S, P, int(Rm), dd, _stream()), "xvit_token_rows_scatter")
+    _call("xvit_token_rows_scatter", "token_rows_scatter", float(S) * (P + 1 + Rm) * dd * 4, "byte", _ptr(dg), _ptr(mslot), _ptr(dx), S, P, int(Rm), dd)
     return dx
 
 
@@ -805,14 +802,13 @@ def mae_loss_fwd(pred, drop_idx, img, patch, norm_pix=True, out=None):
     stored) -> (loss fp32 [1], loss_seq fp32 [S], row_loss fp32 [S*Rm], stats fp32 [S*Rm, 2] = (mean, rstd)); out: that tuple to write into."""
     geom = _mae_loss_geom(pred, drop_idx, img, patch)
     B, M, Rm = geom[0], geom[1], geom[8]
-    rows, dev = M * B * Rm, pred.device
+    rows = M * B * Rm
     if out is None:
-        out = tuple(torch.empty(*shape, dtype=torch.float32, device=dev) for shape in ((1,), (M * B,), (rows,), (rows, 2)))
+        out = tuple(_f32(*shape, device=pred.device) for shape in ((1,), (M * B,), (rows,), (rows, 2)))
     loss, loss_seq, row_loss, stats = out
     _f32v(loss, (1,), "loss"), _f32v(loss_seq, (M * B,), "loss_seq"), _f32v(row_loss, (rows,), "row_loss"), _f32v(stats, (rows, 2), "stats")
-    _run("mae_loss_fwd", float(pred.numel()) * (img.element_size() + pred.element_size()), "byte",
-         lambda: _lib.load().xvit_mae_loss_fwd(_ptr(pred), _dt(pred), _ptr(drop_idx), _ptr(img), _dt(img), int(bool(norm_pix)), _ptr(stats), _ptr(row_loss),
-                                               _ptr(loss_seq), _ptr(loss), *geom, _stream()), "xvit_mae_loss_fwd")
+    _call("xvit_mae_loss_fwd", "mae_loss_fwd", float(pred.numel()) * (img.element_size() + pred.element_size()), "byte",
+          _ptr(pred), _dt(pred), _ptr(drop_idx), _ptr(img), _dt(img), int(bool(norm_pix)), _ptr(stats), _ptr(row_loss), _ptr(loss_seq), _ptr(loss), *geom)
     return loss, loss_seq, row_loss, stats
 
 
@@ -823,18 +819,17 @@ def mae_loss_bwd(pred, drop_idx, img, patch, stats, g, out=None):
     assert g.dtype == torch.float32 and g.numel() == 1
     dpred = out if out is not None else torch.empty_like(pred)
     assert dpred.dtype == pred.dtype and dpred.shape == pred.shape and dpred.is_contiguous()
-    _run("mae_loss_bwd", float(pred.numel()) * (img.element_size() + 2 * pred.element_size()), "byte",
-         lambda: _lib.load().xvit_mae_loss_bwd(_ptr(pred), _dt(pred), _ptr(drop_idx), _ptr(img), _dt(img), _ptr(stats), _ptr(g), _ptr(dpred), *geom, _stream()),
-         "xvit_mae_loss_bwd")
+    _call("xvit_mae_loss_bwd", "mae_loss_bwd", float(pred.numel()) * (img.element_size() + 2 * pred.element_size()), "byte",
+          _ptr(pred), _dt(pred), _ptr(drop_idx), _ptr(img), _dt(img), _ptr(stats), _ptr(g), _ptr(dpred), *geom)
     return dpred
 
 
 def cast_bf16(src, out=None):
     """fp32 -> bf16 (contiguous)."""
     assert src.dtype == torch.float32 and src.is_contiguous()
-    out = out if out is not None else torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
+    out = out if out is not None else _b16(src.shape, device=src.device)
     assert out.is_contiguous() and out.numel() == src.numel()
-    _run("cast_f32_bf16", src.numel() * 6.0, "byte", lambda: _lib.load().xvit_cast_f32_bf16(_ptr(src), _ptr(out), src.numel(), _stream()), "xvit_cast_f32_bf16")
+    _call("xvit_cast_f32_bf16", "cast_f32_bf16", src.numel() * 6.0, "byte", _ptr(src), _ptr(out), src.numel())
     return out
 
 
@@ -843,7 +838,7 @@ def grad_pack_bf16(segments, dst, scale=1.0):
     (xvit_grad_pack_bf16): the bf16 wire buffer of a reducer bucket.  src: contiguous fp32, 16-byte aligned; off: a multiple of 64;
     dst: contiguous bf16.  One launch per XVIT_GRAD_PACK_MAX_SEGMENTS segments."""
     assert dst.dtype == torch.bfloat16 and dst.is_contiguous()
-    lib, base, m = _lib.load(), _ptr(dst), _lib.GRAD_PACK_MAX_SEGMENTS
+    base, m = _ptr(dst), _lib.GRAD_PACK_MAX_SEGMENTS
     for i in range(0, len(segments), m):
         part = segments[i:i + m]
         table = (_lib.GradSegment * len(part))()
@@ -851,14 +846,14 @@ def grad_pack_bf16(segments, dst, scale=1.0):
             assert src.dtype == torch.float32 and src.is_contiguous()
             e.src, e.dst_offset, e.n = _ptr(src), off, src.numel()
         work = sum(src.numel() for src, _ in part) * 6.0
-        _run("grad_pack_bf16", work, "byte", lambda: lib.xvit_grad_pack_bf16(table, len(part), base, dst.numel(), float(scale), _stream()), "xvit_grad_pack_bf16")
+        _call("xvit_grad_pack_bf16", "grad_pack_bf16", work, "byte", table, len(part), base, dst.numel(), float(scale))
     return dst
 
 
 def grad_unpack_bf16(src, dst, scale=1.0):
     """dst = float(src) * scale (xvit_grad_unpack_bf16): a reduced bf16 wire buffer back into its fp32 bucket; contiguous, same numel."""
     assert src.dtype == torch.bfloat16 and dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
-    _run("grad_unpack_bf16", src.numel() * 6.0, "byte", lambda: _lib.load().xvit_grad_unpack_bf16(_ptr(src), _ptr(dst), src.numel(), float(scale), _stream()), "xvit_grad_unpack_bf16")
+    _call("xvit_grad_unpack_bf16", "grad_unpack_bf16", src.numel() * 6.0, "byte", _ptr(src), _ptr(dst), src.numel(), float(scale))
     return dst
 
 
@@ -866,8 +861,8 @@ def add_cast(a, b):
     """-> (a + b fp32, its bf16 copy) in one pass (xvit_add_cast_f32_bf16); contiguous fp32 tensors of one shape, numel % 8 == 0."""
     assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
     out = torch.empty_like(a)
-    outb = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device)
-    _run("add_cast", a.numel() * 14.0, "byte", lambda: _lib.load().xvit_add_cast_f32_bf16(_ptr(a), _ptr(b), _ptr(out), _ptr(outb), a.numel(), _stream()), "xvit_add_cast_f32_bf16")
+    outb = _b16(a.shape, device=a.device)
+    _call("xvit_add_cast_f32_bf16", "add_cast", a.numel() * 14.0, "byte", _ptr(a), _ptr(b), _ptr(out), _ptr(outb), a.numel())
     return out, outb
 
 
@@ -881,40 +876,33 @@ def rows_combine(dst, a=None, b=None, dst2=None):
             return None, 0, 0
         assert t.shape == (rows, d) and t.stride(1) == 1, f"rows_combine: need [rows, d] views with a unit last stride, got {tuple(t.shape)} {t.stride()}"
         return _ptr(t), _dt(t), t.stride(0)
-    pd, dd, ld = arg(dst)
-    p2, d2, l2 = arg(dst2)
-    pa, da, la = arg(a)
-    pb, db, lb = arg(b)
-    _run("rows_combine", rows * d * 8.0, "byte", lambda: _lib.load().xvit_rows_combine(pd, dd, ld, p2, d2, l2, pa, da, la, pb, db, lb, rows, d, _stream()), "xvit_rows_combine")
+    _call("xvit_rows_combine", "rows_combine", rows * d * 8.0, "byte", *arg(dst), *arg(dst2), *arg(a), *arg(b), rows, d)
     return dst
 
 
 def colsum(x, out=None, accumulate=False):
     rows, n = x.shape
     if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=x.device)
+        out = _f32(n, device=x.device)
         accumulate = False
-    ws, ws_bytes = None, 0
-    if DETERMINISTIC:
-        ws_bytes = _lib.load().xvit_colsum_workspace_bytes(rows, n)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-    _run("colsum", float(rows) * n * x.element_size(), "byte",
-         lambda: _lib.load().xvit_colsum(_ptr(x), _dt(x), _rows2d(x), _ptr(out), rows, n, int(accumulate), _ptr(ws), ws_bytes, _stream()), "xvit_colsum")
+    ws_bytes = _L.xvit_colsum_workspace_bytes(rows, n) if DETERMINISTIC else 0
+    ws = _ws(ws_bytes, x)
+    _call("xvit_colsum", "colsum", float(rows) * n * x.element_size(), "byte", _ptr(x), _dt(x), _rows2d(x), _ptr(out), rows, n, int(accumulate), _ptr(ws), ws_bytes)
     return out
 
 
 def dropout(x, p, seed, out=None):
     assert x.is_contiguous()
     out = out if out is not None else torch.empty_like(x)
-    _lib.check(_lib.load().xvit_dropout(_ptr(x), _ptr(out), _dt(x), x.numel(), p, seed, _stream()), "xvit_dropout")
+    _launch("xvit_dropout", _ptr(x), _ptr(out), _dt(x), x.numel(), p, seed)
     return out
 
 
 def small_linear_fwd(x, W, b):
     M, K = x.shape
     N = W.shape[0]
-    y = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().xvit_small_linear_fwd(_ptr(x), _rows2d(x), _ptr(W), _ptr(b), _ptr(y), M, N, K, _stream()), "xvit_small_linear_fwd")
+    y = _f32(M, N, device=x.device)
+    _launch("xvit_small_linear_fwd", _ptr(x), _rows2d(x), _ptr(W), _ptr(b), _ptr(y), M, N, K)
     return y
 
 
@@ -922,18 +910,21 @@ def small_linear_bwd(dy, x, W, dW, db, z=None):
     """dx = (dy W) * gelu'(z) if z is given (x = gelu(z))."""
     M, K = x.shape
     N = W.shape[0]
-    dx = torch.empty(M, K, dtype=torch.bfloat16, device=x.device)
-    _lib.check(_lib.load().xvit_small_linear_bwd(_ptr(dy), _ptr(x), _rows2d(x), _ptr(W), _ptr(z), _rows2d(z) if z is not None else 0,
-                                                 _ptr(dx), K, _ptr(dW), _ptr(db), M, N, K, int(DETERMINISTIC), _stream()), "xvit_small_linear_bwd")
+    dx = _b16(M, K, device=x.device)
+    _launch("xvit_small_linear_bwd", _ptr(dy), _ptr(x), _rows2d(x), _ptr(W), _ptr(z), _ld(z), _ptr(dx), K, _ptr(dW), _ptr(db), M, N, K, int(DETERMINISTIC))
     return dx
+
+
+def _mean_ce_out(logits_m):
+    """(mean logits [B, C], loss scalar, d loss / d logits_m) of the two cross-entropy kernels."""
+    dev = logits_m.device
+    return _f32(logits_m.shape[1:], device=dev), _f32((), device=dev), torch.empty_like(logits_m)
 
 
 def mean_ce(logits_m, labels, smoothing):
     M, B, Cn = logits_m.shape
-    logits = torch.empty(B, Cn, dtype=torch.float32, device=logits_m.device)
-    loss = torch.empty((), dtype=torch.float32, device=logits_m.device)
-    dl = torch.empty_like(logits_m)
-    _lib.check(_lib.load().xvit_mean_ce(_ptr(logits_m), _ptr(labels), smoothing, _ptr(logits), _ptr(loss), _ptr(dl), M, B, Cn, _stream()), "xvit_mean_ce")
+    logits, loss, dl = _mean_ce_out(logits_m)
+    _launch("xvit_mean_ce", _ptr(logits_m), _ptr(labels), smoothing, _ptr(logits), _ptr(loss), _ptr(dl), M, B, Cn)
     return logits, loss, dl
 
 
@@ -950,8 +941,7 @@ def mix_draw(config, table, vol_size, seed):
     B = table.shape[0]
     _mix_table(table, B, "mix_draw")
     D, H, W = vol_size
-    _run("mix_draw", table.numel() * 4.0, "byte",
-         lambda: _lib.load().xvit_mix_draw(C.byref(config), _ptr(table), B, int(D), int(H), int(W), _seed64(seed), _stream()), "xvit_mix_draw")
+    _call("xvit_mix_draw", "mix_draw", table.numel() * 4.0, "byte", C.byref(config), _ptr(table), B, int(D), int(H), int(W), _seed64(seed))
     return table
 
 
@@ -967,8 +957,8 @@ def mix_apply(img, table, out=None):
     if not (out.dtype == img.dtype and out.is_contiguous() and out.shape == img.shape):
         raise RuntimeError("mix_apply: out must be contiguous, of img's shape and dtype")
     # one read and one write per voxel; a mixup record reads its partner's volume on top, but which records are mixup ones only the device knows
-    _run("mix_apply", img.numel() * float(img.element_size()) * 2.0, "byte",
-         lambda: _lib.load().xvit_mix_apply(_ptr(img), _ptr(out), _dt(img), _ptr(table), B, M, D, H, W, img.stride(0), img.stride(1), _stream()), "xvit_mix_apply")
+    _call("xvit_mix_apply", "mix_apply", img.numel() * float(img.element_size()) * 2.0, "byte",
+          _ptr(img), _ptr(out), _dt(img), _ptr(table), B, M, D, H, W, img.stride(0), img.stride(1))
     return out
 
 
@@ -978,12 +968,9 @@ def mean_ce_mix(logits_m, labels, table, smoothing):
     if table is None:
         raise RuntimeError("mean_ce_mix: a record table is required (mean_ce is the loss without mixing)")
     _mix_table(table, B, "mean_ce_mix")
-    logits = torch.empty(B, Cn, dtype=torch.float32, device=logits_m.device)
-    loss = torch.empty((), dtype=torch.float32, device=logits_m.device)
-    dl = torch.empty_like(logits_m)
-    _run("mean_ce_mix", (2.0 * logits_m.numel() + logits.numel() + table.numel()) * 4.0 + B * 8.0, "byte",
-         lambda: _lib.load().xvit_mean_ce_mix(_ptr(logits_m), _ptr(labels), _ptr(table), smoothing, _ptr(logits), _ptr(loss), _ptr(dl), M, B, Cn, _stream()),
-         "xvit_mean_ce_mix")
+    logits, loss, dl = _mean_ce_out(logits_m)
+    _call("xvit_mean_ce_mix", "mean_ce_mix", (2.0 * logits_m.numel() + logits.numel() + table.numel()) * 4.0 + B * 8.0, "byte",
+          _ptr(logits_m), _ptr(labels), _ptr(table), smoothing, _ptr(logits), _ptr(loss), _ptr(dl), M, B, Cn)
     return logits, loss, dl
 
 
@@ -993,10 +980,9 @@ def resize_pad_crop_i16(vol, img_size, pad_value=-1.0):
     assert vol.dtype == torch.int16 and vol.dim() == 5 and vol.is_contiguous()
     B, M, Ds, Hs, Ws = vol.shape
     D, H, W = img_size
-    out = torch.empty(B, M, 1, D, H, W, dtype=torch.bfloat16, device=vol.device)
-    _run("resize_pad_crop_i16", vol.numel() * 2.0 + out.numel() * 2.0, "byte",
-         lambda: _lib.load().xvit_resize_pad_crop_i16(_ptr(vol), _ptr(out), B * M, Ds, Hs, Ws, D, H, W, float(pad_value), _stream()),
-         "xvit_resize_pad_crop_i16")
+    out = _b16(B, M, 1, D, H, W, device=vol.device)
+    _call("xvit_resize_pad_crop_i16", "resize_pad_crop_i16", vol.numel() * 2.0 + out.numel() * 2.0, "byte",
+          _ptr(vol), _ptr(out), B * M, Ds, Hs, Ws, D, H, W, float(pad_value))
     return out
 
 
@@ -1021,10 +1007,8 @@ def augment_draw(config, params, vol_shape, img_size, seed, counter=None, advanc
     _counter_arg(counter, "augment_draw")
     B, M = params.shape[:2]
     (Ds, Hs, Ws), (D, H, W) = vol_shape, img_size
-    _run("augment_draw", params.numel() * 4.0, "byte",
-         lambda: _lib.load().xvit_augment_draw(C.byref(config), _ptr(params), B, M, Ds, Hs, Ws, D, H, W, _seed64(seed), _ptr(counter),
-                                               int(bool(advance)), _stream()),
-         "xvit_augment_draw")
+    _call("xvit_augment_draw", "augment_draw", params.numel() * 4.0, "byte",
+          C.byref(config), _ptr(params), B, M, Ds, Hs, Ws, D, H, W, _seed64(seed), _ptr(counter), int(bool(advance)))
     return params
 
 
@@ -1036,15 +1020,9 @@ def _augment_apply(name, src, params, img_size, pad_value, out_dtype, elastic=No
     grid = _elastic_tables(*elastic, B, name) if elastic is not None else None
     D, H, W = img_size
     out = torch.empty(B, M, 1, D, H, W, dtype=out_dtype, device=src.device)
-    sdt = _src_dt(src)
-
-    def call():
-        head, tail = (_ptr(src), sdt, _ptr(out), _dt(out), _ptr(params)), (Ds, Hs, Ws, D, H, W, float(pad_value), _stream())
-        if elastic is None:
-            return _lib.load().xvit_augment_apply(*head, B * M, *tail)
-        return _lib.load().xvit_augment_apply_elastic(*head, _ptr(elastic[0]), _ptr(elastic[1]), B * M, M, *grid, *tail)
-
-    _run(name, src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte", call, "xvit_" + name)
+    volumes = (B * M,) if elastic is None else (_ptr(elastic[0]), _ptr(elastic[1]), B * M, M, *grid)
+    _call("xvit_" + name, name, src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
+          _ptr(src), _src_dt(src), _ptr(out), _dt(out), _ptr(params), *volumes, Ds, Hs, Ws, D, H, W, float(pad_value))
     return out
 
 
@@ -1072,10 +1050,8 @@ def elastic_draw(config, field, erec, seed, counter=None, advance=False):
     B = field.shape[0] if isinstance(field, torch.Tensor) and field.dim() == 5 else 0
     Gz, Gy, Gx = _elastic_tables(field, erec, B, "elastic_draw")
     _counter_arg(counter, "elastic_draw")
-    _run("elastic_draw", (field.numel() + erec.numel()) * 4.0, "byte",
-         lambda: _lib.load().xvit_elastic_draw(C.byref(config), _ptr(field), _ptr(erec), B, Gz, Gy, Gx, _seed64(seed), _ptr(counter),
-                                               int(bool(advance)), _stream()),
-         "xvit_elastic_draw")
+    _call("xvit_elastic_draw", "elastic_draw", (field.numel() + erec.numel()) * 4.0, "byte",
+          C.byref(config), _ptr(field), _ptr(erec), B, Gz, Gy, Gx, _seed64(seed), _ptr(counter), int(bool(advance)))
     return field, erec
 
 
@@ -1091,10 +1067,7 @@ def contrast_draw(config, params, seed, counter=None, advance=False):
     assert params.dtype == torch.float32 and params.dim() == 3 and params.shape[2] == _lib.CON_NPARAM and params.is_contiguous()
     _counter_arg(counter, "contrast_draw")
     nvol = params.shape[0] * params.shape[1]
-    _run("contrast_draw", params.numel() * 4.0, "byte",
-         lambda: _lib.load().xvit_contrast_draw(C.byref(config), _ptr(params), nvol, _seed64(seed), _ptr(counter), int(bool(advance)),
-                                                _stream()),
-         "xvit_contrast_draw")
+    _call("xvit_contrast_draw", "contrast_draw", params.numel() * 4.0, "byte", C.byref(config), _ptr(params), nvol, _seed64(seed), _ptr(counter), int(bool(advance)))
     return params
 
 
@@ -1107,16 +1080,15 @@ def contrast_apply(src, params, out_dtype=None):
     assert src.numel() == B * M * D * H * W, f"volumes {tuple(src.shape)} are not [B, M, (1,) D, H, W]"
     assert tuple(params.shape) == (B, M, _lib.CON_NPARAM), f"params {tuple(params.shape)} do not match {B} x {M} volumes"
     out = torch.empty(src.shape, dtype=out_dtype or src.dtype, device=src.device)
-    _run("contrast_apply", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
-         lambda: _lib.load().xvit_contrast_apply(_ptr(src), _ptr(out), _dt(src), _dt(out), _ptr(params), B * M, D, H, W, _stream()),
-         "xvit_contrast_apply")
+    _call("xvit_contrast_apply", "contrast_apply", src.numel() * float(src.element_size()) + out.numel() * float(out.element_size()), "byte",
+          _ptr(src), _ptr(out), _dt(src), _dt(out), _ptr(params), B * M, D, H, W)
     return out
 
 
 def volume_stats_workspace(nvol, device):
     """The zero-filled histogram workspace of volume_stats for nvol volumes (xvit_volume_stats_workspace_bytes): every call leaves it
     zero again, so it is filled once, here."""
-    return torch.zeros(_lib.load().xvit_volume_stats_workspace_bytes(int(nvol)), dtype=torch.uint8, device=device)
+    return torch.zeros(_L.xvit_volume_stats_workspace_bytes(int(nvol)), dtype=torch.uint8, device=device)
 
 
 def volume_stats(src, config, stats, workspace, params=None):
@@ -1130,12 +1102,9 @@ def volume_stats(src, config, stats, workspace, params=None):
     assert tuple(stats.shape) == (B, M, _lib.STATS_NSTAT), f"stats {tuple(stats.shape)} do not match {B} x {M} volumes"
     if params is not None:
         assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B, M, _lib.AUG_NPARAM)
-    sdt = _src_dt(src)
     try:
-        _run("volume_stats", src.numel() * float(src.element_size()), "byte",
-             lambda: _lib.load().xvit_volume_stats(_ptr(src), sdt, B * M, nvox, C.byref(config), _ptr(stats), _ptr(params), _ptr(workspace),
-                                                   workspace.numel() * workspace.element_size(), _stream()),
-             "xvit_volume_stats")
+        _call("xvit_volume_stats", "volume_stats", src.numel() * float(src.element_size()), "byte", _ptr(src), _src_dt(src), B * M, nvox, C.byref(config),
+              _ptr(stats), _ptr(params), _ptr(workspace), workspace.numel() * workspace.element_size())
     except RuntimeError as e:
         if src.dtype == torch.float32:
             raise TypeError(str(e)) from None
@@ -1146,7 +1115,7 @@ def volume_stats(src, config, stats, workspace, params=None):
 def volume_bbox_workspace(nvol, nvox, device):
     """The partial-box workspace of volume_bbox for nvol volumes of nvox voxels (xvit_volume_bbox_workspace_bytes); its contents do not
     matter on entry."""
-    return torch.empty(_lib.load().xvit_volume_bbox_workspace_bytes(int(nvol), int(nvox)), dtype=torch.uint8, device=device)
+    return torch.empty(_L.xvit_volume_bbox_workspace_bytes(int(nvol), int(nvox)), dtype=torch.uint8, device=device)
 
 
 def volume_bbox(src, config, img_size, boxes, crop, workspace, params=None):
@@ -1163,11 +1132,8 @@ def volume_bbox(src, config, img_size, boxes, crop, workspace, params=None):
     if params is not None:
         assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B, M, _lib.AUG_NPARAM)
     D, H, W = img_size
-    sdt = _src_dt(src)
-    _run("volume_bbox", src.numel() * float(src.element_size()), "byte",
-         lambda: _lib.load().xvit_volume_bbox(_ptr(src), sdt, B * M, M, Ds, Hs, Ws, D, H, W, C.byref(config), _ptr(boxes), _ptr(crop), _ptr(params),
-                                              _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
-         "xvit_volume_bbox")
+    _call("xvit_volume_bbox", "volume_bbox", src.numel() * float(src.element_size()), "byte", _ptr(src), _src_dt(src), B * M, M, Ds, Hs, Ws, D, H, W,
+          C.byref(config), _ptr(boxes), _ptr(crop), _ptr(params), _ptr(workspace), workspace.numel() * workspace.element_size())
     return boxes, crop
 
 
@@ -1182,15 +1148,13 @@ def epoch_metrics_update(logits, labels, scores, labels32, preds, state):
     assert labels32.dtype == torch.int32 and preds.dtype == torch.int32 and labels32.is_contiguous() and preds.is_contiguous()
     assert labels32.numel() == cap and preds.numel() == cap
     assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() == _lib.EPOCH_STATE_HEAD + Cn * Cn
-    _run("epoch_metrics_update", B * Cn * 8.0, "byte",
-         lambda: _lib.load().xvit_epoch_metrics_update(_ptr(logits), _rows2d(logits), _ptr(labels), B, Cn, _ptr(scores), _ptr(labels32), _ptr(preds), cap,
-                                                       _ptr(state), _stream()),
-         "xvit_epoch_metrics_update")
+    _call("xvit_epoch_metrics_update", "epoch_metrics_update", B * Cn * 8.0, "byte",
+          _ptr(logits), _rows2d(logits), _ptr(labels), B, Cn, _ptr(scores), _ptr(labels32), _ptr(preds), cap, _ptr(state))
 
 
 def epoch_rank_stats_max_n() -> int:
     """xvit_epoch_rank_stats_max_n: the largest epoch (samples) xvit_epoch_rank_stats takes with bootstrap replicates."""
-    return int(_lib.load().xvit_epoch_rank_stats_max_n())
+    return int(_L.xvit_epoch_rank_stats_max_n())
 
 
 def epoch_rank_stats(scores, labels32, preds, perm, n_dev, n_max, R, seed):
@@ -1207,8 +1171,6 @@ def epoch_rank_stats(scores, labels32, preds, perm, n_dev, n_max, R, seed):
     ranks = torch.empty(R + 1, Cn, _lib.EPOCH_RANK_NSTAT, dtype=torch.int64, device=dev)
     ap = torch.empty(R + 1, Cn, dtype=torch.float64, device=dev)
     conf = torch.empty(R + 1, Cn, Cn, dtype=torch.int64, device=dev)
-    _run("epoch_rank_stats", (R + 1) * Cn * float(n_max) * 16.0, "byte",
-         lambda: _lib.load().xvit_epoch_rank_stats(_ptr(scores), _ptr(labels32), _ptr(preds), _ptr(perm), perm.stride(0), _ptr(n_dev), int(n_max), Cn, int(R),
-                                                   _seed64(seed), _ptr(ranks), _ptr(ap), _ptr(conf), _stream()),
-         "xvit_epoch_rank_stats")
+    _call("xvit_epoch_rank_stats", "epoch_rank_stats", (R + 1) * Cn * float(n_max) * 16.0, "byte", _ptr(scores), _ptr(labels32), _ptr(preds),
+          _ptr(perm), perm.stride(0), _ptr(n_dev), int(n_max), Cn, int(R), _seed64(seed), _ptr(ranks), _ptr(ap), _ptr(conf))
     return ranks, ap, conf
