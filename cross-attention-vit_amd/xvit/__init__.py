@@ -13,6 +13,7 @@ own nn.Module signatures (vsahni3/cross-attention-ViT: model_cross.py, model.py)
     config.mixup_alpha / config.cutmix_alpha         # Mixup / CutMix with a soft-target loss in ModelCross.train() (fine-tuning)
     config.patch_select = "foreground"               # patch dropout ranked by per-patch foreground; eval_patch_dropout shortens eval() too
     xvit.token_occupancy(img, patch_size)            # the per-patch foreground counts that ranking reads
+    xvit.data.VolumeStore / xvit.data.BatchSampler   # raw volumes resident on the device; batches drawn and gathered there, capturable
 """
 from . import _lib  # noqa: F401
 from .functional import invalidate_shadows, token_occupancy  # noqa: F401   (token_occupancy: per-patch foreground counts, stand-alone)
@@ -24,4 +25,5 @@ from .metrics import BinaryEpochMetrics, EpochMetrics  # noqa: F401
 from . import interpret  # noqa: F401   (attention maps and rollout: xvit.interpret.attention_maps)
 from . import augment  # noqa: F401     (the augmenting input stage: xvit.augment.VolumeAugment)
 from .augment import AugmentParams, ContrastAugment, ContrastParams, ForegroundBoxes, VolumeAugment  # noqa: F401
+from . import data  # noqa: F401        (the device-resident volume store: xvit.data.VolumeStore, xvit.data.BatchSampler)
 from .mae import MaskedVolumeModel  # noqa: F401   (masked-volume pretraining around a ModelCross encoder)

@@ -104,6 +104,7 @@ MIX_NPARAM = 16                                        # XVIT_MIX_NPARAM: floats
 MIX_MODE, MIX_PARTNER, MIX_LAM, MIX_OML, MIX_BOX, MIX_LAM0 = 0, 1, 2, 3, 4, 10    # XVIT_MIX_*: the record's fields
 MIX_MODE_MIXUP, MIX_MODE_CUTMIX = 1, 2                 # XVIT_MIX_MODE_*
 MIX_DRAW_STRIDE = 256                                  # XVIT_MIX_DRAW_STRIDE: hash indices per decision block of xvit_mix_draw
+BATCH_WEIGHTED, BATCH_SHUFFLE, BATCH_SEQUENTIAL = 0, 1, 2   # XVIT_BATCH_*: the modes of xvit_batch_draw
 
 
 # name -> argtypes; every function returns int except the two noted below
@@ -163,6 +164,8 @@ SIGNATURES = {
     "xvit_mix_draw": [C.POINTER(MixConfig), vp, i32, i32, i32, i32, u64, vp],
     "xvit_mix_apply": [vp, vp, i32, vp, i32, i32, i32, i32, i32, i64, i64, vp],
     "xvit_mean_ce_mix": [vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, vp],
+    "xvit_batch_draw": [vp, vp, i64, i32, i32, i32, i32, u64, u64, vp, i32, vp],
+    "xvit_batch_gather": [vp, i64, i64, vp, i32, vp, vp, vp, vp, vp],
     "xvit_resize_pad_crop_i16": [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "xvit_augment_draw": [C.POINTER(AugmentConfig), vp, i32, i32, i32, i32, i32, i32, i32, i32, u64, vp, i32, vp],
     "xvit_augment_apply": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],

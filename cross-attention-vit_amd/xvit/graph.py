@@ -19,6 +19,12 @@ corrections and learning rate are all device-side), the whole training step as o
     logits, loss = step(img, labels)                         # replay: gradients, clip, Adam; p.grad stay the UNCLIPPED gradients
     sched.step()                                             # the next call writes the new rate to the device before it replays
 
+or, with the input stage inside the graph as well (xvit.data: a device-resident store, a capturable sampler and capturable stages):
+
+    src = lambda: (lambda r, y: (con(aug(r)), y))(*sampler())               # draw, gather, augment: every launch capturable
+    step = GraphedStep(model, img_example, labels_example, optimizer=opt, source=src)
+    logits, loss = step()                                    # replay: the next batch is drawn, gathered, augmented and trained on
+
 Restrictions: static shapes.  Dropout (the reference trains with p = 0.1 .. 0.25, main_mist.py:71-77): the host-side seeds of the
 capture are frozen into the graph, so the step registers a device counter (xvit_set_dropout_epoch), increments it at the head of the
 graph, and every dropout kernel mixes its value into the seed at run time: each replay draws fresh masks, the same in its forward and
@@ -58,9 +64,16 @@ class GraphedStep:
 
     optimizer (xvit.optim.FusedAdam(capturable=True), optional): its launches are appended to the capture, behind reducer.finish() when
     there is a reducer (the clipped norm is that of the averaged gradients, the same on every rank).  Construction leaves parameters,
-    moments and step count untouched: the warm-up runs the model step alone, and a capture executes nothing."""
+    moments and step count untouched: the warm-up runs the model step alone, and a capture executes nothing.
 
-    def __init__(self, model, img, labels, warmup: int = 3, reducer=None, optimizer=None):
+    source (a callable returning (img, labels), optional): the step's input is produced INSIDE the graph.  source() is invoked at the top of
+    every step, in the warm-up and in the capture, in place of the static img / labels, which are then only shape / dtype examples; after
+    the capture step.img / step.labels are the graph's own buffers, so the caller can read what a replay trained on.  Everything source()
+    launches must be capturable (xvit.data.BatchSampler(capturable=True), VolumeAugment(capturable=True), ...) and already called once, so
+    that nothing is allocated outside the graph's pool.  The warm-up calls source() `warmup` times: it advances the call indices of the
+    sampler and the stages by that many (the capture itself executes nothing).  step(img=...) / step(labels=...) are refused."""
+
+    def __init__(self, model, img, labels, warmup: int = 3, reducer=None, optimizer=None, source=None):
         if not img.is_cuda:
             raise RuntimeError("GraphedStep needs GPU tensors")
         if optimizer is not None:
@@ -69,7 +82,10 @@ class GraphedStep:
                 raise RuntimeError("GraphedStep: only xvit.optim.FusedAdam(..., capturable=True) can run inside the graph (any other optimizer's step "
                                    f"keeps host-side numbers or allocates); got {type(optimizer).__name__}"
                                    + ("(capturable=False)" if isinstance(optimizer, FusedAdam) else "") + ". Leave optimizer=None and step it after the replay")
+        if source is not None and not callable(source):
+            raise TypeError(f"GraphedStep: source is a callable returning (img, labels), got {type(source).__name__}")
         self.optimizer = optimizer
+        self.source = source
         # dropout active anywhere in the step: a device-side epoch makes every replay draw new masks (module docstring)
         self._training = model.training        # frozen into the graph: the epoch below, and every kernel choice that depends on the mode
         self._epoch = torch.zeros(1, dtype=torch.int64, device=img.device) if model.training and _has_dropout(model) else None
@@ -157,10 +173,21 @@ class GraphedStep:
         finally:
             ops.set_dropout_epoch(None)
 
+    def _inputs(self):
+        """The step's (img, labels): the static pair, or what source() produces now (kept as self.img / self.labels: inside the capture
+        these are the graph's own buffers)."""
+        if self.source is not None:
+            img, labels = self.source()
+            if img.shape != self.img.shape or img.dtype != self.img.dtype or labels.shape != self.labels.shape or labels.dtype != self.labels.dtype:
+                raise RuntimeError(f"GraphedStep: source() returned {img.dtype} {tuple(img.shape)} / {labels.dtype} {tuple(labels.shape)}, the examples are "
+                                   f"{self.img.dtype} {tuple(self.img.shape)} / {self.labels.dtype} {tuple(self.labels.shape)}")
+            self.img, self.labels = img, labels
+        return self.img, self.labels
+
     def _step(self):
         red = self.reducer
         if red is None:
-            logits, loss = torch.func.functional_call(self.model, self._alias, (self.img, self.labels))
+            logits, loss = torch.func.functional_call(self.model, self._alias, self._inputs())
             grads = torch.autograd.grad(loss, [self._alias[n] for n, _ in self._named], allow_unused=True)   # see the module docstring
             for p, g in zip(self.params, grads):
                 p.grad = g
@@ -169,7 +196,7 @@ class GraphedStep:
         handles = red.attach_leaves([(p, self._alias[n]) for n, p in self._named])
         red.set_graph_mode(True)
         try:
-            logits, loss = torch.func.functional_call(self.model, self._alias, (self.img, self.labels))
+            logits, loss = torch.func.functional_call(self.model, self._alias, self._inputs())
             torch.autograd.grad(loss, [self._alias[n] for n, _ in self._named], allow_unused=True)   # the hooks move / count the gradients
             red.finish()                       # unused parameters' buckets, then the capture stream waits for every collective
         finally:
@@ -190,6 +217,9 @@ class GraphedStep:
         if self.optimizer is not None:
             self.optimizer.check_addresses(grads=False)    # the graph owns the gradient buffers; the optimizer's parameters must not have moved
             self.optimizer.sync_lr()
+        if self.source is not None and (img is not None or labels is not None):
+            raise RuntimeError("GraphedStep: this step takes its input from source() inside the graph; img= / labels= cannot be passed (build a step "
+                               "without source= to feed tensors)")
         if img is not None:
             self.img.copy_(img, non_blocking=True)
         if labels is not None:

@@ -1174,3 +1174,49 @@ def epoch_rank_stats(scores, labels32, preds, perm, n_dev, n_max, R, seed):
     _call("xvit_epoch_rank_stats", "epoch_rank_stats", (R + 1) * Cn * float(n_max) * 16.0, "byte", _ptr(scores), _ptr(labels32), _ptr(preds),
           _ptr(perm), perm.stride(0), _ptr(n_dev), int(n_max), Cn, int(R), _seed64(seed), _ptr(ranks), _ptr(ap), _ptr(conf))
     return ranks, ap, conf
+
+
+def batch_draw(idx, mode, n_cases, seed, *, cdf=None, rank=0, world=1, call=0, counter=None, advance=False):
+    """xvit_batch_draw (include/xvit.h): fill idx int32 [B] with the case indices of one batch of a store of n_cases cases.  mode:
+    _lib.BATCH_WEIGHTED (cdf: the fp64 [n_cases] inclusive prefix of the normalised weights, on the device), BATCH_SHUFFLE or
+    BATCH_SEQUENTIAL.  The call index is `call`, or, with counter (a one-element int64 device tensor), read from it at kernel run time and
+    advanced by one behind the read when advance is set."""
+    if not (idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()):
+        raise RuntimeError(f"batch_draw: idx is a contiguous int32 vector, got {idx.dtype} {tuple(idx.shape)}")
+    if cdf is not None and not (cdf.dtype == torch.float64 and cdf.is_contiguous() and cdf.numel() == n_cases):
+        raise RuntimeError(f"batch_draw: the cdf is a contiguous fp64 vector of {n_cases} entries, got {cdf.dtype} {tuple(cdf.shape)}")
+    _counter_arg(counter, "batch_draw")
+    B = idx.numel()
+    _call("xvit_batch_draw", "batch_draw", B * 4.0, "byte", _ptr(idx), _ptr(cdf), int(n_cases), B, int(mode), int(rank), int(world), _seed64(seed),
+          _seed64(call), _ptr(counter), int(bool(advance)))
+    return idx
+
+
+def batch_gather(store, idx, n_cases=None, labels=None, out=None, labels_out=None, status=None):
+    """xvit_batch_gather (include/xvit.h): store [capacity, ...] (contiguous, any dtype of 2 or 4 bytes) and idx int32 [B], both on the
+    device -> out [B, ...] with out[b] = store[idx[b]] among the first n_cases cases (None: all); labels int64 [capacity] -> labels_out
+    int64 [B]; status int32 [B] (optional) receives 1 where an index was out of range (zeros, label -1), else 0.  Returns (out, labels_out)."""
+    if not (store.dim() >= 1 and store.is_contiguous() and store.shape[0] > 0):
+        raise RuntimeError(f"batch_gather: the store is a contiguous [capacity, ...] tensor, got {tuple(store.shape)} strides {store.stride()}")
+    if not (idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous() and idx.numel() > 0):
+        raise RuntimeError(f"batch_gather: idx is a non-empty contiguous int32 vector, got {idx.dtype} {tuple(idx.shape)}")
+    n_cases = store.shape[0] if n_cases is None else int(n_cases)
+    if not 0 < n_cases <= store.shape[0]:
+        raise RuntimeError(f"batch_gather: n_cases={n_cases} must lie in [1, {store.shape[0]}]")
+    B = idx.numel()
+    case_bytes = store[0].numel() * store.element_size()
+    out = out if out is not None else torch.empty((B,) + tuple(store.shape[1:]), dtype=store.dtype, device=store.device)
+    if not (out.dtype == store.dtype and out.is_contiguous() and tuple(out.shape) == (B,) + tuple(store.shape[1:])):
+        raise RuntimeError("batch_gather: out must be contiguous, of the store's dtype and of shape [B, ...]")
+    if labels is not None:
+        if not (labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() >= n_cases):
+            raise RuntimeError(f"batch_gather: labels is a contiguous int64 vector of at least {n_cases} entries")
+        labels_out = labels_out if labels_out is not None else torch.empty(B, dtype=torch.int64, device=store.device)
+        if not (labels_out.dtype == torch.int64 and labels_out.is_contiguous() and labels_out.numel() == B):
+            raise RuntimeError(f"batch_gather: labels_out is a contiguous int64 vector of {B} entries")
+    if status is not None and not (status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B):
+        raise RuntimeError(f"batch_gather: status is a contiguous int32 vector of {B} entries")
+    # one read and one write per byte of the batch
+    _call("xvit_batch_gather", "batch_gather", 2.0 * B * case_bytes, "byte", _ptr(store), case_bytes, n_cases, _ptr(idx), B, _ptr(out),
+          _ptr(labels), _ptr(labels_out) if labels is not None else None, _ptr(status))
+    return out, (labels_out if labels is not None else None)

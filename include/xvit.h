@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 319 /* 0.3.19: xvit_patch_occupancy, xvit_token_select_ranked and XVIT_TOKEN_RANK_RANDOM / XVIT_TOKEN_RANK_TOP (foreground-ranked token selection for training and eval()); 0.3.18:xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 320 /* 0.3.20: xvit_batch_draw, xvit_batch_gather and XVIT_BATCH_WEIGHTED / XVIT_BATCH_SHUFFLE / XVIT_BATCH_SEQUENTIAL (a device-resident volume store whose batches a captured step draws); 0.3.19: xvit_patch_occupancy, xvit_token_select_ranked and XVIT_TOKEN_RANK_RANDOM / XVIT_TOKEN_RANK_TOP (foreground-ranked token selection for training and eval()); 0.3.18:xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply, xvit_volume_stats and xvit_volume_bbox only */ };
@@ -990,6 +990,47 @@ typedef struct xvit_grad_segment {
 } xvit_grad_segment;
 int xvit_grad_pack_bf16(const xvit_grad_segment* segments, int n_segments, void* dst_bf16, int64_t dst_n, float scale, xvit_stream_t stream);
 int xvit_grad_unpack_bf16(const void* src_bf16, float* dst, int64_t n, float scale, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Device-resident volume store (csrc/batch_store.hip; xvit/data.py).  The reference draws its batches on the host
+ * (main_mist.py:194-207: WeightedRandomSampler over the case table, five loader workers); here the raw volumes of every case live in one
+ * device allocation, the sampler is drawn on the device and the batch is gathered through an index tensor that never leaves it, so a
+ * captured step replays draw -> gather -> augment -> forward -> backward -> optimizer with no host data work.
+ *
+ * xvit_batch_draw writes idx[B] (int32), the case index of every sample of one batch.  With c = counter ? *counter : call, sample i has the
+ * global ordinal k = (c * world + rank) * B + i (uint64, modulo 2^64), and its index is a function of (seed, k) alone: the sample stream
+ * does not depend on how it is cut into ranks and calls.  s = seed ^ 0x5356444154415354 keeps the stream apart from the other draw streams
+ * under one seed; hash32 is the dropout hash (xvit_dropout), draw24 its low 24 bits.
+ *    XVIT_BATCH_WEIGHTED    with replacement (WeightedRandomSampler(replacement=True) in kind; parity with torch's stream is NOT claimed):
+ *                           u = (draw24(s, 2k) * 2^24 + draw24(s, 2k + 1)) * 2^-48, exact in fp64; idx = the number of j with cdf[j] <= u,
+ *                           clamped to n_cases - 1.  cdf[n_cases] is the inclusive fp64 prefix of the normalised weights, built on the
+ *                           host, non-decreasing, with every entry from the last positive weight on exactly 1: a zero-weight case is never
+ *                           drawn.  cdf is required in this mode and ignored in the others.
+ *    XVIT_BATCH_SHUFFLE     without replacement within an epoch: q = k mod n, e = k div n, idx = pi_e(q).  pi_e is a keyed bijection on
+ *                           [0, n): a balanced 4-round Feistel network on w bits, w = max(2, ceil(log2 n)) rounded up to even, with cycle
+ *                           walking.  L = x >> w/2, R = x & mask; each round r = 0..3: (L, R) <- (R, L ^ (hash32(key, r << 32 | R) & mask)),
+ *                           key = s + e * 0xD1B54A32D192ED03; x = L << w/2 | R; repeat while x >= n.  Any n consecutive ordinals from a
+ *                           multiple of n see every case exactly once, so the ranks of an epoch are disjoint; a batch may straddle two
+ *                           epochs.  A bijection; uniformity over all permutations is not claimed.
+ *    XVIT_BATCH_SEQUENTIAL  idx = k mod n.
+ * The counter as in xvit_augment_draw: optional, 8-byte aligned, read at run time; advance != 0: one thread stores counter + 1 after every
+ * thread has read it.  One workgroup loops over B.  Refused before the launch: null idx, n_cases <= 0 or > 2^31 - 1, B <= 0, an unknown
+ * mode, rank outside [0, world), a misaligned counter, idx or cdf, advance without a counter, the weighted mode without a cdf.
+ *
+ * xvit_batch_gather: dst[b] = store[idx[b]] byte for byte (case_bytes bytes each, any dtype) and, with labels_src != NULL,
+ * labels_dst[b] = labels_src[idx[b]]; status (optional) receives 0 per sample.  idx is read on the device: the next replay of a captured
+ * launch gathers another batch.  An index outside [0, n_cases) gives a zero-filled case, label -1 and status[b] = 1; the kernel never
+ * reads outside the store whatever idx holds.  store [n_cases, case_bytes] and dst [B, case_bytes] are contiguous and 16-byte aligned,
+ * case_bytes a positive multiple of 2.  With case_bytes % 16 == 0 (every real volume shape) every case base is aligned: 16 bytes per
+ * lane, eight loads of a lane in flight before its first store, each 256-thread workgroup owns a 32 KiB chunk of one case.  Otherwise
+ * the phases of source and destination differ per case and a 2-byte-per-lane path runs (4 KiB chunks).  Refused before the launch: null
+ * store, idx or dst, labels_src without labels_dst, sizes <= 0, an odd case_bytes, misalignment, B x chunks >= 2^31.
+ * ---------------------------------------------------------------------------------------- */
+enum { XVIT_BATCH_WEIGHTED = 0, XVIT_BATCH_SHUFFLE = 1, XVIT_BATCH_SEQUENTIAL = 2 };
+int xvit_batch_draw(int32_t* idx, const double* cdf, int64_t n_cases, int B, int mode, int rank, int world, uint64_t seed, uint64_t call,
+                    uint64_t* counter, int advance, xvit_stream_t stream);
+int xvit_batch_gather(const void* store, int64_t case_bytes, int64_t n_cases, const int32_t* idx, int B, void* dst, const int64_t* labels_src,
+                      int64_t* labels_dst, int32_t* status, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Head tail (model_cross.py:205-211): logits = mean_m logits_m;  loss = CE(logits, labels,
