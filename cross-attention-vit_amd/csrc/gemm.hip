@@ -926,6 +926,19 @@ __device__ __forceinline__ void wave_tile_epilogue(const GemmParams& p, const f3
     e.slab_step = 4u * (uint32_t)p.N * 4u;
     e.c_gap = smap ? (uint32_t)p.seg_skip * (uint32_t)p.ldc * ce : 0u;
     e.res_wrap = rmap ? e.rmod * (uint32_t)p.ldr * 4u : 0u;
+    // A body steps 4 rows and wraps at most once, which takes a residual modulus of at least 4 (a patch embedding of 1 or 2 tokens per
+    // sample has 1 to 3 rows of pos).  Moduli 1, 2 and 4 divide the step: the residual row never changes.  Modulus 3: 4 rows on is one
+    // residual row on, and the remainder is counted in quarters (4 rrem against 12), so the bodies' rule holds unchanged.
+    if (rmap && e.rmod <= 4u) {
+      if (e.rmod == 3u) { e.rrem *= 4u; e.rmod = 12u; e.res_step = (uint32_t)p.ldr * 4u; }
+      else { e.rmod = 0x7FFFFFFFu; e.res_step = 0u; e.res_wrap = 0u; }
+    }
+    // The same for output segments of 1 to 4 rows: a step crosses 4, 2 or 1 segment ends whatever the row (4 / seg_rows whole gaps
+    // go into the step), or, with 3 rows, one end plus another one at every third step.
+    if (smap && e.smod <= 4u) {
+      if (e.smod == 3u) { e.srem *= 4u; e.smod = 12u; e.c_step += e.c_gap; }
+      else { e.c_step += (e.smod == 1u ? 4u : e.smod == 2u ? 2u : 1u) * e.c_gap; e.smod = 0x7FFFFFFFu; }
+    }
   }
   // one specialised, fully unrolled copy per (activation, dropout): every acc[][] index is a compile-time constant
   // a plain bias + residual epilogue loads its residual one region ahead; nothing is read where the split-K reduce adds it

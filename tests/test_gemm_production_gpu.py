@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import xvit.functional as XF
-from _gemm_check import TN_EDGES, Spec, _operands, _options, check_site
+from _gemm_check import TN_EDGES, Spec, _operands, _options, check_site, compare, launch, reference
 from _util import assert_exact, dev, exact_grid
 
 GEMM_HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cross-attention-vit_amd", "csrc", "gemm.hip")
@@ -207,3 +207,20 @@ def test_batched_grids(layout, batch, split, f32, bias, res):
     M, N, K = 296, 520, 192
     _exact_case(layout, M, N, K, f32=f32, split=split, batch=(batch,), bias=bias, res=res,
                 what=f"batched {layout} {batch}x{M}x{N}x{K} split {split}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("f32", [True, False], ids=["f32", "bf16"])
+@pytest.mark.parametrize("period", [1, 2, 3, 4, 5, 7])
+def test_short_residual_and_segment_periods(period, f32):
+    """A residual table of `period` rows (res_row_mod) and output segments of `period` rows with a one-row gap (out_seg): the narrow
+    epilogue steps 4 rows per body, so periods up to 4 wrap more than once per step, or on every step (the patch embedding of a
+    volume of 1 or 2 tokens per sample, fused or as patchify + GEMM).  Once with both maps, once each alone; ragged last tiles."""
+    M, N, K = 296, 520, 128
+    for res_mod, seg in ((period, (period, 1, 1)), (period, (0, 0, 0)), (0, (period, 1, 1))):
+        spec = Spec(f"period-{period}-res{res_mod}-seg{seg[0]}", "NT", M, N, K, f32=f32, bias=True, res=res_mod > 0, res_mod=res_mod, res_off=1 if res_mod else 0,
+                    seg=seg, s=2)
+        R = reference(spec)
+        with _options(gemm_tile=2):
+            out = launch(spec, R)
+        compare(spec, R, out)

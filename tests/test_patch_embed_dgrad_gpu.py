@@ -8,7 +8,8 @@ output sits in a sentinel-filled buffer with margins that must come back untouch
 import pytest
 import torch
 
-import ref_cpu as R
+from _pe_check import DGRAD_SENTINEL as SENTINEL, MARGIN   # operands, reference and the margined output: shared with test_patch_embed_edges_gpu.py
+from _pe_check import dgrad_operands as _operands, dgrad_reference as _reference, index_map as _index_map, sentinel_out as _sentinel_out
 from _util import assert_exact, dev, exact_operands
 
 pytestmark = pytest.mark.gpu
@@ -24,44 +25,6 @@ GEOMS = [
     pytest.param(4, 4, (64, 32, 128), (4, 8, 64), 128, id="wp64-d128"),
     pytest.param(2, 1, (60, 40, 64), (3, 5, 8), 64, id="pd120-edge-columns"),              # pd = 120 < one 256-wide column tile
 ]
-
-SENTINEL = 12288.0     # 3 * 2^12: exact in bf16
-MARGIN = 4096
-
-
-def _index_map(vol, patch):
-    """[P, pd] int64: the flat voxel index (inside one [D, H, W] volume) of every (token, feature) — the oracle's patchify order."""
-    D, H, W = vol
-    return R.patchify(torch.arange(D * H * W, dtype=torch.int64).reshape(1, D, H, W), patch)[0]
-
-
-def _reference(dx, w, B, M, vol, patch):
-    """fp32 [B, M, 1, D, H, W]: the patch rows of dx @ w (exact) placed on the voxel grid."""
-    P = (vol[0] // patch[0]) * (vol[1] // patch[1]) * (vol[2] // patch[2])
-    rows = dx.reshape(M, B, 1 + P, -1)[:, :, 1:]
-    idx = _index_map(vol, patch).reshape(-1)
-    out = torch.empty(B, M, vol[0] * vol[1] * vol[2])
-    for m in range(M):
-        out[:, m].index_copy_(1, idx, (rows[m].reshape(B * P, -1) @ w).reshape(B, -1))
-    return out.reshape(B, M, 1, *vol)
-
-
-def _sentinel_out(shape, dtype):
-    n = 1
-    for s in shape:
-        n *= s
-    buf = torch.full((n + 2 * MARGIN,), SENTINEL, dtype=dtype, device=dev())
-    return buf, buf[MARGIN:MARGIN + n].view(shape)
-
-
-def _operands(B, M, vol, patch, d, seed):
-    P = (vol[0] // patch[0]) * (vol[1] // patch[1]) * (vol[2] // patch[2])
-    pd = patch[0] * patch[1] * patch[2]
-    dx = exact_operands((M * B * (1 + P), d), seed, 2)
-    w = exact_operands((d, pd), seed + 1, 3)
-    dx.view(M * B, 1 + P, d)[:, 0] = float("nan")          # CLS rows: never stored
-    return dx, w
-
 
 @pytest.mark.parametrize("B,M,vol,patch,d", GEOMS)
 def test_dgrad_bit_exact(B, M, vol, patch, d):
