@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "xvit", "libxvit_hip.so")
 OBJ = os.path.join(HERE, "build")
-SOURCES = ["core.hip", "gemm.hip", "linear_f32.hip", "layernorm.hip", "attention.hip", "attention_fp8.hip", "cls_xattn.hip", "head_linear.hip", "misc.hip", "metrics.hip", "epoch_metrics.hip", "grad_comm.hip", "augment.hip", "elastic.hip", "contrast.hip", "volume_stats.hip", "volume_bbox.hip", "token_select.hip", "token_occupancy.hip", "mae.hip", "mix.hip", "batch_store.hip"]
+SOURCES = ["core.hip", "gemm.hip", "linear_f32.hip", "layernorm.hip", "attention.hip", "attention_fp8.hip", "cls_xattn.hip", "head_linear.hip", "misc.hip", "metrics.hip", "epoch_metrics.hip", "grad_comm.hip", "augment.hip", "elastic.hip", "contrast.hip", "volume_stats.hip", "volume_bbox.hip", "volume_components.hip", "token_select.hip", "token_occupancy.hip", "mae.hip", "mix.hip", "batch_store.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 
 

@@ -4,105 +4,21 @@
 // result does not depend on the execution order.
 #include <math.h>
 
-#include "volume_io.h"
+#include "volume_box.h"
 
 namespace xvit {
 
-constexpr int kBoxThreads = 256;
-constexpr int kBoxWaves = kBoxThreads / kWave;
 constexpr int64_t kBoxMinChunk = 8192;   // voxels: one round of four 16-byte loads per lane of a 16-bit source
 constexpr int kBoxMaxGroups = 2048;      // about eight 256-thread workgroups per CU
 
 // The chunk rule of the header: parts per volume and voxels per part.
-static int bbox_parts(int nvol, int64_t nvox, int64_t* chunk_out) {
+int bbox_parts(int nvol, int64_t nvox, int64_t* chunk_out) {
   const int64_t cap = nvol >= kBoxMaxGroups ? 1 : kBoxMaxGroups / nvol;
   int64_t parts = min(cap, (nvox + kBoxMinChunk - 1) / kBoxMinChunk);
   const int64_t chunk = ((nvox + parts - 1) / parts + 7) & ~(int64_t)7;
   parts = (nvox + chunk - 1) / chunk;   // no empty workgroup
   if (chunk_out) *chunk_out = chunk;
   return (int)parts;
-}
-
-struct Box {
-  int z0, z1, y0, y1, x0, x1, n;   // inclusive; empty: lo = size, hi = -1
-  __device__ __forceinline__ void add(int z, int y, int xa, int xb) {
-    z0 = min(z0, z), z1 = max(z1, z), y0 = min(y0, y), y1 = max(y1, y), x0 = min(x0, xa), x1 = max(x1, xb);
-  }
-  __device__ __forceinline__ void merge(const Box& o) {
-    z0 = min(z0, o.z0), z1 = max(z1, o.z1), y0 = min(y0, o.y0), y1 = max(y1, o.y1), x0 = min(x0, o.x0), x1 = max(x1, o.x1), n += o.n;
-  }
-};
-__device__ __forceinline__ Box empty_box(int Ds, int Hs, int Ws) { return Box{Ds, -1, Hs, -1, Ws, -1, 0}; }
-
-// bit e of the result: element e of the 16-byte run is foreground (NaN compares false)
-template <class S>
-__device__ __forceinline__ uint32_t fg_mask(const uint4& r, float fg) {
-  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (sizeof(S) == 4) {
-      m |= (uint32_t)(__builtin_bit_cast(float, w[i]) > fg) << i;
-    } else if constexpr (std::is_same<S, bf16>::value) {
-      m |= (uint32_t)(__builtin_bit_cast(float, w[i] << 16) > fg) << (2 * i);
-      m |= (uint32_t)(__builtin_bit_cast(float, w[i] & 0xFFFF0000u) > fg) << (2 * i + 1);
-    } else {
-      m |= (uint32_t)((float)(int16_t)(w[i] & 0xFFFFu) > fg) << (2 * i);
-      m |= (uint32_t)((float)(int16_t)(w[i] >> 16) > fg) << (2 * i + 1);
-    }
-  }
-  return m;
-}
-
-// E consecutive voxels from flat index `flat` of the volume, foreground where `mask` is set.  The two divisions are paid by runs that hold
-// foreground only; a run that crosses a row end walks its elements.
-template <int E>
-__device__ __forceinline__ void add_run(Box& b, uint32_t mask, uint32_t flat, int Hs, int Ws) {
-  if (mask == 0) return;
-  const uint32_t row = flat / (uint32_t)Ws, z = row / (uint32_t)Hs;
-  int x = (int)(flat - row * (uint32_t)Ws), y = (int)(row - z * (uint32_t)Hs), zi = (int)z;
-  b.n += __popc(mask);
-  if (E == 1 || x + E <= Ws) {
-    b.add(zi, y, x + (__ffs(mask) - 1), x + (31 - __clz(mask)));
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      if ((mask >> e) & 1u) b.add(zi, y, x, x);
-      if (++x == Ws) {
-        x = 0;
-        if (++y == Hs) y = 0, ++zi;
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ Box wave_merge(Box b) {
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    Box o;
-    o.z0 = __shfl_xor(b.z0, d), o.z1 = __shfl_xor(b.z1, d), o.y0 = __shfl_xor(b.y0, d), o.y1 = __shfl_xor(b.y1, d);
-    o.x0 = __shfl_xor(b.x0, d), o.x1 = __shfl_xor(b.x1, d), o.n = __shfl_xor(b.n, d);
-    b.merge(o);
-  }
-  return b;
-}
-// every thread gets the workgroup's box; the leading barrier lets consecutive calls share `red`
-__device__ __forceinline__ Box block_merge(Box b, int4* red) {
-  b = wave_merge(b);
-  __syncthreads();
-  if (lane_id() == 0) {
-    red[2 * (threadIdx.x >> 6)] = int4{b.z0, b.z1, b.y0, b.y1};
-    red[2 * (threadIdx.x >> 6) + 1] = int4{b.x0, b.x1, b.n, 0};
-  }
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < kBoxWaves; ++w) {
-    const int4 p = red[2 * w], q = red[2 * w + 1];
-    const Box o{p.x, p.y, p.z, p.w, q.x, q.y, q.z};
-    if (w == 0) b = o;
-    else b.merge(o);
-  }
-  return b;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -212,6 +128,12 @@ __global__ void __launch_bounds__(kBoxThreads) volume_bbox_finish_kernel(const i
   }
 }
 
+void launch_volume_bbox_finish(const int4* partial, int nvol, int M, int per_vol, int Ds, int Hs, int Ws, int D, int H, int W, const xvit_crop_config& cfg,
+                               int4* boxes, int4* crop, float* params, hipStream_t s) {
+  hipLaunchKernelGGL(volume_bbox_finish_kernel, dim3((unsigned)(nvol / M)), dim3(kBoxThreads), 0, s, partial, M, per_vol, Ds, Hs, Ws, D, H, W, cfg, boxes, crop,
+                     params);
+}
+
 }  // namespace xvit
 
 extern "C" int64_t xvit_volume_bbox_workspace_bytes(int nvol, int64_t nvox) {
@@ -245,7 +167,6 @@ extern "C" int xvit_volume_bbox(const void* src, int src_dtype, int nvol, int M,
     hipLaunchKernelGGL(xvit::volume_bbox_kernel<S>, dim3((unsigned)((int64_t)nvol * per_vol)), dim3(xvit::kBoxThreads), 0, s, (const S*)src, (int4*)workspace, nvox,
                        per_vol, chunk, Ds, Hs, Ws, cfg->foreground_above);
   });
-  hipLaunchKernelGGL(xvit::volume_bbox_finish_kernel, dim3((unsigned)(nvol / M)), dim3(xvit::kBoxThreads), 0, s, (const int4*)workspace, M, per_vol, Ds, Hs, Ws, D, H,
-                     W, *cfg, (int4*)boxes, (int4*)crop, params);
+  xvit::launch_volume_bbox_finish((const int4*)workspace, nvol, M, per_vol, Ds, Hs, Ws, D, H, W, *cfg, (int4*)boxes, (int4*)crop, params, s);
   return xvit::check_launch("xvit_volume_bbox");
 }

@@ -24,6 +24,6 @@ from .model_cross import (Attention, CrossAttention, CrossAttentionBlock, FeedFo
 from .metrics import BinaryEpochMetrics, EpochMetrics  # noqa: F401
 from . import interpret  # noqa: F401   (attention maps and rollout: xvit.interpret.attention_maps)
 from . import augment  # noqa: F401     (the augmenting input stage: xvit.augment.VolumeAugment)
-from .augment import AugmentParams, ContrastAugment, ContrastParams, ForegroundBoxes, VolumeAugment  # noqa: F401
+from .augment import AugmentParams, ContrastAugment, ContrastParams, ForegroundBoxes, ForegroundComponents, VolumeAugment  # noqa: F401
 from . import data  # noqa: F401        (the device-resident volume store: xvit.data.VolumeStore, xvit.data.BatchSampler)
 from .mae import MaskedVolumeModel  # noqa: F401   (masked-volume pretraining around a ModelCross encoder)

@@ -83,6 +83,16 @@ BBOX_NREC = 8                                          # XVIT_BBOX_NREC
 BBOX_Z0, BBOX_Z1, BBOX_Y0, BBOX_Y1, BBOX_X0, BBOX_X1, BBOX_COUNT = 0, 1, 2, 3, 4, 5, 6   # XVIT_BBOX_*
 CROP_BOXES_ONLY, CROP_CENTER, CROP_FIT = 0, 1, 2       # XVIT_CROP_*
 AUG_CROP_SCALE = 31                                    # XVIT_AUG_CROP_SCALE
+
+
+class ComponentConfig(C.Structure):
+    """struct xvit_component_config (include/xvit.h)."""
+    _fields_ = [("connectivity", i32), ("keep", i32), ("min_voxels", i32), ("foreground_above", f32)]
+
+
+CC_NREC = 8                                            # XVIT_CC_NREC
+CC_COUNT, CC_LARGEST_ROOT, CC_LARGEST_SIZE, CC_KEPT, CC_KEPT_VOXELS, CC_STATUS = 0, 1, 2, 3, 4, 5   # XVIT_CC_*: the slots of a comps record
+CC_LARGEST, CC_MIN_VOXELS = 0, 1                       # XVIT_CC_LARGEST, XVIT_CC_MIN_VOXELS: the keep modes
 MAE_MAX_PD = 8192                                      # XVIT_MAE_MAX_PD: the largest patch (voxels) xvit_mae_loss_fwd holds in LDS
 TOKEN_SELECT_MAX_P = 8192                              # XVIT_TOKEN_SELECT_MAX_P: the longest sequence xvit_token_select_draw ranks in LDS
 TOKEN_RANK_RANDOM, TOKEN_RANK_TOP = 0, 1               # XVIT_TOKEN_RANK_*: the modes of xvit_token_select_ranked
@@ -175,6 +185,8 @@ SIGNATURES = {
     "xvit_contrast_apply": [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp],
     "xvit_volume_stats": [vp, i32, i32, i64, C.POINTER(NormConfig), vp, vp, vp, i64, vp],
     "xvit_volume_bbox": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(CropConfig), vp, vp, vp, vp, i64, vp],
+    "xvit_volume_components": [vp, i32, i32, i32, i32, i32, C.POINTER(ComponentConfig), vp, vp, vp, i64, vp],
+    "xvit_volume_bbox_components": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(CropConfig), C.POINTER(ComponentConfig), vp, vp, vp, vp, vp, vp, i64, vp],
     "xvit_set_option": [C.c_char_p, i32],
     "xvit_set_dropout_epoch": [C.c_void_p],
     "xvit_adam_step": [vp, vp, i32, f32, f32, f32, f32, f32, i32, f32, vp],
@@ -189,7 +201,7 @@ SIGNATURES = {
 }
 EXPORTS = sorted(list(SIGNATURES) + ["xvit_version", "xvit_last_error_string", "xvit_gemm_workspace_bytes", "xvit_linear_f32_workspace_bytes",
                                     "xvit_colsum_workspace_bytes", "xvit_layernorm_bwd_workspace_bytes", "xvit_patch_embed_wgrad_workspace_bytes", "xvit_attn_fp8_workspace_bytes",
-                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes", "xvit_volume_bbox_workspace_bytes", "xvit_epoch_rank_stats_max_n"])
+                                    "xvit_attn_fwd_workspace_bytes", "xvit_attn_bwd_workspace_bytes", "xvit_volume_stats_workspace_bytes", "xvit_volume_bbox_workspace_bytes", "xvit_volume_components_workspace_bytes", "xvit_epoch_rank_stats_max_n"])
 
 _lib = None
 
@@ -222,8 +234,9 @@ def load() -> C.CDLL:
         lib.xvit_patch_embed_wgrad_workspace_bytes.restype = C.c_int64
         lib.xvit_volume_stats_workspace_bytes.argtypes = [i32]
         lib.xvit_volume_stats_workspace_bytes.restype = C.c_int64
-        lib.xvit_volume_bbox_workspace_bytes.argtypes = [i32, i64]
-        lib.xvit_volume_bbox_workspace_bytes.restype = C.c_int64
+        for name in ("xvit_volume_bbox_workspace_bytes", "xvit_volume_components_workspace_bytes"):
+            getattr(lib, name).argtypes = [i32, i64]
+            getattr(lib, name).restype = C.c_int64
         lib.xvit_epoch_rank_stats_max_n.argtypes = []
         lib.xvit_epoch_rank_stats_max_n.restype = C.c_int64
         lib.xvit_version.restype = C.c_int

@@ -13,6 +13,9 @@
     aug = xvit.augment.VolumeAugment((128, 128, 128), crop_foreground="fit", crop_margin=4)   # window the foreground, not the volume centre
     aug.last_crop                    # ForegroundBoxes: every volume's foreground box and the crop of every sample
     xvit.augment.foreground_boxes(raw)   # the boxes alone
+    aug = xvit.augment.VolumeAugment((128, 128, 128), crop_foreground="fit", crop_component="largest")   # ... of the largest component only
+    aug.last_crop.components         # ForegroundComponents: every voxel's component label and the per-volume component table
+    xvit.augment.foreground_components(raw)   # the labels and the table alone
 
     con = xvit.augment.ContrastAugment(blur_prob=.2, bias_prob=.2, gamma_prob=.3, seed=0)      # a second stage behind the first
     img = con(aug(raw))              # Gaussian blur, bias field, gamma: one fused kernel, a NEW tensor of the same shape
@@ -31,8 +34,12 @@ window [lo, hi] first, pad_value included: the background lands on the window fl
 crop_foreground="center" | "fit" moves the pad / crop window from the centre of the volume to the bounding box of the sample's foreground
 (include/xvit.h, "Foreground bounding box and crop"; what MONAI's CropForegroundd followed by ResizeWithPadOrCropd or a resize does in a
 loader): two launches that fold the box into the table's A | t between the draw and the statistics fold, so the voxels are still
-interpolated once.  The box is the index range of v > crop_above over all modalities of the sample; nothing filters connected components,
-so one isolated bright background voxel widens it.  The box moves the window and masks nothing.
+interpolated once.  The box is the index range of v > crop_above over all modalities of the sample, so one isolated bright background
+voxel widens it.  crop_component="largest" | n takes the box over the voxels of every volume's largest 6- or 26-connected foreground
+component, or of its components of at least n voxels, instead (include/xvit.h, "Connected foreground components"; what MONAI's
+KeepLargestConnectedComponent or RemoveSmallObjects does in front of CropForegroundd): union-find labelling on the device, seven more
+launches, 4 bytes of labels per source voxel plus as much workspace.  The box moves the window and masks nothing: a dropped component
+that falls inside the window stays in the image.
 """
 from __future__ import annotations
 
@@ -51,6 +58,7 @@ ELASTIC_MAX_GRID, ELASTIC_NREC = _lib.ELASTIC_MAX_GRID, _lib.ELASTIC_NREC
 ELASTIC_FLAG, ELASTIC_U, ELASTIC_MAX_ABS = 0, 1, 2     # slots of an elastic record: enum XVIT_ELASTIC_* of include/xvit.h
 _NORM_MODES = {None: _lib.NORM_STATS_ONLY, "zscore": _lib.NORM_ZSCORE, "window": _lib.NORM_WINDOW}
 BBOX_NREC = _lib.BBOX_NREC
+CC_NREC = _lib.CC_NREC
 _CROP_MODES = {None: _lib.CROP_BOXES_ONLY, "center": _lib.CROP_CENTER, "fit": _lib.CROP_FIT}
 _COUNTER_STRIDE = 0xD1B54A32D192ED03   # seed' = seed + call index * this (mod 2^64): kSeedStride of csrc/xvit_common.h, on the host
 _MASK64 = (1 << 64) - 1
@@ -204,12 +212,13 @@ class ForegroundBoxes:
     z, y, x, its voxel count, zero) and crop [B, 8] (int32; the union over the sample's modalities, widened by the margin and clipped, a
     has-foreground flag, zero).  The tables stay on the device: reading a value is the one host synchronisation."""
 
-    def __init__(self, boxes: torch.Tensor, crop: torch.Tensor):
+    def __init__(self, boxes: torch.Tensor, crop: torch.Tensor, components=None):
         if boxes.dtype != torch.int32 or boxes.dim() != 3 or boxes.shape[2] != BBOX_NREC:
             raise ValueError(f"ForegroundBoxes: need int32 [B, M, {BBOX_NREC}] boxes, got {boxes.dtype} {tuple(boxes.shape)}")
         if crop.dtype != torch.int32 or tuple(crop.shape) != (boxes.shape[0], BBOX_NREC):
             raise ValueError(f"ForegroundBoxes: need an int32 [{boxes.shape[0]}, {BBOX_NREC}] crop, got {crop.dtype} {tuple(crop.shape)}")
         self.boxes, self.crop = boxes, crop
+        self.components = components     # ForegroundComponents when the boxes were taken over kept components, else None
 
     lo = property(lambda s: s.crop[:, 0:6:2])              # [B, 3]: the first index of the sample's crop along z, y, x
     hi = property(lambda s: s.crop[:, 1:6:2])              # ... and the last, inclusive
@@ -219,7 +228,62 @@ class ForegroundBoxes:
     volume_hi = property(lambda s: s.boxes[..., 1:6:2])
 
     def clone(self):
-        return ForegroundBoxes(self.boxes.clone(), self.crop.clone())
+        return ForegroundBoxes(self.boxes.clone(), self.crop.clone(), None if self.components is None else self.components.clone())
+
+
+class ForegroundComponents:
+    """Named views of the outputs of xvit_volume_components: labels [B, M, Ds, Hs, Ws] (int32; the smallest flat index (z Hs + y) Ws + x of
+    a foreground voxel's connected component, -1 for background) and table [B, M, 8] (int32; the number of components, the largest one's
+    root and size, the numbers of kept components and kept voxels, the status, two zeros).  They stay on the device."""
+
+    def __init__(self, labels: torch.Tensor, table: torch.Tensor):
+        if labels.dtype != torch.int32 or labels.dim() != 5:
+            raise ValueError(f"ForegroundComponents: need int32 [B, M, Ds, Hs, Ws] labels, got {labels.dtype} {tuple(labels.shape)}")
+        if table.dtype != torch.int32 or tuple(table.shape) != (*labels.shape[:2], CC_NREC):
+            raise ValueError(f"ForegroundComponents: need an int32 [{labels.shape[0]}, {labels.shape[1]}, {CC_NREC}] table, got {table.dtype} {tuple(table.shape)}")
+        self.labels, self.table = labels, table
+
+    count = property(lambda s: s.table[..., _lib.CC_COUNT])                 # [B, M]: components of every volume
+    largest_root = property(lambda s: s.table[..., _lib.CC_LARGEST_ROOT])   # the label of the largest (-1: no foreground)
+    largest_size = property(lambda s: s.table[..., _lib.CC_LARGEST_SIZE])   # ... and its voxels
+    kept = property(lambda s: s.table[..., _lib.CC_KEPT])                   # components the box was taken over
+    kept_voxels = property(lambda s: s.table[..., _lib.CC_KEPT_VOXELS])     # ... and their voxels
+    status = property(lambda s: s.table[..., _lib.CC_STATUS])               # 0 = fine
+
+    def clone(self):
+        return ForegroundComponents(self.labels.clone(), self.table.clone())
+
+
+def component_config(component="largest", connectivity=6, above=0.0):
+    """_lib.ComponentConfig from the Python arguments ("largest", or an int n >= 1: components of at least n voxels), validated as
+    xvit_volume_components validates it."""
+    if isinstance(component, bool) or not (component == "largest" or (isinstance(component, int) and 1 <= component < 2 ** 31)):
+        raise ValueError(f"crop_component={component!r} must be None, 'largest' or an int >= 1 (components of at least that many voxels)")
+    if isinstance(connectivity, bool) or connectivity not in (6, 26):
+        raise ValueError(f"crop_connectivity={connectivity!r} must be 6 (faces) or 26 (faces, edges, corners)")
+    fg = float(above)
+    if fg != fg:
+        raise ValueError("the foreground threshold is NaN")
+    c = _lib.ComponentConfig()
+    c.connectivity, c.foreground_above = connectivity, fg
+    c.keep, c.min_voxels = (_lib.CC_LARGEST, 1) if component == "largest" else (_lib.CC_MIN_VOXELS, component)
+    return c
+
+
+def _component_tables(raw):
+    """labels, the component table and the workspace for the volumes raw: 4 bytes per voxel, and a little more than that again."""
+    B, M = raw.shape[:2]
+    return (torch.empty(raw.shape, dtype=torch.int32, device=raw.device), torch.empty(B, M, CC_NREC, dtype=torch.int32, device=raw.device),
+            ops.volume_components_workspace(B * M, raw[0, 0].numel(), raw.device))
+
+
+def foreground_components(raw, foreground_above=0.0, connectivity=6) -> ForegroundComponents:
+    """The connected components of the foreground v > foreground_above of raw [B, M, Ds, Hs, Ws] (int16, bf16 or fp32 on the GPU): every
+    voxel's label and the per-volume table (the kept set is the largest component), without a host synchronisation until they are read."""
+    raw = VolumeAugment._volumes(raw)
+    labels, table, workspace = _component_tables(raw)
+    ops.volume_components(raw, component_config("largest", connectivity, foreground_above), labels, table, workspace)
+    return ForegroundComponents(labels, table)
 
 
 def crop_config(mode=None, margin=0, upscale=False, above=0.0):
@@ -237,18 +301,26 @@ def crop_config(mode=None, margin=0, upscale=False, above=0.0):
     return c
 
 
-def _crop_tables(B, M, device):
+def _crop_tables(B, M, device, workspace=True):
     """boxes, crop and a workspace that serves B x M volumes of any size (the chunk rule never gives a volume more parts than an
-    unbounded one gets)."""
+    unbounded one gets); workspace=False: None in its place, for the component path, which brings its own."""
     return (torch.empty(B, M, BBOX_NREC, dtype=torch.int32, device=device), torch.empty(B, BBOX_NREC, dtype=torch.int32, device=device),
-            ops.volume_bbox_workspace(B * M, 2 ** 31 - 1, device))
+            ops.volume_bbox_workspace(B * M, 2 ** 31 - 1, device) if workspace else None)
 
 
-def foreground_boxes(raw, foreground_above=0.0, margin=0) -> ForegroundBoxes:
+def foreground_boxes(raw, foreground_above=0.0, margin=0, component=None, connectivity=6) -> ForegroundBoxes:
     """The foreground boxes of raw [B, M, Ds, Hs, Ws] (int16, bf16 or fp32 on the GPU) over v > foreground_above, and per sample their
-    union widened by margin: two launches, no host synchronisation until the result is read."""
+    union widened by margin: two launches, no host synchronisation until the result is read.  component="largest" | n takes them over the
+    voxels of every volume's largest connected component, or of its components of at least n voxels (connectivity 6 or 26); the result's
+    .components then holds the labels and the component table."""
     raw = VolumeAugment._volumes(raw)
     config = crop_config(None, margin, False, foreground_above)
+    if component is not None:
+        comp = component_config(component, connectivity, foreground_above)
+        boxes, crop, _ = _crop_tables(raw.shape[0], raw.shape[1], raw.device, workspace=False)
+        labels, table, workspace = _component_tables(raw)
+        ops.volume_bbox_components(raw, config, comp, (1, 1, 1), boxes, crop, labels, table, workspace)
+        return ForegroundBoxes(boxes, crop, ForegroundComponents(labels, table))
     boxes, crop, workspace = _crop_tables(raw.shape[0], raw.shape[1], raw.device)
     ops.volume_bbox(raw, config, (1, 1, 1), boxes, crop, workspace)
     return ForegroundBoxes(boxes, crop)
@@ -358,7 +430,15 @@ class VolumeAugment(_CallIndexed):
     over all its modalities and widened by crop_margin voxels (an int or three) inside the volume.  "center" keeps the voxel size (the
     exact copy stays exact); "fit" also zooms out by k = max over the axes of box size / img_size so that the whole box is seen, and
     zooms in (k < 1) only with crop_upscale.  Like normalize it is preprocessing: not random, and it runs in eval() as in train().
-    last_crop holds the ForegroundBoxes of the last call and last_params.crop_scale the k that was folded."""
+    last_crop holds the ForegroundBoxes of the last call and last_params.crop_scale the k that was folded.
+
+    crop_component="largest" | n (an int >= 1) takes every volume's box over its largest connected foreground component, or over its
+    components of at least n voxels (the largest when none has n), with crop_connectivity 6 (faces) or 26 (faces, edges, corners): a
+    speck of noise or a marker far from the head no longer widens the window (xvit.augment.foreground_components; include/xvit.h,
+    "Connected foreground components").  It needs crop_foreground, runs in eval() as in train(), and changes where the window goes only:
+    a dropped component inside the window stays in the image.  It costs seven more launches, 4 bytes of labels per source voxel (571 MB
+    at B = 8, M = 2, 240 x 240 x 155) and a workspace of xvit_volume_components_workspace_bytes (a little more than the labels again);
+    last_crop.components holds the ForegroundComponents of the last call.  With None nothing of it is launched or allocated."""
 
     _WHO = "VolumeAugment"
 
@@ -367,7 +447,7 @@ class VolumeAugment(_CallIndexed):
                  shift_intensity_prob=.5, shift_intensity_range=(-.1, .1), noise_prob=.2, noise_std=.05, intensity_scale=1.0, intensity_shift=0.0,
                  out_dtype=torch.bfloat16, seed=0, capturable=False, normalize=None, foreground_above=0.0, percentiles=(0.005, 0.995), clip=True,
                  elastic_prob=0.0, elastic_control_points=7, elastic_max_displacement=7.5, elastic_locked_borders=2, elastic_allow_folding=False,
-                 crop_foreground=None, crop_margin=0, crop_upscale=False, crop_above=None):
+                 crop_foreground=None, crop_margin=0, crop_upscale=False, crop_above=None, crop_component=None, crop_connectivity=6):
         super().__init__(seed, capturable)
         who = self._WHO
         self.img_size = tuple(int(v) for v in img_size)
@@ -414,6 +494,15 @@ class VolumeAugment(_CallIndexed):
             raise ValueError(f"VolumeAugment: {e}") from None
         self.crop_foreground = crop_foreground
         self._crops = {}           # capturable: the static box tables and workspace per (B, M, device)
+        try:                       # crop_connectivity is checked in any case; it acts with crop_component only
+            comp = component_config("largest" if crop_component is None else crop_component, crop_connectivity, self._crop_config.foreground_above)
+        except ValueError as e:
+            raise ValueError(f"VolumeAugment: {e}") from None
+        if crop_component is not None and crop_foreground is None:
+            raise ValueError("VolumeAugment: crop_component needs crop_foreground='center' or 'fit'")
+        self._component_config = None if crop_component is None else comp
+        self.crop_component, self.crop_connectivity = crop_component, crop_connectivity
+        self._components = {}      # capturable: the static labels, component table and workspace per (volume shape, device)
         self.last_params = None
         self.last_stats = None
         self.last_crop = None
@@ -482,9 +571,21 @@ class VolumeAugment(_CallIndexed):
             self._table(B, M, raw.device)                  # the static buffers are allocated together
             boxes, crop, workspace = self._crops[(B, M, raw.device)]
         else:
-            boxes, crop, workspace = _crop_tables(B, M, raw.device)
-        ops.volume_bbox(raw, self.crop_config, self.img_size, boxes, crop, workspace, table)
-        return ForegroundBoxes(boxes, crop)
+            boxes, crop, workspace = _crop_tables(B, M, raw.device, workspace=self._component_config is None)
+        if self._component_config is None:
+            ops.volume_bbox(raw, self.crop_config, self.img_size, boxes, crop, workspace, table)
+            return ForegroundBoxes(boxes, crop)
+        key = (tuple(raw.shape), raw.device)
+        if not self.capturable:
+            labels, comps, workspace = _component_tables(raw)
+        else:                                                  # static: allocated by the call in front of the capture
+            if key not in self._components:
+                self._components[key] = _component_tables(raw)
+            labels, comps, workspace = self._components[key]
+        ops.volume_bbox_components(raw, self.crop_config, self._component_config, self.img_size, boxes, crop, labels, comps, workspace, table)
+        return ForegroundBoxes(boxes, crop, ForegroundComponents(labels, comps))
+
+    component_config = property(lambda self: self._component_config, doc="_lib.ComponentConfig of crop_component / crop_connectivity, or None")
 
     def draw(self, B, M, vol_shape, device) -> AugmentParams:
         """One table for B x M volumes of vol_shape; advances the call index in training mode."""

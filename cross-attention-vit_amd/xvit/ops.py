@@ -1137,6 +1137,52 @@ def volume_bbox(src, config, img_size, boxes, crop, workspace, params=None):
     return boxes, crop
 
 
+def volume_components_workspace(nvol, nvox, device):
+    """The workspace of volume_components and volume_bbox_components for nvol volumes of nvox voxels
+    (xvit_volume_components_workspace_bytes: the accumulators, one int32 size per voxel and the partial boxes); the calls zero what they
+    need, its contents do not matter on entry."""
+    return torch.empty(_L.xvit_volume_components_workspace_bytes(int(nvol), int(nvox)), dtype=torch.uint8, device=device)
+
+
+def _components_args(src, labels, comps):
+    assert src.dim() == 5 and src.is_contiguous(), f"need contiguous [B, M, Ds, Hs, Ws] volumes, got {tuple(src.shape)}"
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == tuple(src.shape), \
+        f"labels {labels.dtype} {tuple(labels.shape)} do not match the volumes {tuple(src.shape)}"
+    assert comps.dtype == torch.int32 and comps.is_contiguous() and tuple(comps.shape) == (*src.shape[:2], _lib.CC_NREC), \
+        f"comps {comps.dtype} {tuple(comps.shape)} do not match {src.shape[0]} x {src.shape[1]} volumes"
+
+
+def volume_components(src, config, labels, comps, workspace):
+    """xvit_volume_components (include/xvit.h): the connected foreground components of src [B, M, Ds, Hs, Ws] (int16, bf16 or fp32,
+    contiguous).  labels [B, M, Ds, Hs, Ws] (int32): the smallest flat index of a foreground voxel's component, -1 for background; comps
+    [B, M, 8] (int32): the component table.  config: _lib.ComponentConfig.  workspace: volume_components_workspace(B * M, Ds * Hs * Ws,
+    device)."""
+    _components_args(src, labels, comps)
+    B, M, Ds, Hs, Ws = src.shape
+    _call("xvit_volume_components", "volume_components", src.numel() * (float(src.element_size()) + 8.0), "byte", _ptr(src), _src_dt(src), B * M, Ds, Hs, Ws,
+          C.byref(config), _ptr(labels), _ptr(comps), _ptr(workspace), workspace.numel() * workspace.element_size())
+    return labels, comps
+
+
+def volume_bbox_components(src, config, components, img_size, boxes, crop, labels, comps, workspace, params=None):
+    """xvit_volume_bbox_components (include/xvit.h): volume_components, then volume_bbox's boxes, crop and fold over the voxels of the kept
+    components only.  config: _lib.CropConfig; components: _lib.ComponentConfig with the same foreground_above; the other arguments are
+    those of volume_bbox and volume_components."""
+    _components_args(src, labels, comps)
+    B, M, Ds, Hs, Ws = src.shape
+    assert boxes.dtype == torch.int32 and boxes.is_contiguous() and tuple(boxes.shape) == (B, M, _lib.BBOX_NREC), \
+        f"boxes {boxes.dtype} {tuple(boxes.shape)} do not match {B} x {M} volumes"
+    assert crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (B, _lib.BBOX_NREC), \
+        f"crop {crop.dtype} {tuple(crop.shape)} does not match {B} samples"
+    if params is not None:
+        assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (B, M, _lib.AUG_NPARAM)
+    D, H, W = img_size
+    _call("xvit_volume_bbox_components", "volume_bbox_components", src.numel() * (float(src.element_size()) + 12.0), "byte", _ptr(src), _src_dt(src), B * M, M, Ds,
+          Hs, Ws, D, H, W, C.byref(config), C.byref(components), _ptr(boxes), _ptr(crop), _ptr(params), _ptr(labels), _ptr(comps), _ptr(workspace),
+          workspace.numel() * workspace.element_size())
+    return boxes, crop
+
+
 def epoch_metrics_update(logits, labels, scores, labels32, preds, state):
     """xvit_epoch_metrics_update (include/xvit.h): append the step's softmax rows, labels and argmax to the epoch buffers at the device-side
     cursor state[0] and fold it into the integer confusion matrix behind the state head.  logits fp32 [B, C] (rows contiguous), labels

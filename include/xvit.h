@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define XVIT_VERSION 321 /* 0.3.21: the 256x256 GEMM epilogue adds the right residual row for res_row_mod 1 to 3 (xvit_patch_embed_fwd with 1 or 2 tokens per sample, xvit_gemm), no new entry point; 0.3.20: xvit_batch_draw, xvit_batch_gather and XVIT_BATCH_WEIGHTED / XVIT_BATCH_SHUFFLE / XVIT_BATCH_SEQUENTIAL (a device-resident volume store whose batches a captured step draws); 0.3.19: xvit_patch_occupancy, xvit_token_select_ranked and XVIT_TOKEN_RANK_RANDOM / XVIT_TOKEN_RANK_TOP (foreground-ranked token selection for training and eval()); 0.3.18:xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
+#define XVIT_VERSION 322 /* 0.3.22: xvit_volume_components, xvit_volume_bbox_components, xvit_volume_components_workspace_bytes, xvit_component_config, the XVIT_CC_* record and keep modes (connected foreground components: the crop follows the largest component or those of a minimum size); 0.3.21: the 256x256 GEMM epilogue adds the right residual row for res_row_mod 1 to 3 (xvit_patch_embed_fwd with 1 or 2 tokens per sample, xvit_gemm), no new entry point; 0.3.20: xvit_batch_draw, xvit_batch_gather and XVIT_BATCH_WEIGHTED / XVIT_BATCH_SHUFFLE / XVIT_BATCH_SEQUENTIAL (a device-resident volume store whose batches a captured step draws); 0.3.19: xvit_patch_occupancy, xvit_token_select_ranked and XVIT_TOKEN_RANK_RANDOM / XVIT_TOKEN_RANK_TOP (foreground-ranked token selection for training and eval()); 0.3.18:xvit_volume_bbox, xvit_volume_bbox_workspace_bytes, xvit_crop_config, the XVIT_BBOX_* record and XVIT_AUG_CROP_SCALE (record slot 31): foreground bounding box and crop folded into the augmenting input stage's table; 0.3.17: xvit_elastic_draw, xvit_augment_apply_elastic, xvit_elastic_config and the XVIT_ELASTIC_* record (cubic B-spline elastic deformation composed into the augmenting input stage's resample); 0.3.16: xvit_contrast_draw, xvit_contrast_apply, xvit_contrast_config and the XVIT_CON_* record (Gaussian blur, bias field and gamma behind the augmenting input stage); 0.3.15: xvit_epoch_metrics_update, xvit_epoch_rank_stats, xvit_epoch_rank_stats_max_n and the XVIT_EPOCH_* state head (pooled multi-class epoch metrics, exact one-vs-rest AUROC / AP and bootstrap replicates); 0.3.14: xvit_adamw_step, xvit_adamw_step_dev, xvit_ema_swap and the xvit_adamw_extra table: AdamW, per-tensor rates, fused weight EMA; 0.3.13: xvit_mix_draw, xvit_mix_apply, xvit_mean_ce_mix, xvit_mix_config and the XVIT_MIX_* record (Mixup / CutMix with a soft-target loss); 0.3.12: xvit_token_select_complement, xvit_mae_unshuffle_fwd, xvit_mae_unshuffle_bwd, xvit_token_rows_gather, xvit_token_rows_scatter, xvit_mae_loss_fwd, xvit_mae_loss_bwd and XVIT_MAE_MAX_PD (masked-volume pretraining); 0.3.11: xvit_token_select_draw, xvit_patchify_select, xvit_embed_select_fwd, xvit_embed_select_bwd and XVIT_TOKEN_SELECT_MAX_P (patch dropout: training on a random subset of the patch tokens); 0.3.10: xvit_volume_stats, xvit_volume_stats_workspace_bytes, xvit_norm_config, the clamp of xvit_augment_apply (record slots 29, 30, flag bit 1): per-volume intensity normalisation on the device; 0.3.9: xvit_augment_draw, xvit_augment_apply, their parameter record and XVIT_I16 (device-side volume augmentation); 0.3.8: xvit_grad_sqnorm_partials, xvit_adam_prologue, xvit_adam_step_dev and their state record: capturable Adam with fused global-norm clipping; 0.3.7: xvit_patch_embed_dgrad, xvit_patch_embed_dgrad_supported, xvit_unpatchify (input-volume gradient); 0.3.6: xvit_attn_relevance_step (gradient-weighted relevance through a self-attention block); 0.3.5: xvit_attn_rollout_step (attention rollout through a self-attention block); 0.3.4: xvit_grad_pack_bf16, xvit_grad_unpack_bf16 (bf16 gradient communication); 0.3.3: xvit_add_cast_f32_bf16, xvit_rows_combine; 0.3.2: probability dropout in the low-rank fusion (xvit_cls_softmax_*, xvit_head_cols bias_scale, xvit_head_bias_grad), xvit_xattn_kv_wgrad removed; 0.3.1: xvit_set_dropout_epoch; 0.3.0: workspaces in xvit_attn_fwd/bwd (CLS peel), xvit_linear_f32_batched; 0.2.0: ld_alt in xvit_layernorm_fwd/bwd, dropout in xvit_attn_*, xvit_patch_embed_*, xvit_attn_fwd_fp8, xvit_linear_f32, workspaces */
 
 enum { XVIT_OK = 0, XVIT_ERR_ARG = -1, XVIT_ERR_UNSUPPORTED = -2 };
 enum { XVIT_BF16 = 0, XVIT_F32 = 1, XVIT_I16 = 2 /* source volumes of xvit_augment_apply, xvit_volume_stats and xvit_volume_bbox only */ };
@@ -500,8 +500,8 @@ int xvit_volume_stats(const void* src, int src_dtype, int nvol, int64_t nvox, co
  * Boxes.  src [nvol, Ds, Hs, Ws] int16 / bf16 / fp32 (only a comparison is needed, so fp32 is supported here), contiguous, aligned to its
  * element size; a volume has fewer than 2^31 voxels.  F = { (z, y, x) : src[v, z, y, x] > foreground_above }; NaN compares false and is
  * never foreground, -0.0 is not above 0.  boxes [nvol, XVIT_BBOX_NREC] (int32): slots 0..5 the inclusive index range of F along z, y, x
- * (XVIT_BBOX_Z0 .. XVIT_BBOX_X1), slot 6 |F|, slot 7 zero.  A volume without foreground gets lo = size, hi = -1, count 0.  There is no
- * connected-component filtering: one isolated bright background voxel widens the box to itself.
+ * (XVIT_BBOX_Z0 .. XVIT_BBOX_X1), slot 6 |F|, slot 7 zero.  A volume without foreground gets lo = size, hi = -1, count 0.  This box
+ * follows every voxel of F: one isolated bright background voxel widens it to itself ("Connected foreground components" filters that).
  *
  * Sample crop.  The M modalities of a sample (volumes b M .. b M + M - 1; nvol is a multiple of M) are co-registered and share one
  * spatial transform, so they share one box.  crop [nvol / M, XVIT_BBOX_NREC] (int32): the union of the sample's non-empty volume boxes,
@@ -550,6 +550,66 @@ int64_t xvit_volume_bbox_workspace_bytes(int nvol, int64_t nvox);
 int xvit_volume_bbox(const void* src, int src_dtype, int nvol, int M, int Ds, int Hs, int Ws, int D, int H, int W, const xvit_crop_config* cfg,
                      int32_t* boxes /* [nvol, 8] */, int32_t* crop /* [nvol / M, 8] */, float* params /* [nvol, 32]; NULL: no fold */, void* workspace,
                      int64_t workspace_bytes, xvit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Connected foreground components (csrc/volume_components.hip; stands where a loader runs MONAI's KeepLargestConnectedComponent or
+ * RemoveSmallObjects in front of CropForegroundd).  The box of xvit_volume_bbox follows every voxel above the threshold; this takes the
+ * box over the voxels of the kept connected components only, so that a speck of noise, a residue of skull-stripping or a fiducial marker
+ * no longer widens it.  It changes where the window goes and masks nothing: a dropped component that falls inside the window stays in
+ * the image.  The rule is this project's own; parity with MONAI's numerics is NOT claimed.
+ *
+ * Foreground.  The predicate of xvit_volume_bbox: F = { (z, y, x) : src[v, z, y, x] > foreground_above }, strict; NaN is never
+ * foreground; -0.0 is not above 0.  src [nvol, Ds, Hs, Ws] int16 / bf16 / fp32, contiguous, aligned to its element size, nvox = Ds Hs Ws
+ * < 2^31.
+ *
+ * Labels.  labels [nvol, nvox] (int32).  A foreground voxel holds the smallest flat index (z Hs + y) Ws + x of its component; a
+ * background voxel holds -1.  Two foreground voxels are neighbours when they differ by at most one along every axis and, for
+ * connectivity 6, along exactly one axis (faces); for connectivity 26 along one, two or three (faces, edges, corners).  18 is refused.
+ * The smallest index of a component does not depend on the execution order: the labels are bit-reproducible.
+ *
+ * Kept set, per volume.  The size of a component is its number of voxels, an exact integer.
+ *    XVIT_CC_LARGEST      keeps the component of greatest size; a tie goes to the smaller root index.
+ *    XVIT_CC_MIN_VOXELS   keeps every component with at least min_voxels voxels; if none qualifies it keeps the largest (as above), so a
+ *                         volume with foreground never becomes empty.
+ * comps [nvol, XVIT_CC_NREC] (int32): slot 0 the number of components, 1 the largest component's root (-1 without foreground), 2 its
+ * size, 3 the number of kept components, 4 the number of kept voxels, 5 the status (0 = fine; any other value is a defect of the
+ * kernels: a union-find loop reached its step cap, bit 0 in a tile, bit 1 in the merge, bit 2 in the flatten, and the other outputs are
+ * not to be used), 6 and 7 zero.
+ *
+ * Boxes (xvit_volume_bbox_components).  boxes [nvol, XVIT_BBOX_NREC] in xvit_volume_bbox's layout, over the kept voxels only; slot 6 is
+ * the kept-voxel count; a volume without foreground gets lo = size, hi = -1, count 0.  The per-sample union, margin, clip, crop and the
+ * fold into params are those of xvit_volume_bbox, by the same kernel.  cfg->foreground_above must equal comp->foreground_above.
+ *
+ * Launches: zero, tile (an 8 x 8 x 32 tile labelled by union-find in LDS, 16-byte source loads where a run lies inside its row and is
+ * aligned), merge (voxels on tile faces, device-scope atomicMin on the labels), flatten, count (sizes aggregated per wave and workgroup
+ * before one global add per (workgroup, root)), pick (64-bit atomicMax of (size << 32) | (0x7fffffff - root) per workgroup), table;
+ * xvit_volume_bbox_components adds the partial boxes over the labels and xvit_volume_bbox's finish.  A fixed number of launches, no host
+ * read-back, no host loop, no spinning; every device loop has a step cap that reports through the status.  The workspace is zeroed
+ * inside the call, so the sequence can be captured in a graph and replayed.
+ * Memory: labels cost 4 bytes per source voxel (571 MB at 16 volumes of 240 x 240 x 155).  xvit_volume_components_workspace_bytes(nvol,
+ * nvox) = 32 nvol + (4 nvol nvox rounded up to 16) + xvit_volume_bbox_workspace_bytes(nvol, nvox): the accumulators, one int32 size per
+ * voxel (as much again as the labels) and the partial boxes; 16-byte aligned, caller-owned, contents irrelevant on entry.
+ * Argument errors, raised before any launch: null pointers (params may be NULL), an unknown dtype, connectivity other than 6 or 26, an
+ * unknown keep mode, min_voxels < 1 (in either mode), non-positive sizes or nvox >= 2^31, a NaN foreground_above, labels / comps / boxes /
+ * crop / params / workspace not 16-byte aligned, a workspace that is too small, and for xvit_volume_bbox_components what xvit_volume_bbox
+ * refuses.  Both configs are HOST structs, read during the call.
+ * ---------------------------------------------------------------------------------------- */
+#define XVIT_CC_NREC 8
+enum { XVIT_CC_COUNT = 0, XVIT_CC_LARGEST_ROOT = 1, XVIT_CC_LARGEST_SIZE = 2, XVIT_CC_KEPT = 3, XVIT_CC_KEPT_VOXELS = 4, XVIT_CC_STATUS = 5 };
+enum { XVIT_CC_LARGEST = 0, XVIT_CC_MIN_VOXELS = 1 };
+typedef struct xvit_component_config {
+  int connectivity;         /* 6 or 26 */
+  int keep;                 /* XVIT_CC_LARGEST or XVIT_CC_MIN_VOXELS */
+  int min_voxels;           /* >= 1; read by XVIT_CC_MIN_VOXELS */
+  float foreground_above;   /* F = { v > foreground_above }; NaN is never foreground */
+} xvit_component_config;
+int64_t xvit_volume_components_workspace_bytes(int nvol, int64_t nvox);
+int xvit_volume_components(const void* src, int src_dtype, int nvol, int Ds, int Hs, int Ws, const xvit_component_config* cfg, int32_t* labels /* [nvol, nvox] */,
+                           int32_t* comps /* [nvol, 8] */, void* workspace, int64_t workspace_bytes, xvit_stream_t stream);
+int xvit_volume_bbox_components(const void* src, int src_dtype, int nvol, int M, int Ds, int Hs, int Ws, int D, int H, int W, const xvit_crop_config* cfg,
+                                const xvit_component_config* comp, int32_t* boxes /* [nvol, 8] */, int32_t* crop /* [nvol / M, 8] */,
+                                float* params /* [nvol, 32]; NULL: no fold */, int32_t* labels /* [nvol, nvox] */, int32_t* comps /* [nvol, 8] */, void* workspace,
+                                int64_t workspace_bytes, xvit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Contrast augmentations (csrc/contrast.hip): Gaussian blur, a smooth multiplicative bias field and gamma, as a second, independent

@@ -1,10 +1,12 @@
 """Time the augmenting input stage at the reference's input shape: B = 8, M = 2, 240 x 240 x 155 int16 -> 128^3 bf16.
 
-    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE] [--mode stage|elastic|crop]
+    python tools/augment_bench.py [--reps 20] [--inner 10] [--out FILE] [--mode stage|elastic|crop|components]
 
 --mode elastic times elastic deformation against the general path of the same run (see `elastic` below; profiles/elastic_measured.txt).
 --mode crop times the foreground bounding-box pair against the statistics pair of the same run, and the whole stage with and without
 crop_foreground (see `crop` below; profiles/crop_measured.txt).
+--mode components times the connected-component pipeline at connectivity 6 and 26 against the bounding-box pair of the same run, and the
+whole stage with crop_component None / "largest" (see `components` below; profiles/components_measured.txt).
 
 Arms, interleaved inside every repeat (so that drift hits them alike): xvit_resize_pad_crop_i16 (twice: two identical arms), the exact
 path as identity, the exact path with all three flips, the general path (every random transform on), the draw kernel, the statistics pair
@@ -180,12 +182,82 @@ def crop(a) -> int:
     return 0
 
 
+def components(a) -> int:
+    """--mode components: xvit_volume_components and xvit_volume_bbox_components at connectivity 6 and 26 against the xvit_volume_bbox pair
+    (twice: two identical arms) on the brains of --mode crop plus 300 isolated bright voxels per volume, and the whole stage (every random
+    transform on) with crop_foreground "center" / "fit", each with crop_component None and "largest".  Reported, not gated: nothing is
+    asserted of a time.  The kernels of one call are told apart by a kernel trace of this run, not by this tool."""
+    from xvit import ops
+    from xvit.augment import VolumeAugment, _component_tables, _crop_tables, component_config, crop_config
+
+    dev = torch.device("cuda:0")
+    src = brain_volumes(dev)
+    nvox = SRC[0] * SRC[1] * SRC[2]
+    g = torch.Generator().manual_seed(1)
+    flat = src.view(B * M, nvox)
+    for v in range(B * M):
+        flat[v, torch.randint(0, nvox, (300,), generator=g).to(dev)] = 3000
+    on = dict(flip_prob=(1, 1, 1), rotate_prob=1, zoom_prob=1, translate_prob=1, scale_intensity_prob=1, shift_intensity_prob=1, noise_prob=0, intensity_scale=1e-3)
+    stages = {(c, k): VolumeAugment(DST, crop_foreground=c, crop_component=k, **on) for c in ("center", "fit") for k in (None, "largest")}
+    box_cfg = crop_config(None, 0, False, 0.0)
+    boxes, crop_t, _ = _crop_tables(B, M, dev)
+    box_ws = ops.volume_bbox_workspace(B * M, nvox, dev)
+    labels, comps, ws = _component_tables(src)
+    cfgs = {c: component_config("largest", c, 0.0) for c in (6, 26)}
+    ops.volume_bbox(src, box_cfg, DST, boxes, crop_t, box_ws)
+    plain_extent = (crop_t[:, 1:6:2] - crop_t[:, 0:6:2] + 1).float().mean(0).tolist()
+    ops.volume_bbox_components(src, box_cfg, cfgs[6], DST, boxes, crop_t, labels, comps, ws)
+    kept_extent = (crop_t[:, 1:6:2] - crop_t[:, 0:6:2] + 1).float().mean(0).tolist()
+    assert int(comps[..., 5].abs().sum()) == 0, "status"
+    ncomp, kept_frac = comps[..., 0].float().mean().item(), float(comps[..., 4].sum()) / (B * M * nvox)
+
+    bbox = lambda: ops.volume_bbox(src, box_cfg, DST, boxes, crop_t, box_ws)      # noqa: E731
+    arms = [("bounding-box pair", bbox)]
+    for c in (6, 26):
+        arms += [(f"components alone, connectivity {c}", lambda c=c: ops.volume_components(src, cfgs[c], labels, comps, ws)),
+                 (f"components + boxes + finish, connectivity {c}", lambda c=c: ops.volume_bbox_components(src, box_cfg, cfgs[c], DST, boxes, crop_t, labels, comps, ws))]
+    arms += [(f"stage, crop={c}, component={k}", lambda st=st: st(src)) for (c, k), st in stages.items()]
+    arms += [("bounding-box pair (again)", bbox)]
+    times = interleaved(arms, a.reps, a.inner)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    raw_bytes, label_bytes = src.numel() * 2, src.numel() * 4
+    least = raw_bytes + 2 * label_bytes                  # the source read once, the labels written once and read once
+    lines = [f"augment_bench --mode components: B={B} M={M} {SRC} int16 -> {DST} bf16; ellipsoid brains plus 300 bright voxels per volume: {ncomp:.0f} components per "
+             f"volume at connectivity 6, {100 * kept_frac:.1f} % of the voxels in the largest; mean crop {plain_extent[0]:.0f} x {plain_extent[1]:.0f} x {plain_extent[2]:.0f} "
+             f"voxels unfiltered, {kept_extent[0]:.0f} x {kept_extent[1]:.0f} x {kept_extent[2]:.0f} over the largest component; labels {label_bytes / 1e6:.0f} MB, workspace "
+             f"{ws.numel() / 1e6:.0f} MB; {a.reps} repeats x {a.inner} calls per arm, interleaved; device-event microseconds per call"]
+    for name, _ in arms:
+        t = times[name]
+        rate = f"  {raw_bytes / med[name] / 1e3:8.1f} GB/s of source" if "pair" in name else f"  {least / med[name] / 1e3:8.1f} GB/s of least traffic" if "components" in name else ""
+        lines.append(f"  {name:48s} median {med[name]:9.2f} us  (min {min(t):9.2f}, max {max(t):9.2f}){rate}")
+    same = ("bounding-box pair", "bounding-box pair (again)")
+    spread = max(max(times[n]) - min(times[n]) for n in same)
+    pair = min(med[n] for n in same)
+    lines.append(f"  least traffic of the component pipeline: {least / 1e6:.0f} MB (source once, labels written once and read once); at the 6.3 TB/s a copy reaches that is "
+                 f"{least / 6.3e12 * 1e6:.0f} us; spread between the two identical bounding-box arms' repeats {spread:.2f} us")
+    for c in (6, 26):
+        full = med[f"components + boxes + finish, connectivity {c}"]
+        lines.append(f"  connectivity {c}: components + boxes + finish is {full / pair:.1f} x the bounding-box pair of this run ({full - pair:+.2f} us), "
+                     f"{full / (least / 6.3e12 * 1e6):.1f} x its least traffic at 6.3 TB/s")
+    for c in ("center", "fit"):
+        lines.append(f"  stage with crop={c}, component=largest - stage with component=None: "
+                     f"{med[f'stage, crop={c}, component=largest'] - med[f'stage, crop={c}, component=None']:+.2f} us "
+                     f"({med[f'stage, crop={c}, component=largest'] / med[f'stage, crop={c}, component=None']:.2f} x)")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--mode", choices=("stage", "elastic", "crop"), default="stage")
+    ap.add_argument("--mode", choices=("stage", "elastic", "crop", "components"), default="stage")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("augment_bench: needs a GPU; a CPU run measures nothing")
@@ -193,6 +265,8 @@ def main() -> int:
         return elastic(a)
     if a.mode == "crop":
         return crop(a)
+    if a.mode == "components":
+        return components(a)
     from xvit import ops
     from xvit.augment import NSTAT, AugmentParams, VolumeAugment, norm_config
 
